@@ -59,16 +59,15 @@ def measure_traffic_now(targets, budget_s=240):
         return "rocprofv3 not on PATH"
     if any(k in os.environ for k in ("ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB", "ROCPROFILER_REGISTER_FORCE_LOAD")):
         return "this process runs under a profiler"
-    out = os.path.join(ROOT, "gpurun_out", "pmc_bench_run.json")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
+    import tempfile
     try:
-        os.remove(out)
-    except OSError:
-        pass
-    try:
-        subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_record.py"), *targets, "--hbm-only", "--tag",
-                        "benchrun", "--out", out, "--timeout", "60"], capture_output=True, text=True, timeout=budget_s)
-        _PMC_NOW.update(json.load(open(out)))
+        # outside the checkout: the tree the bench runs from need not be writable
+        with tempfile.TemporaryDirectory(prefix="tfhe_bench_pmc_") as d:
+            out = os.path.join(d, "pmc_bench_run.json")
+            subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_record.py"), *targets, "--hbm-only", "--tag",
+                            "benchrun", "--out", out, "--dir", d, "--timeout", "60"], capture_output=True, text=True,
+                           timeout=budget_s)
+            _PMC_NOW.update(json.load(open(out)))
         return None
     except Exception as e:  # noqa: BLE001
         return f"in-run PMC passes failed ({e.__class__.__name__})"
@@ -122,6 +121,27 @@ def pmc_counters(target):
 
 
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 4   # wave-instructions per second: 256 CUs x 4 SIMDs, one 4-cycle VALU instruction at a time
+
+# rows of the headline output written by --dump-outputs: 3 arrays x 1024 x 2049 words x 8 bytes = 50 MB, under the 64 MB cap
+DUMP_ROWS = 1024
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: what the caller of the timed launch receives — its output LWE ciphertexts, `out` [B][kN + 1] u64 —
+    as float64 .npy files, a fixed seeded sample of DUMP_ROWS rows when B is larger (the rows' indices in
+    pbs_out_rows.npy).  A u64 torus word does not fit a float64: each is written exactly as its two 32-bit halves
+    (pbs_out_hi32, pbs_out_lo32), and as the centred torus value word / 2^64 in [-1/2, 1/2) for a comparison with a
+    tolerance (pbs_out_torus)."""
+    import numpy as np
+    n = len(out)
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    s = np.ascontiguousarray(out[rows], dtype=np.uint64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("pbs_out_rows", rows.astype(np.float64)),
+                    ("pbs_out_hi32", (s >> np.uint64(32)).astype(np.float64)),
+                    ("pbs_out_lo32", (s & np.uint64(0xFFFFFFFF)).astype(np.float64)),
+                    ("pbs_out_torus", s.view(np.int64).astype(np.float64) / 2.0 ** 64)):
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 class HeadlineShard:
@@ -368,8 +388,13 @@ def main():
     ap.add_argument("--scale-quick", action="store_true",
                     help="headline only (= --no-extra --no-cpu-baseline --no-pmc): the form for a 1/2/4/8-GPU scaling sweep — no CPU-oracle "
                          "legs (they are 95 %% of the default run's wall time), per-GPU ms_per_step and config 5's active-GPU count in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output ciphertexts (shard 0 of a multi-GPU run) to "
+                         "DIR/*.npy as float64, a fixed sample of 1024 rows when the batch is larger")
     ap.add_argument("--fheuint64-worker", default=None, help=argparse.SUPPRESS)  # child process of the N > 1 config-5 datapoints
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.scale_quick:
         args.no_extra = args.no_cpu_baseline = args.no_pmc = True
     if args.fheuint64_worker:
@@ -458,6 +483,8 @@ def main():
     bsk, d_in, d_lut, idx, lidx, buf, cts, lut, msgs = (sh.bsk, sh.d_in, sh.d_lut, sh.idx, sh.lidx, sh.buf, sh.cts,
                                                         sh.lut, sh.msgs)
     single = n_gpus == 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sh.outputs())   # nothing has been launched into d_out since the last timed step
 
     # ---- single-PBS latency (outside the timed region; the reference publishes this figure)
     latency_ms = None

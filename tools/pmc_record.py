@@ -2,7 +2,7 @@
 """PMC passes over ONE batch-4096 launch of each throughput kernel of the path, written as a record that
 bench.py can tie to the build it runs (profiles/pmc_latest.json, stamped with tools/build_id.py).
 
-Run on the GPU box:   python tools/pmc_record.py [fft ntt mb_g3 ...] [--tag r02]
+Run on the GPU box:   python tools/pmc_record.py [fft ntt mb_g3 ...] [--tag r02] [--out record.json] [--dir raw_output_dir]
 For every target the launch is profiled in separate rocprofv3 --pmc passes (counters only; never combined
 with the sys/hip/hsa trace domains), as MI355X_MICROARCH.md prescribes.  HBM bytes per launch =
 2 x FETCH_SIZE + WRITE_SIZE (the guide's gfx950 correction for 16-byte coalesced reads: FETCH_SIZE tallies
@@ -75,7 +75,7 @@ def main():
     global PASSES
     argv = sys.argv[1:]
     opts = {}
-    for name in ("--tag", "--out", "--timeout"):
+    for name in ("--tag", "--out", "--timeout", "--dir"):
         if name in argv:
             i = argv.index(name)
             opts[name] = argv[i + 1]
@@ -93,6 +93,8 @@ def main():
     per_pass_timeout = float(opts.get("--timeout", 600))
     targets = [a for a in argv if not a.startswith("--")] or ["fft", "ntt", "mb_g3", "mb_g4"]
     out_dir = os.path.join(ROOT, "gpurun_out")
+    if "--dir" in opts:   # raw passes elsewhere: bench.py's run may come from a checkout it cannot write to
+        out_dir = opts["--dir"]
     os.makedirs(out_dir, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
     record = {"build_id": source_build_id(), "batch": 4096, "kernels": {}, "provenance": provenance(),
