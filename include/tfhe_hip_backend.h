@@ -652,6 +652,13 @@ void hip_backend_set_ntt_kernel(uint32_t which);
  * 5 exact, 6 wave multi-bit, 7 block (latency), 8 block dual-stream, 9 wave f64 for N = 1024,
  * 10 multi-bit latency path, 11 reference-order f64 engine, 12 NTT engine in its two-prime FP64 form */
 uint32_t hip_backend_last_pbs_kernel(void);
+/* the template instantiation the last PBS launch took, for tests: out[0] the kernel id above, out[1] template level
+ * count L, out[2] template base_log B (0, 0: the run-time decomposition form), out[3] template grouping factor G (0:
+ * classic or run-time), out[4] mode (0 plain, 1 SHARE, 2 OCTET, 3 LIMBS, 4 single-level digit path, 5 one group per
+ * polynomial, 6 accumulator in device memory, 7 / 8 multi-bit products on the block kernel with the keybundles in slot /
+ * position order), out[5] LWEs per workgroup, out[6] the kernel's N, out[7] its k + 1.  A call with two launches reports
+ * the one that runs the external products. */
+void hip_backend_last_pbs_instantiation(uint32_t *out8);
 /* last 64-bit keyswitch, for tests: 0 scalar kernels, 1 one-launch matrix-core kernel, 2 digit pass + staged GEMM,
  * 3 staged GEMM on the digits the previous bootstrap emitted */
 uint32_t hip_backend_last_keyswitch_path(void);

@@ -216,3 +216,50 @@ def generate_many_lut(p: Params, functions):
     body[:half] = (np.uint64(0) - body[:half])
     body = np.roll(body, -half)
     return np.concatenate([np.zeros(p.k * p.N, dtype=np.uint64), body]), max_degree, sub
+
+
+# ---------------------------------------------------------------- the reference's parameter sets on N = 1024 / 2048
+# Every KS-PBS set of tfhe/src/shortint/parameters/v1_*/{classic,multi_bit}/**/ks_pbs*.rs on a ring of 1024 or 2048
+# coefficients has one of the twelve bootstrap shapes below (the other fields — n, noise, keyswitch, message/carry —
+# do not change which kernel runs, apart from n, which is cut to a toy size in the tests).  One set per shape is
+# restated with its citation; `count` is the number of sets of that shape across v1_0 .. v1_7 (aliases included).
+@dataclasses.dataclass(frozen=True)
+class RefShape:
+    name: str           # one set of the shape
+    cite: str           # where it is defined
+    n: int
+    k: int
+    N: int
+    pbs_base_log: int
+    pbs_level: int
+    grouping: int       # 0: classic
+    count: int
+
+
+_P = "tfhe/src/shortint/parameters/"
+REFERENCE_PBS_SHAPES = [
+    RefShape("V1_1_PARAM_MESSAGE_2_CARRY_2_KS_PBS_TUNIFORM_2M128",
+             _P + "v1_1/classic/tuniform/p_fail_2_minus_128/ks_pbs.rs:40-69", 918, 1, 2048, 23, 1, 0, 45),
+    RefShape("V1_0_PARAM_MESSAGE_1_CARRY_2_COMPACT_PK_KS_PBS_GAUSSIAN_2M128",
+             _P + "v1_0/classic/compact_pk/gaussian/p_fail_2_minus_128/ks_pbs.rs:75-107", 885, 2, 1024, 23, 1, 0, 24),
+    RefShape("V1_0_PARAM_MULTI_BIT_GROUP_2_MESSAGE_1_CARRY_3_KS_PBS_GAUSSIAN_2M64",
+             _P + "v1_0/multi_bit/gaussian/p_fail_2_minus_64/ks_pbs.rs:83-106", 834, 1, 2048, 15, 2, 2, 1),
+    RefShape("V1_0_PARAM_MULTI_BIT_GROUP_2_MESSAGE_2_CARRY_2_KS_PBS_GAUSSIAN_2M64",
+             _P + "v1_0/multi_bit/gaussian/p_fail_2_minus_64/ks_pbs.rs:258-281", 872, 1, 2048, 22, 1, 2, 21),
+    RefShape("V1_0_PARAM_MULTI_BIT_GROUP_2_MESSAGE_1_CARRY_1_KS_PBS_GAUSSIAN_2M128",
+             _P + "v1_0/multi_bit/gaussian/p_fail_2_minus_128/ks_pbs.rs:8-31", 784, 2, 1024, 22, 1, 2, 20),
+    RefShape("V1_1_PARAM_GPU_MULTI_BIT_GROUP_3_MESSAGE_2_CARRY_2_KS_PBS_TUNIFORM_2M128",
+             _P + "v1_1/multi_bit/tuniform/p_fail_2_minus_128/ks_pbs_gpu.rs:118-137", 879, 1, 2048, 14, 2, 3, 1),
+    RefShape("V1_1_PARAM_MULTI_BIT_GROUP_3_MESSAGE_2_CARRY_2_KS_PBS_GAUSSIAN_2M128",
+             _P + "v1_1/multi_bit/gaussian/p_fail_2_minus_128/ks_pbs.rs:138-161", 891, 1, 2048, 15, 2, 3, 4),
+    RefShape("V1_0_PARAM_MULTI_BIT_GROUP_3_MESSAGE_1_CARRY_2_KS_PBS_GAUSSIAN_2M64",
+             _P + "v1_0/multi_bit/gaussian/p_fail_2_minus_64/ks_pbs.rs:958-981", 807, 1, 2048, 22, 1, 3, 22),
+    RefShape("V1_0_PARAM_MULTI_BIT_GROUP_3_MESSAGE_1_CARRY_1_KS_PBS_GAUSSIAN_2M128",
+             _P + "v1_0/multi_bit/gaussian/p_fail_2_minus_128/ks_pbs.rs:109-132", 783, 2, 1024, 22, 1, 3, 16),
+    RefShape("V1_0_PARAM_MULTI_BIT_GROUP_4_MESSAGE_1_CARRY_3_KS_PBS_GAUSSIAN_2M64",
+             _P + "v1_0/multi_bit/gaussian/p_fail_2_minus_64/ks_pbs.rs:1883-1906", 836, 1, 2048, 14, 2, 4, 1),
+    RefShape("V1_4_PARAM_GPU_MULTI_BIT_GROUP_4_MESSAGE_1_CARRY_1_KS_PBS_TUNIFORM_2M128",
+             _P + "v1_4/multi_bit/tuniform/p_fail_2_minus_128/ks_pbs_gpu.rs:23-42", 760, 1, 2048, 22, 1, 4, 40),
+    RefShape("V1_0_PARAM_GPU_MULTI_BIT_GROUP_4_MESSAGE_1_CARRY_1_KS_PBS_GAUSSIAN_2M128",
+             _P + "v1_0/multi_bit/gaussian/p_fail_2_minus_128/ks_pbs_gpu.rs:209-232", 752, 2, 1024, 22, 1, 4, 4),
+]

@@ -20,6 +20,7 @@ inline void set_device(uint32_t gpu_index) { HX_CHECK(hipSetDevice((int)gpu_inde
 
 std::atomic<uint32_t> g_fft_kernel_choice{0};
 std::atomic<uint32_t> g_last_pbs_kernel{0};
+std::atomic<uint32_t> g_last_pbs_inst[7];  // L, B, G, mode, LWEs per workgroup, N, K1 (note_pbs_instantiation)
 
 constexpr uint32_t kPbsMagic = 0x50425331;   // "PBS1"
 constexpr uint32_t kMbMagic = 0x4d425031;    // "MBP1"
@@ -105,6 +106,20 @@ PbsArgs make_args(void *lwe_array_out, void const *lwe_output_indexes, void cons
   return a;
 }
 }  // namespace
+
+namespace tfhe_hip {
+void note_pbs_instantiation(uint32_t L, uint32_t B, uint32_t G, uint32_t mode, uint32_t lwes_per_wg, uint32_t N,
+                            uint32_t K1) {
+  const uint32_t v[7] = {L, B, G, mode, lwes_per_wg, N, K1};
+  set_pbs_instantiation(v);
+}
+void get_pbs_instantiation(uint32_t out7[7]) {
+  for (int i = 0; i < 7; ++i) out7[i] = g_last_pbs_inst[i].load();
+}
+void set_pbs_instantiation(const uint32_t in7[7]) {
+  for (int i = 0; i < 7; ++i) g_last_pbs_inst[i].store(in7[i]);
+}
+}  // namespace tfhe_hip
 
 extern "C" {
 
@@ -668,6 +683,8 @@ void hip_programmable_bootstrap_ntt64_split_async(void *stream, uint32_t gpu_ind
   }
   launch_pbs_ntt_split_wave(S(stream), a, b->fft);
   if (twin != nullptr) {
+    uint32_t inst[7];
+    get_pbs_instantiation(inst);  // what hip_backend_last_pbs_instantiation reports: the split-key launch, not the redo
     PbsArgs r = a;
     r.bsk = twin;
     r.acc_scratch = nullptr;
@@ -677,6 +694,7 @@ void hip_programmable_bootstrap_ntt64_split_async(void *stream, uint32_t gpu_ind
     r.only_flagged = b->split_bad;
     r.recomputed = b->split_flag + 1;
     launch_pbs_ntt_generic(S(stream), polynomial_size, glwe_dimension, r, b->ntt);
+    set_pbs_instantiation(inst);
   }
   g_last_pbs_kernel.store(13);
 }
@@ -1114,6 +1132,10 @@ void hip_backend_set_keyswitch_kernel(uint32_t which) {
 void hip_backend_set_ntt_kernel(uint32_t which) { g_ntt_kernel_serial = (which == 1); }
 void hip_backend_set_multibit_latency_groups(uint32_t groups) { g_multibit_latency_groups.store(groups); }
 uint32_t hip_backend_last_pbs_kernel(void) { return g_last_pbs_kernel.load(); }
+void hip_backend_last_pbs_instantiation(uint32_t *out8) {
+  out8[0] = g_last_pbs_kernel.load();
+  get_pbs_instantiation(out8 + 1);
+}
 uint32_t hip_backend_last_keyswitch_path(void) { return g_last_keyswitch_path.load(); }
 void hip_backend_set_keyswitch_kparts(uint32_t parts) { g_keyswitch_kparts.store(parts ? parts : 1); }
 const char *hip_backend_version(void) {

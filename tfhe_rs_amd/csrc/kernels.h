@@ -66,6 +66,24 @@ bool stream_is_capturing(hipStream_t st);  // keyswitch.hip: the stream is recor
 void ksd_release_stream(int device, hipStream_t st);  // the large-batch keyswitch's per-stream scratch
 extern bool g_ntt_kernel_serial;
 
+// test hook behind hip_backend_last_pbs_instantiation (abi.hip): the template instantiation the last PBS launch took.
+// Every launcher of a PBS kernel records it on the host as it launches; nothing of it reaches a kernel.
+enum PbsInstMode : uint32_t {
+  PBS_INST_PLAIN = 0,
+  PBS_INST_SHARE = 1,   // multi-bit wave kernel: quads of waves share the key loads of two LWEs
+  PBS_INST_OCTET = 2,   // multi-bit wave kernel: all eight waves share the key loads of four LWEs
+  PBS_INST_LIMBS = 3,   // wave kernel in the exact engine's split-key form
+  PBS_INST_L1 = 4,      // N = 1024 wave kernel: the single-level digit path
+  PBS_INST_PAR = 5,     // generic kernels: one thread group per GLWE polynomial
+  PBS_INST_BIG = 6,     // generic kernels for N >= 8192: accumulator in device memory
+  PBS_INST_SLOTS = 7,   // multi-bit latency path, products on the block kernel: keybundles in the key's slot order
+  PBS_INST_BLOCK = 8,   // ... the same in position order
+};
+void note_pbs_instantiation(uint32_t L, uint32_t B, uint32_t G, uint32_t mode, uint32_t lwes_per_wg, uint32_t N,
+                            uint32_t K1);
+void get_pbs_instantiation(uint32_t out7[7]);
+void set_pbs_instantiation(const uint32_t in7[7]);
+
 // small helpers — ciphertext.hip
 void launch_iota_u64(hipStream_t st, uint64_t *out, uint32_t count);  // out[i] = i
 void launch_modulus_switch(hipStream_t st, uint64_t *out, const uint64_t *in, uint32_t size, uint32_t log_modulus);

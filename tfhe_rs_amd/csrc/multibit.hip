@@ -444,6 +444,7 @@ static void launch_mb_latency(hipStream_t st, const MultiBitArgs &m, const FftTa
       HX_LAUNCH((mb_keybundle_kernel<N, K1, MB_KB_TILE>), dim3(gpass * kb_polys, (a.num_samples + MB_KB_TILE - 1) / MB_KB_TILE),
                 dim3(GenericCfg<N>::TPB), MB_KB_TILE * 16 * sizeof(uint32_t), st, a, m.grouping_factor, kb_lat, tb, g0,
                 group_chunk);
+    if (!block_products) note_pbs_instantiation(0, 0, 0, par ? PBS_INST_PAR : PBS_INST_PLAIN, 1, N, K1);
     if (block_products)
       // the latency kernel's structure (registers + wave-local exchanges, 4 barriers per product)
       launch_mb_accumulate_block(st, a, tb, (const cplx *)kb_lat, acc_g, group_chunk, gpass, (int)(g0 == 0),
@@ -461,6 +462,7 @@ template <int N, int K1>
 static void launch_mb(hipStream_t st, const MultiBitArgs &m, const FftTables &tb) {
   const size_t smem = (size_t)K1 * N * 8 + fbuf_bytes(N);
   hx_set_dynamic_smem_once<pbs_multi_bit_kernel<N, K1>>(smem);
+  note_pbs_instantiation(0, 0, 0, PBS_INST_PLAIN, 1, N, K1);
   HX_LAUNCH((pbs_multi_bit_kernel<N, K1>), dim3(m.pbs.num_samples), dim3(GenericCfg<N>::TPB), smem, st, m.pbs,
             m.grouping_factor, tb);
 }
@@ -469,6 +471,7 @@ static void launch_mb_big(hipStream_t st, const MultiBitArgs &m, const FftTables
   HX_PANIC_IF_FALSE(m.pbs.acc_scratch != nullptr, "multi-bit PBS scratch of a polynomial_size >= 8192 set has no accumulator buffer");
   const size_t smem = fbuf_bytes(N);
   hx_set_dynamic_smem_once<pbs_multi_bit_kernel<N, 2, true>>(smem);
+  note_pbs_instantiation(0, 0, 0, PBS_INST_BIG, 1, N, 2);
   HX_LAUNCH((pbs_multi_bit_kernel<N, 2, true>), dim3(m.pbs.num_samples), dim3(GenericCfg<N>::TPB), smem, st, m.pbs,
             m.grouping_factor, tb);
 }

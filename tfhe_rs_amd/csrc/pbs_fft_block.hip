@@ -621,12 +621,14 @@ template <int L, int B>
 static void launch_block_t(hipStream_t st, const PbsArgs &a, const FftTables &tb) {
   using namespace blockk;
   hx_set_dynamic_smem_once<pbs_fft_block_kernel<L, B>>(SMEM_BYTES);
+  note_pbs_instantiation(L, B, 0, PBS_INST_PLAIN, 1, 2048, 2);
   HX_LAUNCH((pbs_fft_block_kernel<L, B>), dim3(a.num_samples), dim3(TPB), SMEM_BYTES, st, a, tb, MbLatArgs{});
 }
 
 template <int L, int B>
 static void launch_block_mb_t(hipStream_t st, const PbsArgs &a, const FftTables &tb, const blockk::MbLatArgs &mb) {
   using namespace blockk;
+  note_pbs_instantiation(L, B, 0, mb.slots ? PBS_INST_SLOTS : PBS_INST_BLOCK, 1, 2048, 2);
   if (mb.slots) {
     hx_set_dynamic_smem_once<pbs_fft_block_kernel<L, B, true, true>>(SMEM_MB_BYTES);
     HX_LAUNCH((pbs_fft_block_kernel<L, B, true, true>), dim3(a.num_samples), dim3(TPB), SMEM_MB_BYTES, st, a, tb, mb);
@@ -655,6 +657,7 @@ template <int L, int B>
 static void launch_block2_t(hipStream_t st, const PbsArgs &a, const FftTables &tb) {
   using namespace blockk;
   hx_set_dynamic_smem_once<pbs_fft_block2_kernel<L, B>>(SMEM2_BYTES);
+  note_pbs_instantiation(L, B, 0, PBS_INST_PLAIN, 1, 2048, 2);
   HX_LAUNCH((pbs_fft_block2_kernel<L, B>), dim3(a.num_samples), dim3(TPB2), SMEM2_BYTES, st, a, tb);
 }
 

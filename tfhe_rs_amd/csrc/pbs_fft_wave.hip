@@ -2401,6 +2401,7 @@ static void launch_wave_t(hipStream_t st, const PbsArgs &a, const FftTables &tb)
   hx_set_dynamic_smem_once<pbs_fft_wave_kernel<L, B>>(SMEM_BYTES);
   const unsigned per_block = lwes_per_block(a.num_samples);
   const unsigned blocks = (a.num_samples + per_block - 1) / per_block;
+  note_pbs_instantiation(L, B, 0, PBS_INST_PLAIN, per_block, 2048, 2);
   HX_LAUNCH((pbs_fft_wave_kernel<L, B>), dim3(blocks), dim3(128 * per_block), SMEM_BYTES, st, a, tb);
 }
 
@@ -2418,6 +2419,7 @@ static void launch_split_t(hipStream_t st, const PbsArgs &a, const FftTables &tb
 #if WAVE_SPLIT_PACE
   if (a.pace) HX_CHECK(hipMemsetAsync(a.pace, 0, 8 * 32 * sizeof(uint32_t), st));
 #endif
+  note_pbs_instantiation(1, B, 0, PBS_INST_LIMBS, per_block, 2048, 2);
   HX_LAUNCH((pbs_fft_wave_kernel<1, B, 0, false, NTT_SPLIT_LIMBS>), dim3(blocks), dim3(128 * per_block), SMEM_BYTES, st, a,
             tb);
 }
@@ -2444,6 +2446,7 @@ static void launch_wave_mb_t(hipStream_t st, const PbsArgs &a, const FftTables &
   if constexpr ((L == 1 || (L >= 2 && WAVE_MB_OCTET >= 2)) && WAVE_MB_OCTET != 0) {
     if (per_block == 4 && share && !a.mb_no_octet) {
       hx_set_dynamic_smem_once<pbs_fft_wave_kernel<L, B, G, false, 0, true>>(SMEM_BYTES);
+      note_pbs_instantiation(L, B, G, PBS_INST_OCTET, per_block, 2048, 2);
       HX_LAUNCH((pbs_fft_wave_kernel<L, B, G, false, 0, true>), dim3(blocks), dim3(512), SMEM_BYTES, st, a, tb);
       return;
     }
@@ -2451,9 +2454,11 @@ static void launch_wave_mb_t(hipStream_t st, const PbsArgs &a, const FftTables &
   // an even number of LWEs per workgroup: quads of waves share the key loads of their two LWEs (SHARE)
   if (per_block % 2 == 0 && share) {
     hx_set_dynamic_smem_once<pbs_fft_wave_kernel<L, B, G, true>>(SMEM_BYTES);
+    note_pbs_instantiation(L, B, G, PBS_INST_SHARE, per_block, 2048, 2);
     HX_LAUNCH((pbs_fft_wave_kernel<L, B, G, true>), dim3(blocks), dim3(128 * per_block), SMEM_BYTES, st, a, tb);
   } else {
     hx_set_dynamic_smem_once<pbs_fft_wave_kernel<L, B, G>>(SMEM_BYTES);
+    note_pbs_instantiation(L, B, G, PBS_INST_PLAIN, per_block, 2048, 2);
     HX_LAUNCH((pbs_fft_wave_kernel<L, B, G>), dim3(blocks), dim3(128 * per_block), SMEM_BYTES, st, a, tb);
   }
 }

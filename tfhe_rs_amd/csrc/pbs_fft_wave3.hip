@@ -622,6 +622,7 @@ static void launch_wave3_t(hipStream_t st, const PbsArgs &a, const FftTables &tb
   const unsigned blocks = (a.num_samples + per_block - 1) / per_block;
   const size_t smem = smem_bytes((int)(per_block * K1));
   const bool l1 = a.level == 1 && a.base_log >= 1 && a.base_log <= 30;
+  note_pbs_instantiation(0, 0, 0, l1 ? PBS_INST_L1 : PBS_INST_PLAIN, per_block, 1024, K1);
   if (l1) {
     hx_set_dynamic_smem_once<pbs_fft_wave3_kernel<K1, true>>(smem_bytes(MAX_WAVES));
     HX_LAUNCH((pbs_fft_wave3_kernel<K1, true>), dim3(blocks), dim3(64 * per_block * K1), smem, st, a, tb, per_block);

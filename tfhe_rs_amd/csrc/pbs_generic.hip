@@ -470,12 +470,14 @@ static void launch_fft_big(hipStream_t st, const PbsArgs &a, const FftTables &tb
   HX_PANIC_IF_FALSE(a.acc_scratch != nullptr, "PBS scratch of a polynomial_size >= 8192 set has no accumulator buffer");
   const size_t smem = fbuf_bytes(N);
   hx_set_dynamic_smem_once<pbs_fft_generic_kernel<N, 2, true>>(smem);
+  note_pbs_instantiation(0, 0, 0, PBS_INST_BIG, 1, N, 2);
   HX_LAUNCH((pbs_fft_generic_kernel<N, 2, true>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a, tb);
 }
 template <int N, int K1>
 static void launch_fft(hipStream_t st, const PbsArgs &a, const FftTables &tb) {
   // one group per polynomial pays off for k = 1 (43.5k PBS/s at 2_2); with three groups (k = 2, N = 1024) the
   // larger workgroup costs more occupancy than the shorter barrier chain returns (45.9k vs 59.0k): single group
+  note_pbs_instantiation(0, 0, 0, (g_ntt_kernel_serial || K1 != 2) ? PBS_INST_PLAIN : PBS_INST_PAR, 1, N, K1);
   if (g_ntt_kernel_serial || K1 != 2) {
     const size_t smem = (size_t)K1 * N * 8 + fbuf_bytes(N);
     hx_set_dynamic_smem_once<pbs_fft_generic_kernel<N, K1>>(smem);
@@ -488,6 +490,7 @@ static void launch_fft(hipStream_t st, const PbsArgs &a, const FftTables &tb) {
 }
 template <int N, int K1>
 static void launch_ntt(hipStream_t st, const PbsArgs &a, const NttTables &tb) {
+  note_pbs_instantiation(0, 0, 0, (g_ntt_kernel_serial || K1 != 2) ? PBS_INST_PLAIN : PBS_INST_PAR, 1, N, K1);
   if (g_ntt_kernel_serial || K1 != 2) {  // same rule as the f64 engine above
     const size_t smem = (size_t)(K1 + 1) * N * 8;
     hx_set_dynamic_smem_once<pbs_ntt_generic_kernel<N, K1>>(smem);
@@ -527,6 +530,7 @@ template <int N, int K1>
 static void launch_exact(hipStream_t st, const PbsArgs &a) {
   const size_t smem = (size_t)(K1 + 1) * N * 8;
   hx_set_dynamic_smem_once<pbs_exact_generic_kernel<N, K1>>(smem);
+  note_pbs_instantiation(0, 0, 0, PBS_INST_PLAIN, 1, N, K1);
   HX_LAUNCH((pbs_exact_generic_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a);
 }
 void launch_pbs_exact_generic(hipStream_t st, uint32_t N, uint32_t glwe_dim, const PbsArgs &a) {

@@ -195,6 +195,7 @@ template <int N, int K1>
 static void launch_ref(hipStream_t st, const PbsArgs &a, const RefTables &tb) {
   const size_t smem = (size_t)K1 * N * 8 + (size_t)N * 16;
   hx_set_dynamic_smem_once<pbs_ref64_kernel<N, K1>>(smem);
+  note_pbs_instantiation(0, 0, 0, PBS_INST_PLAIN, 1, N, K1);
   HX_LAUNCH((pbs_ref64_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a, tb);
 }
 template <int N>

@@ -124,6 +124,7 @@ SIGNATURES = {
         (None, [_v, _u32, _v, _v, _v, _v, _v, _v, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32]),
     "hip_backend_set_fft_kernel": (None, [_u32]),
     "hip_backend_last_pbs_kernel": (_u32, []),
+    "hip_backend_last_pbs_instantiation": (None, [C.POINTER(C.c_uint32)]),
     "hip_backend_trim_allocator": (_u64, [_u32]),
     "hip_backend_allocator_stats": (None, [_u32, C.POINTER(C.c_uint64)]),
     "hip_backend_redzone_checks": (_u64, [_u32]),
