@@ -210,7 +210,7 @@ struct alignas(16) cplx {
 // STREAM: read-once data (nontemporal).
 template <bool STREAM = false>
 HX_DEV cplx load_global_cplx(const cplx *p) {
-#if defined(TFHE_HIPEMU) || defined(HX_KEY_FLAT_LOADS)  // (the second: A/B knob of tools/build_variants.py)
+#if defined(TFHE_HIPEMU)
   return *p;
 #else
   typedef double v2d __attribute__((ext_vector_type(2)));

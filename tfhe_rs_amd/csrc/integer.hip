@@ -1606,7 +1606,7 @@ void cuda_add_lwe_ciphertext_vector_inplace_64(void *stream, uint32_t gpu_index,
 
 // The carry tree's first bootstrap holds two functions in its accumulator, so a block's value must stay below
 // msg * carry / 2: at most 2 msg - 2 (two clean blocks added), one more for block 0 of an integer when an input carry
-// is added to it.  A caller that tracks degrees gets the call refused instead of a wrong result.
+// is added to it.  A caller that tracks degrees gets the call refused instead of an incorrect result.
 static void check_propagation_degrees(const CudaRadixCiphertextFFI *ct, uint32_t msg, bool /*with_carry_in*/,
                                       uint32_t /*blocks_per_integer*/, const char *who) {
   if (ct == nullptr || ct->degrees == nullptr) return;

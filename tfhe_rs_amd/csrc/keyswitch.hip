@@ -542,34 +542,27 @@ __global__ void __launch_bounds__(256) ks_digits_kernel(int8_t *aplanes, int32_t
   }
 }
 
-// steps of 32 k between two workgroup barriers of ks_gemm_kernel, by key word size: measured per 4096 LWEs on one box,
-// u64 keys 0.373 / 0.307 / 0.325 ms with 1 / 2 / 4 (4 fills the 64 KB of static LDS), u32 keys 0.279 / 0.216 / 0.203 ms
-#ifndef KSG_STEPS_PER_BARRIER_U64
-#define KSG_STEPS_PER_BARRIER_U64 2
-#endif
-#ifndef KSG_STEPS_PER_BARRIER_U32
-#define KSG_STEPS_PER_BARRIER_U32 4
-#endif
 template <typename OutT, int SPB>
 __global__ void ks_gemm_kernel(OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in, const uint64_t *in_idx,
                                const int8_t *planes, const uint64_t *colsum, const int8_t *aplanes, const int32_t *suma,
                                uint32_t n_in, uint32_t n_out, uint32_t base_log, uint32_t num_samples, uint32_t col_tiles,
                                uint32_t steps, const OutT *ksk_raw, size_t ksk_words);
-// the widest supported step count per barrier that divides `steps`
+// the widest supported step count per barrier that divides `steps`.  Steps of 32 k between two workgroup barriers, by key
+// word size: measured per 4096 LWEs on one box, u64 keys 0.373 / 0.307 / 0.325 ms with 1 / 2 / 4 (4 fills the 64 KB of
+// static LDS), u32 keys 0.279 / 0.216 / 0.203 ms
 template <typename OutT, typename... Args>
 static void launch_ks_gemm(dim3 grid, hipStream_t st, uint32_t steps, Args... args) {
-  constexpr int WANT = sizeof(OutT) == 8 ? KSG_STEPS_PER_BARRIER_U64 : KSG_STEPS_PER_BARRIER_U32;
+  constexpr int WANT = sizeof(OutT) == 8 ? 2 : 4;
   if (WANT >= 4 && steps % 4 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 4>), grid, dim3(256), 0, st, args...);
   else if (WANT >= 2 && steps % 2 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 2>), grid, dim3(256), 0, st, args...);
   else HX_LAUNCH((ks_gemm_kernel<OutT, 1>), grid, dim3(256), 0, st, args...);
 }
 // SPB = steps of 32 k per workgroup barrier: with 2 the barrier, the drain of the global -> LDS loads in front of it and
 // the LDS round trip behind it are paid once per 16 matrix instructions instead of once per 8 (32 KB of LDS for u64 keys)
-#ifndef KS_GEMM_MIN_WAVES
-#define KS_GEMM_MIN_WAVES 2  // waves per SIMD the register budget is cut for (2: 256 registers; the u64 forms spill 40-61 in their epilogue)
-#endif
+// The register budget is cut for 2 waves per SIMD (256 registers; the u64 forms spill 40-61 in their epilogue): one wave
+// per SIMD without spills measured 0.31 -> 0.46 ms per 4096 (profiles/r06_ab_keyswitch_register_cap.txt).
 template <typename OutT, int SPB>
-__global__ void __launch_bounds__(256, KS_GEMM_MIN_WAVES) ks_gemm_kernel(OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
+__global__ void __launch_bounds__(256, 2) ks_gemm_kernel(OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
                                                       const uint64_t *in_idx, const int8_t *planes,
                                                       const uint64_t *colsum, const int8_t *aplanes,
                                                       const int32_t *suma, uint32_t n_in, uint32_t n_out,
@@ -636,22 +629,13 @@ __global__ void __launch_bounds__(256, KS_GEMM_MIN_WAVES) ks_gemm_kernel(OutT *l
       for (int p = 0; p < PLANES; ++p) bv[p] = *(const hx_i8x16 *)&bs[cur][u][h][p * (KSM_CT * 16) + row * 16];
       HX_SCHED_FENCE();
       if (u == SPB - 1) {
-#ifndef KSG_SKIP_B  // (timing experiments: wrong results)
         stage_b(nx, cur ^ 1);
-#endif
-#ifndef KSG_SKIP_A
         HX_UNROLL
         for (int v = 0; v < SPB; ++v) a1[v] = ap[((size_t)nx * SPB + v) * 64];
-#endif
       }
       HX_SCHED_FENCE();
-#ifndef KSG_SKIP_MFMA
       HX_UNROLL
       for (int p = 0; p < PLANES; ++p) acc[p] = hx_mfma_i32_32x32x32_i8(av[u], bv[p], acc[p]);
-#else
-      HX_UNROLL
-      for (int p = 0; p < PLANES; ++p) acc[p].v[0] += bv[p].w[0] ^ av[u].w[0];
-#endif
       HX_SCHED_FENCE();
     }
     HX_UNROLL

@@ -121,9 +121,7 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB)
 // ciphertext per workgroup 32 ciphertexts re-read the 241 MB key 32 times from L2 (2.5 ms for a round of 32 blocks
 // of the radix layer).  Same combine order per ciphertext: identical bits.
 constexpr int MB_KB_TILE = 8;  // from 4 ciphertexts up; below, one ciphertext per workgroup (S = 1)
-#ifndef MB_KB_SLOTS_FROM
-#define MB_KB_SLOTS_FROM 17
-#endif
+constexpr uint32_t MB_KB_SLOTS_FROM = 17;  // batch size from which the keybundles stay in the key's slot order (see the use)
 template <int N, int K1, int S>
 __global__ void __launch_bounds__(GenericCfg<N>::TPB)
     mb_keybundle_kernel(PbsArgs a, uint32_t grouping, cplx *kb_lat, FftTables tb, uint32_t g0, uint32_t gcount) {
@@ -420,7 +418,7 @@ static void launch_mb_latency(hipStream_t st, const MultiBitArgs &m, const FftTa
     // From MB_KB_SLOTS_FROM ciphertexts on the keybundles stay in the key's slot order (the latency kernel reads them
     // like a classic key): the keybundle kernel drops its slot -> position transposition, 4-10 % of a round of 32-256
     // blocks; below, position order — one 64-byte run per thread and row is worth 3 % to a PBS that runs alone
-    const bool slots = block_products && a.num_samples >= (uint32_t)MB_KB_SLOTS_FROM;
+    const bool slots = block_products && a.num_samples >= MB_KB_SLOTS_FROM;
     if (N == 2048 && K1 == 2 && a.num_samples < 4) {
       if (slots)
         HX_LAUNCH((mb_keybundle_2048_kernel<1, true>), dim3(gpass * kb_polys, a.num_samples), dim3(256), 0, st, a,

@@ -33,230 +33,10 @@
 #include "kernels.h"
 #include <type_traits>
 
-// tuning knobs (tools/build_variants.py rebuilds this file with other values)
-#ifndef WAVE_EARLY_CHUNKS
-#define WAVE_EARLY_CHUNKS 1  // key chunks requested at the top of an iteration (0, 1 or 2); the rest at the MAC
-#endif
-// Issue priority of a wave by phase of its CMUX iteration (s_setprio, 0..3).  The two waves that share a
-// SIMD belong to different LWEs; with equal priority they interleave instruction by instruction and tend
-// to reach their LDS round trips and pair waits together.  Raising the priority as the iteration advances
-// lets the wave that is further along run through (its partner wave is waiting for it), while the other
-// one fills the gaps: measured 102.6 k -> 117 k PBS/s; the order matters (digits < forward, inverse >= MAC),
-// see profiles/r01_setprio_variants.txt.
-#ifndef WAVE_MAC_PREFETCH
-#define WAVE_MAC_PREFETCH 0  // measured: 0 -> 117.9 k, 2 -> 117.4 k, 4 -> 117.4 k, 8 -> 117.2 k PBS/s (the partner wave already covers the LDS latency)
-#endif
-#ifndef WAVE_PRIO_A
-#define WAVE_PRIO_A 0  // rotation + digits
-#endif
-#ifndef WAVE_PRIO_B
-#define WAVE_PRIO_B 1  // forward transform
-#endif
-#ifndef WAVE_PRIO_C
-#define WAVE_PRIO_C 2  // pair exchange + MAC
-#endif
-#ifndef WAVE_PRIO_D
-#define WAVE_PRIO_D 3  // inverse transform, conversion, accumulation
-#endif
-#ifndef WAVE_PRIO_MB_A
-#define WAVE_PRIO_MB_K 0  // multi-bit: keybundle build (key streaming)
-#define WAVE_PRIO_MB_A 1
-#define WAVE_PRIO_MB_B 2
-#define WAVE_PRIO_MB_C 3
-#define WAVE_PRIO_MB_D 3
-#endif
-// optional finer steps inside the transforms (-1: keep the phase's level)
-#ifndef WAVE_PRIO_F3
-#define WAVE_PRIO_F3 -1
-#endif
-#ifndef WAVE_PRIO_I3
-#define WAVE_PRIO_I3 -1
-#endif
-#ifndef WAVE_PRIO_CONV
-#define WAVE_PRIO_CONV -1
-#endif
-#if !defined(TFHE_HIPEMU)
-#define HX_PRIO_OPT(p) do { if ((p) >= 0) __builtin_amdgcn_s_setprio((p) < 0 ? 0 : (p)); } while (0)
-#else
-#define HX_PRIO_OPT(p) do { } while (0)
-#endif
 #if !defined(TFHE_HIPEMU)
 #define HX_PRIO(p) __builtin_amdgcn_s_setprio(p)
 #else
 #define HX_PRIO(p) do { } while (0)
-#endif
-#ifndef WAVE_FLAG_SLEEP
-#define WAVE_FLAG_SLEEP 1  // s_sleep argument between two polls of a pair flag
-#endif
-#ifndef WAVE_MB_PTS
-#define WAVE_MB_PTS 2   // multi-bit: points per lane and row of one keybundle step (16 / PTS chunks per level)
-#endif
-#ifndef WAVE_MB_PACE
-#define WAVE_MB_PACE 1  // multi-bit: groups a wave pair may run ahead of the slowest pair of its XCD, plus 1 (0: no pacing)
-#endif
-#ifndef WAVE_MB_PACE_OCTET
-// ... in OCTET mode (0: none).  With a wave working for all four LWEs of its workgroup and the touch of the next group's key
-// lines below, the workgroups of an XCD do better unpaced: the first to arrive at a line fetches it for the others
-// (g = 4 / g = 3 per 4096, same box: paced 20.8 / 36.5 ms, unpaced 20.6 / 35.9)
-#define WAVE_MB_PACE_OCTET 0
-#endif
-#ifndef WAVE_MB_PACE_AT_KEY
-// multi-bit pacing: 1 = a wave waits for its XCD right in front of the group's first key request (digits and forward transform
-// do not touch the key: they run under the wait for the slower workgroups) and reports a group as soon as its last key
-// request is out; 0 = wait at the top of the group, report at its end (rounds 3-5)
-#define WAVE_MB_PACE_AT_KEY 0
-#endif
-#ifndef WAVE_MB_PACE_SLEEP
-#define WAVE_MB_PACE_SLEEP 2  // s_sleep argument between two polls of the XCD's counter (64 cycles each)
-#endif
-#ifndef WAVE_MB_PACE_SPINS
-#define WAVE_MB_PACE_SPINS 4096  // polls (with s_sleep) before a wave gives up pacing for the rest of the launch
-#endif
-#ifndef WAVE_MB_TURNS
-#define WAVE_MB_TURNS 0  // SHARE: the two quads of a workgroup take the multiply-accumulate in turns (measured slower: 60 vs 54 ms)
-#endif
-#ifndef WAVE_MB_SHARE_SETS
-// SHARE: register sets in rotation (a request = the 2 rows of one point and subset); 0: two for one level, three for
-// several (one box, g = 3 / g = 4 per 4096: 2 -> 48.8 / 29.8 ms, 3 -> 43.8 / 30.3, 4 -> 43.0 / 30.7, 5 -> 43.9 / 31.3)
-#define WAVE_MB_SHARE_SETS 0
-#endif
-#ifndef WAVE_MB_OCTET
-#define WAVE_MB_OCTET 2  // four LWEs per workgroup: the eight waves share every key load (1: one-level sets only, 2: also the sets with a compile-time level count >= 2)
-#endif
-#ifndef WAVE_MB_OCTET_K_FIRST
-// OCTET: 1 = the keybundle (which depends on the mask and the key only) is combined BEFORE the barrier that publishes the
-// eight transforms, so the waves meet once per group (barrier, products, barrier) and run free in between
-#define WAVE_MB_OCTET_K_FIRST 0
-#endif
-#ifndef WAVE_MB_PREFETCH
-#define WAVE_MB_PREFETCH 1  // multi-bit (pair and quad modes): a load per wave and group touches the next group's key lines
-#endif
-#ifndef WAVE_MB_EXPERIMENT
-#define WAVE_MB_EXPERIMENT 0  // timing experiments (wrong results): bit 0 = every base request reads one of 16 rows of the table, bit 1 = no scalar root loads, bit 2 = no base requests (OCTET)
-#endif
-#if WAVE_MB_EXPERIMENT & 1
-#define MB_EXP_ROW(d) ((d) & 15u)
-#else
-#define MB_EXP_ROW(d) (d)
-#endif
-#ifndef WAVE_MB_OCTET2_K_FIRST
-// OCTET, several levels: 1 = the level's barrier behind the first point's keybundle (which needs the key and the mask only)
-// instead of in front of it: a wave that is early combines instead of waiting (g = 3 per 4096, same box: 36.77 -> 36.04 ms
-// and 35.71 -> 35.47, profiles/r06_ab_multibit.txt section 10)
-#define WAVE_MB_OCTET2_K_FIRST 1
-#endif
-#ifndef WAVE_MB_PF_DIST
-#define WAVE_MB_PF_DIST 1  // ... of the group this many groups ahead
-#endif
-#ifndef WAVE_MB_PF_POS
-#define WAVE_MB_PF_POS 0  // ... issued 0: in front of the inverse transform, 1: at the top of the group
-#endif
-#ifndef WAVE_MB_PREFETCH_OCTET
-// the same touch in OCTET mode: 0 never, 1 always, 2 for the sets with several levels only (g = 3, two levels: 40.3 -> 36.5 ms
-// per 4096; g = 4, one level: 20.9 -> 21.2)
-#define WAVE_MB_PREFETCH_OCTET 2
-#endif
-#ifndef WAVE_MB_OCTET_SETS
-#define WAVE_MB_OCTET_SETS 3  // OCTET: register sets in rotation (a request = the 2 rows of one point and subset)
-#endif
-#ifndef WAVE_MB_SETS
-#define WAVE_MB_SETS 4  // multi-bit: register sets in rotation (SETS - 1 key requests in flight)
-#endif
-#ifndef WAVE_MB_BASES
-// multi-bit monomial bases requested 0: once per group (held across the digit and transform phases: the two-level g = 3
-// kernel then spills 55 registers, 8 dword stores + loads per wave and level), 1: per level ahead of the level's key
-// requests (no spills), 2: per level behind the first key requests (no spills); -1: 1 for several levels, 0 for one.
-// With the bases as 64 scattered table entries per request (rounds 2-3) 0 won everywhere (g = 3 / g = 4: 0 -> 46.5 /
-// 33.4 ms, 1 -> 48.5 / 35.4, 2 -> 48.2 / 35.6: the gathers in front of the multiply-accumulate cost more than the
-// spills); with the lane-order table (one coalesced 1 KB request, tables.h mono_lane) g = 3 / g = 4 on one box:
-// 0 -> 45.1 / 30.2 ms, 1 -> 43.8 / 30.4, 2 -> 43.8 / 30.6: the two-level kernel takes 1 (and spills nothing).
-#define WAVE_MB_BASES -1
-#endif
-#ifndef WAVE_MB_W16_SCALAR
-// multi-bit: the 16th roots of unity that complete the monomial factors (wave-uniform index) come through the scalar
-// data cache (1) instead of as broadcast reads of the LDS table (0): 2 (2^g - 1) reads per point fewer — at g = 4 as
-// many LDS instructions as the whole rest of a group
-#define WAVE_MB_W16_SCALAR 1
-#endif
-#ifndef WAVE_MB_ROOT_JIT
-// multi-bit, scalar 16th roots: 1 = the degree is fenced (HX_OPAQUE_S) right where its root is fetched, so the address of every
-// root of a level (2 (2^g - 1) x 8 or 16 pointers) is computed just in time instead of all at once at the top of the level —
-// hoisted, they do not fit the scalar file and travel through vector-register lanes (g = 3 quad kernel: 337 spilled SGPRs,
-// ~700 v_writelane / v_readlane per group)
-#define WAVE_MB_ROOT_JIT 1
-#endif
-#ifndef WAVE_SPLIT_LWES
-#define WAVE_SPLIT_LWES 4   // exact engine, split-key form: LWEs per workgroup (the accumulators of a CU's LWEs live in L2)
-#endif
-#ifndef WAVE_STAGGER
-// classic one-level loop: waves 4..7 (the second wave of every SIMD) start the loop this many times 4096 cycles after
-// waves 0..3, so that the two waves of a SIMD are in different phases of the CMUX (0: off).  Same box, ms per 4096,
-// eight interleaved pairs of runs (profiles/r04_ab_stagger*.txt): 0 -> 33.50 / 32.40, 1 -> 33.33 / 32.20 (-0.5 %),
-// 2 -> 32.50, 3 -> 32.24
-#define WAVE_STAGGER 1
-#endif
-#ifndef WAVE_SPLIT_PROBE
-#define WAVE_SPLIT_PROBE 0  // timing probes of the split-key loop (wrong results): see the uses
-#endif
-#ifndef WAVE_SPLIT_PACE
-// exact engine, split-key form: CMUXes a wave pair may run ahead of the slowest pair of its XCD, plus 1 (0: no pacing).
-// Unpaced, the 32 workgroups of an XCD drift apart over the 918 iterations and each pulls its own 256 KB key slice
-// through an L2 that the CU-resident accumulators (4 MB per XCD) already fill
-#define WAVE_SPLIT_PACE 0
-#endif
-#ifndef WAVE_FUSE_PASS1
-#define WAVE_FUSE_PASS1 1    // first inverse pass interleaved with the MAC chunks
-#endif
-#ifndef WAVE_UNIFORM_LITERALS
-// 1: the twiddles that are the same in every lane and every launch (forward d = 0..3, inverse half = 4, 8: 12 of the
-// 118 16-byte LDS reads of an iteration) are literals of the instruction stream (scalar moves) instead of broadcast
-// reads of the LDS table; the inverse butterflies whose twiddle is 1 or -i lose their two products (same roundings:
-// fma(x, 1, y) = x + y).  The values are checked against the host tables when the tables are built (tables.hip).
-#define WAVE_UNIFORM_LITERALS 1
-#endif
-// ... per loop: the classic one-level loop (measured: 34.6 -> 33.3 ms per 4096 with the resident twiddles below), the
-// multi-bit loops, the split-key exact engine (measured slower with literals: 150.3 -> 156.0 ms per 4096 — the kernel
-// already spills, the literals' scalar moves add to it)
-#ifndef WAVE_LIT_MB
-#define WAVE_LIT_MB 2  // 1: plain literals, 2: literals made where they are used (lit_cplx)
-#endif
-#ifndef WAVE_SPLIT_EARLY_RESTORE
-// split-key engine: handshakes posted early / waited for late (see the limb step).  Same box, ms per 4096: 115.28 -> 114.73
-// (profiles/r05_ab_split_restore.txt) — the pair waits are cheap, as in the classic loop:
-#define WAVE_SPLIT_EARLY_RESTORE 1
-#endif
-#ifndef WAVE_DEFER_DONE
-// classic one-level loop: the "done" wait in front of the inverse transposition's first store instead of behind the products:
-// 32.17 -> 32.16 ms per 4096, three interleaved rounds (profiles/r05_ab_classic_defer.txt): not kept
-#define WAVE_DEFER_DONE 0
-#endif
-#ifndef WAVE_CLASSIC_SYNC
-// classic loop: the same barrier (0: none).  Same box, ms per 4096, three interleaved rounds: none 33.27, every 4 / 16 / 64:
-// 34.30 / 33.42 / 33.27 (profiles/r05_ab_classic_sync.txt) — its 60 MB key stays in L2 either way
-#define WAVE_CLASSIC_SYNC 0
-#endif
-#ifndef WAVE_SPLIT_SYNC
-// split-key engine: a bare workgroup barrier every so many mask elements (0: none) keeps the four LWEs of a workgroup on the
-// same key rows.  Same box, ms per 4096, two interleaved rounds: none 121.0, every 1 / 4 / 8 / 16 / 32: 119.4 / 118.6 /
-// 119.1 / 118.9 / 118.7 (profiles/r05_ab_split_sync.txt); de-phasing the upper four waves behind the barrier (the classic
-// loop's WAVE_STAGGER) by 1 / 2 / 4 s_sleep(64): 117.8 -> 118.7 / 118.3 / 118.8
-#define WAVE_SPLIT_SYNC 16
-#endif
-#ifndef WAVE_SPLIT_TAIL_ASM
-#define WAVE_SPLIT_TAIL_ASM 1  // split-key engine: the accumulator update as arith.h's six-instruction sequence
-#endif
-#ifndef WAVE_LIT_LIMBS
-#define WAVE_LIT_LIMBS 0
-#endif
-#ifndef WAVE_ROT_PAIRS
-// 1: the rotation fetches the staged words of two consecutive register rows (r, r + 1: 512 bytes apart) with ONE
-// two-address LDS read off one computed address; the second address may run 512 bytes past the 16 KiB ring, where the
-// staging keeps a copy of the ring's first 512 bytes (the exchange buffer has 1,008 spare bytes behind the ring).
-// 16 LDS instructions and 16 address computations fewer per CMUX.  0: one read and one address per word.
-#define WAVE_ROT_PAIRS 1
-#endif
-#ifndef WAVE_RESIDENT
-#define WAVE_RESIDENT 2  // classic one-level loop: twiddles kept in registers across the iterations (ResidentTwiddles: 0..2)
 #endif
 
 #ifndef WAVE_PROBE_TS
@@ -316,8 +96,24 @@ constexpr int T_TOTAL = 1489;
 constexpr int FLAGS_BYTES = 64;
 constexpr size_t SMEM_BYTES = (size_t)WAVES * BUF_BYTES + (size_t)T_TOTAL * 16 + FLAGS_BYTES;
 
-// wave-uniform twiddles as literals (WAVE_UNIFORM_LITERALS): fwd[1], fwd[2], fwd[4], fwd[6], fwd[8..14 step 2] and
-// E[64 j] = inv[512 + 64 j] of the N = 2048 tables (long-double angles rounded once, tables.hip)
+// Issue priority of a wave by phase of its CMUX iteration (s_setprio, 0..3).  The two waves that share a SIMD belong to
+// different LWEs; with equal priority they interleave instruction by instruction and tend to reach their LDS round trips
+// and pair waits together.  Raising the priority as the iteration advances lets the wave that is further along run
+// through (its partner wave is waiting for it), while the other one fills the gaps: measured 102.6 k -> 117 k PBS/s; the
+// order matters (digits < forward, inverse >= MAC), see profiles/r01_setprio_variants.txt.
+constexpr int PRIO_DIGITS = 0;   // rotation + digits
+constexpr int PRIO_FORWARD = 1;  // forward transform
+constexpr int PRIO_MAC = 2;      // pair exchange + MAC
+constexpr int PRIO_INVERSE = 3;  // inverse transform, conversion, accumulation
+// the multi-bit loop: the same phases one level up; PRIO_MB_KEY from the inverse transform to the next group's digits
+constexpr int PRIO_MB_KEY = 0, PRIO_MB_DIGITS = 1, PRIO_MB_FORWARD = 2, PRIO_MB_MAC = 3, PRIO_MB_INVERSE = 3;
+
+// The twiddles that are the same in every lane and every launch (forward d = 0..3, inverse half = 4, 8: 12 of the 118
+// 16-byte LDS reads of an iteration) as literals of the instruction stream (template parameter LIT of the transforms;
+// the inverse butterflies whose twiddle is 1 or -i lose their two products, same roundings: fma(x, 1, y) = x + y):
+// fwd[1], fwd[2], fwd[4], fwd[6], fwd[8..14 step 2] and E[64 j] = inv[512 + 64 j] of the N = 2048 tables (long-double
+// angles rounded once; checked against the host tables when the tables are built, tables.hip).  The classic one-level
+// loop: 34.6 -> 33.3 ms per 4096; the split-key engine keeps the table reads (literals: 150.3 -> 156.0 ms, it spills).
 constexpr double LIT_F1[8][2] = {{0x1.6a09e667f3bcdp-1, 0x1.6a09e667f3bcdp-1}, {0x1.d906bcf328d46p-1, 0x1.87de2a6aea963p-2},
                                  {0x1.f6297cff75cbp-1, 0x1.8f8b83c69a60bp-3},  {0x1.1c73b39ae68c8p-1, 0x1.a9b66290ea1a3p-1},
                                  {0x1.fd88da3d12526p-1, 0x1.917a6bc29b42cp-4}, {0x1.44cf325091dd6p-1, 0x1.8bc806b151741p-1},
@@ -353,10 +149,7 @@ HX_DEV void flag_set(uint32_t *f, uint32_t v) {
   __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 HX_DEV void flag_wait(uint32_t *f, uint32_t v) {
-#if defined(WAVE_SPLIT_PROBE) && WAVE_SPLIT_PROBE == 4  // timing probe (races): no waiting on the partner
-  return;
-#endif
-  while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v) __builtin_amdgcn_s_sleep(WAVE_FLAG_SLEEP);
+  while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v) __builtin_amdgcn_s_sleep(1);
 }
 #endif
 
@@ -452,7 +245,7 @@ HX_DEV void swap_regs_lane54(cplx (&d)[16]) {
     }
 }
 
-// Twiddles kept in registers for the whole launch by the classic one-level loop (template parameter RES of the
+// Twiddles kept in registers for the whole launch by the classic one-level loop (template parameter RES = 2 of the
 // transforms), read from the LDS table once in front of the CMUX loop: level 1 = the eight of pass F2 (they depend on
 // lane >> 4 only), level 2 = also pass I2's two.  Every LDS read that leaves the loop is worth about 0.1 % of the launch
 // (one box, batch 4096: table reads 33.8 ms, literals for the wave-uniform ones 32.9, level 1 32.7, level 2 32.5; a
@@ -461,21 +254,16 @@ struct ResidentTwiddles {
   cplx e4[4], e5[4];  // F2
   cplx w16, e32;      // I2
 };
-template <int LEVEL>
 HX_DEV void load_resident_twiddles(ResidentTwiddles &t, const cplx *T, int lane) {
   const int g4 = lane >> 4, l15 = lane & 15;
-  if constexpr (LEVEL >= 1) {
-    HX_UNROLL
-    for (int j = 0; j < 4; ++j) {
-      t.e4[j] = T[T_F2 + g4 * 4 + j];
-      t.e5[j] = T[T_F2 + 16 + g4 * 4 + j];
-    }
+  HX_UNROLL
+  for (int j = 0; j < 4; ++j) {
+    t.e4[j] = T[T_F2 + g4 * 4 + j];
+    t.e5[j] = T[T_F2 + 16 + g4 * 4 + j];
   }
-  if constexpr (LEVEL >= 2) {
-    t.w16 = T[T_W16 + (l15 & 7)];
-    if (l15 & 8) t.w16 = times_mi(t.w16);
-    t.e32 = T[T_E32 + l15];
-  }
+  t.w16 = T[T_W16 + (l15 & 7)];
+  if (l15 & 8) t.w16 = times_mi(t.w16);
+  t.e32 = T[T_E32 + l15];
 }
 
 // ---- forward transform of 16 points per lane: mapping M1 in, mapping M3 out (and stored in my buffer)
@@ -517,7 +305,6 @@ HX_DEV void wave_forward(cplx (&d)[16], WaveCtx c, const ResidentTwiddles *res =
                    [&](int r) { px[mx_off(r)] = d[r]; });
   }
   HX_WAVE_SYNC();
-  HX_PRIO_OPT(WAVE_PRIO_F3);
   {  // stages 6..9 over position bits 3..0 (= r bits 3..0), group index = lane . (r bits)
     const cplx w6 = T[T_F6 + lane];
     cplx *p3 = c.buf + base_m3(c);  // transposition MX -> M3, load side
@@ -662,7 +449,6 @@ HX_DEV void wave_inverse_accumulate(cplx (&o)[16], uint64_t (&acc_re)[16], uint6
   HX_SCHED_FENCE();
   swap_regs_lane54(o);  // MX -> M1
   HX_SCHED_FENCE();
-  HX_PRIO_OPT(WAVE_PRIO_I3);
   // pass I3: stages half = 64..512 over position bits 6..9 (= r bits 0..3); j = (r bits).lane
   {
     int lane = c.lane;
@@ -680,7 +466,6 @@ HX_DEV void wave_inverse_accumulate(cplx (&o)[16], uint64_t (&acc_re)[16], uint6
     stage<3>(o, [&](int r) { return (r & 4) ? times_mi(e10[r & 3]) : e10[r & 3]; });
   }
   HX_SCHED_FENCE();
-  HX_PRIO_OPT(WAVE_PRIO_CONV);
   // untwist, back to the torus, accumulate (fft/mod.rs:311-330)
   int lane_u = c.lane;
   HX_OPAQUE(lane_u);
@@ -711,9 +496,7 @@ HX_DEV void wave_inverse_accumulate(cplx (&o)[16], uint64_t (&acc_re)[16], uint6
       // conversion arithmetic instead of in front of the next rotation
       stg[lane_u + r * 64] = acc_re[r];
       stg[lane_u + 1024 + r * 64] = acc_im[r];
-#if WAVE_ROT_PAIRS
       if (r == 0) stg[lane_u + 2048] = acc_re[0];  // the ring's first 64 words again behind its end (make_digits)
-#endif
     }
     if ((r & 3) == 3) HX_SCHED_FENCE();
   }
@@ -837,7 +620,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
     // ragged last workgroup redo the last ciphertext and write nothing
     if (!valid) sample = a.num_samples - 1;
   } else {
-    // the whole pair leaves together.  Bare s_barriers further down (split-key loop, WAVE_CLASSIC_SYNC) stay correct: a
+    // the whole pair leaves together.  The bare s_barriers of the split-key loop further down stay correct: a
     // terminated wave no longer counts towards a workgroup barrier on gfx9, every surviving wave runs the same trip count in
     // front of its a_hat == 0 skip, and those loops are instantiated with SHARE = OCTET = false only (see the static_asserts)
     if (!valid) return;
@@ -906,9 +689,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       p[r * 64] = acc_re[r];
       p[1024 + r * 64] = acc_im[r];
     }
-#if WAVE_ROT_PAIRS
     p[2048] = acc_re[0];  // the ring's first 64 words again behind its end (make_digits)
-#endif
     HX_WAVE_SYNC();
   };
   // EXACT selects the decomposer's own bit sequence; the default for one level is the two-instruction
@@ -929,9 +710,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
         (int32_t)((uint32_t)(((int32_t)lane - (int32_t)(a_hat & (N - 1))) * 8) + ((a_hat & N) ? 0u : 0x80000000u));
     int32_t lowest = 0;
     uint32_t vzero = 0;
-#ifndef WAVE_STAGED_SGPR_BASE
     HX_LAUNDER(vzero);  // the staged copy's base in a vector register: a scalar operand doubles the cost of the add
-#endif
     const char *staged = (const char *)buf64 + vzero;
     uint64_t sp0[2] = {0, 0}, sp1[2] = {0, 0};
     (void)sp0;
@@ -946,8 +725,11 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
         const int32_t u0 = (int32_t)((uint32_t)ub + r * 512u), u1 = (int32_t)((uint32_t)u0 + 8192u);
         const uint32_t m0 = (uint32_t)(u0 >> 31), m1 = (uint32_t)(u1 >> 31);  // all-ones: sign +
         const uint64_t M0 = ((uint64_t)m0 << 32) | m0, M1 = ((uint64_t)m1 << 32) | m1;
-#if WAVE_ROT_PAIRS
-        if ((r & 1) == 0) {  // rows r and r + 1 of both halves: the second word sits 512 bytes behind the first
+        // rows r and r + 1 of both halves with ONE two-address LDS read off one computed address: the second word sits
+        // 512 bytes behind the first and may run past the 16 KiB ring, where the staging keeps a copy of the ring's first
+        // 512 bytes (the exchange buffer has 1,008 spare bytes behind the ring): 16 LDS instructions and 16 address
+        // computations fewer per CMUX than one read per word
+        if ((r & 1) == 0) {
           const uint64_t *q0 = (const uint64_t *)(staged + (u0 & 0x3ff8)), *q1 = (const uint64_t *)(staged + (u1 & 0x3ff8));
           sp0[0] = q0[0];
           sp0[1] = q0[64];
@@ -955,10 +737,6 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           sp1[1] = q1[64];
         }
         const uint64_t s0 = sp0[r & 1], s1 = sp1[r & 1];
-#else
-        const uint64_t s0 = *(const uint64_t *)(staged + (u0 & 0x3ff8));
-        const uint64_t s1 = *(const uint64_t *)(staged + (u1 & 0x3ff8));
-#endif
         uint64_t a0 = acc_re[r], a1 = acc_im[r];
         if constexpr (LIMBS > 0) {  // the accumulator is not in registers here: my own coefficients from the staged copy
           a0 = *(const uint64_t *)(staged + (lane + r * 64) * 8);
@@ -1006,18 +784,11 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
 
   // key rows of GGSW_i: [i][idx][row][c = w][storage s = r*64 + lane], consumed in 4 chunks of 4 points
   const uint32_t key_levels = LIMBS > 0 ? (uint32_t)LIMBS : level;  // split-key form: [i][limb][row][col][slot]
-#ifndef WAVE_KEY_BUFFER
-// The key rows requested through ONE buffer descriptor over the whole key — lane offsets in one vector register, the row's
-// byte offset as a scalar — instead of through two per-lane 64-bit pointers (plus one more pointer pair per 4 KB window of
-// immediate offsets the sweep of 16 KB crosses).  0: never, 1: always, 2: in the split-key exact engine only (same box, ms per
-// 4096: split-key engine 137.9 -> 135.0; classic loop 33.4 -> 33.5: its register file is full either way and the descriptor
-// costs scalar registers — profiles/r05_ab_split_buffers.txt)
-#define WAVE_KEY_BUFFER 2
-#endif
-#ifndef WAVE_KEY_AUX
-#define WAVE_KEY_AUX 0  // cache-policy bits of the buffer-addressed key requests
-#endif
-  constexpr bool KEYBUF = WAVE_KEY_BUFFER == 1 || (WAVE_KEY_BUFFER == 2 && LIMBS > 0);
+  // The split-key engine requests the key rows through ONE buffer descriptor over the whole key — lane offsets in one vector
+  // register, the row's byte offset as a scalar — instead of through two per-lane 64-bit pointers (plus one more pointer pair
+  // per 4 KB window of immediate offsets the sweep of 16 KB crosses): 137.9 -> 135.0 ms per 4096; the classic loop keeps the
+  // pointers (33.4 -> 33.5 with the descriptor: its register file is full either way), profiles/r05_ab_split_buffers.txt
+  constexpr bool KEYBUF = LIMBS > 0;
   const HxBuffer bskb = hx_make_buffer(a.bsk, KEYBUF ? (uint32_t)((size_t)a.n * key_levels * 4 * n * sizeof(cplx)) : 0u);
   auto key_rows = [&](uint32_t i, uint32_t idx, const cplx *&b0, const cplx *&b1) {
     if constexpr (KEYBUF) {
@@ -1038,8 +809,8 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       const uint32_t o0 = (uint32_t)(uintptr_t)b0, o1 = (uint32_t)(uintptr_t)b1;
       HX_UNROLL
       for (int j = 0; j < 4; ++j) {
-        const hx_f64x2 v0 = hx_buffer_load_f64x2<WAVE_KEY_AUX>(bskb, (uint32_t)lane * 16u, o0 + (uint32_t)(ch * 4 + j) * 1024u);
-        const hx_f64x2 v1 = hx_buffer_load_f64x2<WAVE_KEY_AUX>(bskb, (uint32_t)lane * 16u, o1 + (uint32_t)(ch * 4 + j) * 1024u);
+        const hx_f64x2 v0 = hx_buffer_load_f64x2(bskb, (uint32_t)lane * 16u, o0 + (uint32_t)(ch * 4 + j) * 1024u);
+        const hx_f64x2 v1 = hx_buffer_load_f64x2(bskb, (uint32_t)lane * 16u, o1 + (uint32_t)(ch * 4 + j) * 1024u);
         k0[j] = cplx{v0.x, v0.y};
         k1[j] = cplx{v1.x, v1.y};
       }
@@ -1054,8 +825,8 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
 
   // publish my transform, fetch the partner's, multiply-accumulate with GGSW_i rows into dst
   // (cc/fft_impl/fft64/crypto/ggsw.rs:616-697 order: row 0 then row 1 within a level).
-  // Chunks 0 and 1 of the key were requested by the caller at the top of the iteration (ka*, kb*);
-  // chunk c + 2 is requested into the registers chunk c has just released.  With FUSE_PASS1 the
+  // Chunk 0 of the key is requested here or, in the classic one-level loop, by the caller at the top of the iteration (ka*),
+  // chunk 1 here (kb*); chunk c + 2 is requested into the registers chunk c has just released.  With fuse_pass1 the
   // first inverse pass (which only mixes the 4 points of one chunk) runs right behind each chunk.
   // publish: my transform's "ready" flag is set here (false: the caller set it earlier).  wait_done (a type): the wait for
   // the partner's "done with your buffer" closes the multiply-accumulate; std::false_type: the caller waits itself, right in
@@ -1068,9 +839,9 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
     const int lane = ctx.lane;
     // wave_forward left my transform in my buffer (mapping M3)
     if (publish && lane == 0) flag_set(f_ready_me, epoch);
-    constexpr int early = (LEVEL_CT == 1 && !MULTIBIT && LIMBS == 0) ? WAVE_EARLY_CHUNKS : 0;  // otherwise requested here
-    if (early < 1) key_request(ka0, ka1, b0, b1, 0);
-    if (early < 2) key_request(kb0, kb1, b0, b1, 1);
+    // the classic one-level loop requests chunk 0 at the top of its iteration; otherwise it is requested here
+    if constexpr (!(LEVEL_CT == 1 && !MULTIBIT && LIMBS == 0)) key_request(ka0, ka1, b0, b1, 0);
+    key_request(kb0, kb1, b0, b1, 1);
     HX_SCHED_FENCE();
     flag_wait(f_ready_ot, epoch);
     const cplx *row0 = (w == 0 ? buf : obuf) + base_m3(ctx);
@@ -1085,16 +856,8 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
     }
     // Both rows are read from LDS — row 0 from the buffer of the wave that holds polynomial 0, row 1 from
     // the other one — so the roles are a scalar pointer choice: no per-point test of w, no selects, and
-    // the registers of my own transform are free during the products.
-    // the LDS reads run WAVE_MAC_PREFETCH points ahead of the products that consume them (issued just in
-    // time, each pair exposed a full LDS latency to this wave)
-    constexpr int PF = WAVE_MAC_PREFETCH;
-    cplx xn0[PF > 0 ? PF : 1], xn1[PF > 0 ? PF : 1];
-    HX_UNROLL
-    for (int q = 0; q < PF; ++q) {
-      xn0[q] = row0[q];
-      xn1[q] = row1[q];
-    }
+    // the registers of my own transform are free during the products.  The LDS reads are issued just in time: run 2, 4
+    // or 8 points ahead they measured no faster (117.9 k -> 117.4 / 117.4 / 117.2 k PBS/s: the partner wave covers the latency)
     HX_UNROLL
     for (int ch = 0; ch < 4; ++ch) {
       cplx(&k0)[4] = (ch & 1) ? kb0 : ka0;
@@ -1102,18 +865,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       HX_UNROLL
       for (int j = 0; j < 4; ++j) {
         const int r = ch * 4 + j;
-        cplx x0, x1;
-        if constexpr (PF > 0) {
-          x0 = xn0[r % PF];
-          x1 = xn1[r % PF];
-          if (r + PF < 16) {
-            xn0[r % PF] = row0[r + PF];
-            xn1[r % PF] = row1[r + PF];
-          }
-        } else {
-          x0 = row0[r];
-          x1 = row1[r];
-        }
+        const cplx x0 = row0[r], x1 = row1[r];
         const cplx t = (idx == 0) ? cmul_first(x0, k0[j]) : cmul_add(x0, k0[j], dst[r]);
         dst[r] = cmul_add(x1, k1[j], t);
         // pin the product here: otherwise the FMAs are sunk below the flag wait that follows and
@@ -1169,19 +921,20 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
     // 1 KB run (one coalesced request with the degree as the scalar offset) instead of 64 scattered table entries
     const HxBuffer mono_lane = hx_make_buffer(tb.mono_lane, 2u * N * 64u * 16u);
     const uint32_t lane16 = (uint32_t)lane * 16u;
-#if WAVE_MB_PACE && !defined(TFHE_HIPEMU)
+#if !defined(TFHE_HIPEMU)
     // Pacing.  Workgroup b runs on XCD b % 8 (round-robin dispatch; used for speed only, never for correctness),
     // 32 workgroups of an XCD are resident at a time, in index order.  Every wave pair adds 1 to its XCD's counter
     // when it finishes a group; a pair of the XCD's r-th batch may start group g once the counter shows that all
-    // pairs of the earlier batches are done and all pairs of its own batch have finished group g - WAVE_MB_PACE.
-    // A wave that polls WAVE_MB_PACE_SPINS times in vain (peers not resident: fewer CUs than expected) stops
-    // pacing, so the scheme cannot deadlock.
-    // SHARE: the two quads of a workgroup run half a group apart (see mac_turn below), so each quad index paces
-    // with its likes: its own counter (another cache line), its own pair counts
+    // pairs of the earlier batches are done and all pairs of its own batch have finished group g - 1.  A wave that
+    // polls 16384 times in vain (peers not resident: fewer CUs than expected) stops pacing, so the scheme cannot
+    // deadlock.  SHARE: each quad index paces with its likes: its own counter (another cache line), its own pair counts.
+    // OCTET runs unpaced: with a wave working for all four LWEs of its workgroup and the touch of the next group's key
+    // lines below, the first workgroup to arrive at a line fetches it for the others (g = 4 / g = 3 per 4096, same box:
+    // paced 20.8 / 36.5 ms, unpaced 20.6 / 35.9)
     const uint32_t pclass = SHARE ? (uint32_t)(pair >> 1) : 0u;
     uint32_t *pace_ctr = a.pace + (blockIdx.x & 7u) * 32u + pclass * 16u;
     uint32_t pace_before = 0, pace_mine = 0;  // pairs of earlier batches of my XCD; pairs of my batch
-    const bool pace_on = a.pace != nullptr && (!OCTET || WAVE_MB_PACE_OCTET != 0);
+    const bool pace_on = !OCTET && a.pace != nullptr;
     bool pacing = pace_on;
     if (pace_on) {
       const uint32_t ppb = blockDim.x >> 7, xcd = blockIdx.x & 7u, my_batch = (blockIdx.x >> 3) / 32u;
@@ -1206,10 +959,8 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       const uint32_t sL = blockIdx.x * 4u + ((uint32_t)lane >> 4), last = a.num_samples - 1;
       lwe_lane = a.lwe_in + (size_t)a.in_idx[sL < last ? sL : last] * (a.n + 1);
     }
-    // SHARE synchronisation, all in the LDS flag words: word v = progress of wave v (quad_sync: each of the four
-    // waves of a quad posts its count and waits for the other three), word 8 = mac_turn.  The multiply-accumulate
-    // is what loads the key, the transforms are what computes: the two quads of a workgroup (one wave of each per
-    // SIMD) take the multiply-accumulate IN TURNS, so one quad's key loads run under the other's transforms.
+    // SHARE synchronisation in the LDS flag words: word v = progress of wave v (quad_sync: each of the four waves of a
+    // quad posts its count and waits for the other three).
     uint32_t q_epoch = 0;
     auto quad_sync = [&]() {
       ++q_epoch;
@@ -1220,42 +971,33 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       for (int v = 0; v < 4; ++v)
         if (q0 + v != wave) flag_wait(flags + q0 + v, q_epoch);
     };
-    const bool two_quads = WAVE_MB_TURNS && SHARE && blockDim.x == 512;
+    // The two quads of a workgroup taking the multiply-accumulate in turns (flag word 8), so that one quad's key loads run
+    // under the other's transforms: measured slower, 60 vs 54 ms, so off.  The hooks stay: without them the register
+    // allocation of the SHARE kernels changes.
+    const bool two_quads = false;
     auto mac_enter = [&](uint32_t m) {  // m-th multiply-accumulate of the launch (group, level)
       if (two_quads) flag_wait(flags + 8, 2u * m + (uint32_t)(pair >> 1));
     };
     auto mac_leave = [&](uint32_t m) {  // after the quad_sync that ends it
       if (two_quads && (wave & 3) == 0 && lane == 0) flag_set(flags + 8, 2u * m + (uint32_t)(pair >> 1) + 1u);
     };
-    // e^{2 pi i t / 16} = mono[t N / 8], t wave-uniform
-    auto w16_root = [&](uint32_t t) {
-#if WAVE_MB_EXPERIMENT & 2  // timing experiment only (wrong results): no scalar load
-      return cplx{0.5, 0.25};
-#endif
-#if WAVE_MB_W16_SCALAR
-      return load_uniform_cplx(tb.mono, (uint32_t)(N / 8) * t);
-#else
-      return T[T_W16X + t];
-#endif
-    };
+    // e^{2 pi i t / 16} = mono[t N / 8], t wave-uniform: through the scalar data cache rather than as broadcast reads of
+    // the LDS table, 2 (2^g - 1) LDS reads per point fewer (at g = 4 as many LDS instructions as the rest of a group).
+    // The loops fence the degree (HX_OPAQUE_S) right where its root is fetched, so the address of every root of a level is
+    // computed just in time: hoisted to the top of the level they do not fit the scalar file and travel through
+    // vector-register lanes (g = 3 quad kernel: 337 spilled SGPRs, ~700 v_writelane / v_readlane per group)
+    auto w16_root = [&](uint32_t t) { return load_uniform_cplx(tb.mono, (uint32_t)(N / 8) * t); };
     const uint32_t ggsw_bytes = (uint32_t)(ggsw_c * sizeof(cplx));
     auto ldc = [](HxBuffer b, uint32_t voff, uint32_t soff) {
       const hx_f64x2 v = hx_buffer_load_f64x2(b, voff, soff);
       return cplx{v.x, v.y};
     };
-#ifndef WAVE_MB_KEY_AUX
-#define WAVE_MB_KEY_AUX 0  // cache-policy bits of the multi-bit key requests (hx.h)
-#endif
-    auto ldk = [](HxBuffer b, uint32_t voff, uint32_t soff) {
-      const hx_f64x2 v = hx_buffer_load_f64x2<WAVE_MB_KEY_AUX>(b, voff, soff);
-      return cplx{v.x, v.y};
-    };
-#if WAVE_MB_PREFETCH
     // The workgroups of an XCD walk the key in step (pacing), so every line of a group's key is a first touch for all
     // of them at once.  One load per wave and group, issued before the inverse transform, touches the NEXT group's
     // lines (the resident workgroups of the XCD share the 128-byte lines among them; speed only — nothing depends on
     // which lines a wave touches); its value is consumed a group later.  g = 3 per 4096 on one box: 42.9 -> 41.7 ms
-    // (42.3 with the touch at the start of the group).  Not in OCTET mode: measured slower there (25.9 -> 26.9 ms).
+    // (42.3 with the touch at the start of the group).  OCTET: only for the sets with
+    // several levels (g = 3, two levels: 40.3 -> 36.5 ms per 4096; one level: 25.9 -> 26.9, g = 4: 20.9 -> 21.2).
     uint32_t pf_val = 0;
     uint32_t pf_first, pf_stride;
     {
@@ -1264,7 +1006,6 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       pf_first = ((((blockIdx.x >> 3) % sharers) * (blockDim.x >> 6) + (uint32_t)wave) * 64u + (uint32_t)lane) * 128u;
       pf_stride = sharers * (blockDim.x >> 6) * 64u * 128u;
     }
-#endif
     for (uint32_t grp = 0; grp < groups; ++grp) {
       // monomial degrees of the 2^g - 1 non-empty subsets (:30-65): subset s selects mask element m of
       // the group when bit (g-1-m) of s is set
@@ -1304,18 +1045,20 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       } else {
         degrees(lwe, deg);
       }
-      constexpr int MB_BASES = WAVE_MB_BASES >= 0 ? WAVE_MB_BASES : (LEVEL_CT >= 2 ? 1 : 0);
+      // pair mode: the bases once per group (MB_BASES = 0) for one level, per level (1, see above) for several: g = 3 /
+      // g = 4 per 4096 on one box, 0 -> 45.1 / 30.2 ms, 1 -> 43.8 / 30.4
+      constexpr int MB_BASES = LEVEL_CT >= 2 ? 1 : 0;
       cplx base[SHARE ? 1 : per];  // pair mode; (re)written per level unless MB_BASES == 0: not live across levels then
       if constexpr (MB_BASES == 0 && !OCTET && !SHARE) bases(deg, base);
       // the group's 2^g GGSWs as one buffer: uniform base in scalar registers, lane offset in one vector register
-#if WAVE_MB_PACE && !defined(TFHE_HIPEMU)
-      auto pace_wait = [&]() {
-        if (pacing && grp >= (uint32_t)WAVE_MB_PACE) {
-          const uint32_t need = pace_before * groups + pace_mine * (grp + 1u - (uint32_t)WAVE_MB_PACE);
+#if !defined(TFHE_HIPEMU)
+      auto pace_wait = [&]() {  // see pace_ctr
+        if (pacing && grp != 0) {
+          const uint32_t need = pace_before * groups + pace_mine * grp;
           uint32_t spins = 0;
           while (__hip_atomic_load(pace_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-            __builtin_amdgcn_s_sleep(WAVE_MB_PACE_SLEEP);
-            if (++spins > (uint32_t)WAVE_MB_PACE_SPINS * 8u / (uint32_t)WAVE_MB_PACE_SLEEP) {
+            __builtin_amdgcn_s_sleep(2);  // 128 cycles between two polls
+            if (++spins > 16384u) {
               pacing = false;
               break;
             }
@@ -1323,32 +1066,23 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
         }
       };
       auto pace_arrive = [&]() {
-        if (pace_on && valid && w == 0 && lane == 0)
-          __hip_atomic_fetch_add(pace_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (pace_on && valid && w == 0 && lane == 0) __hip_atomic_fetch_add(pace_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       };
-#if !WAVE_MB_PACE_AT_KEY
       pace_wait();
       MBP(0);
-#endif
 #else
-      auto pace_wait = []() {};
       auto pace_arrive = []() {};
 #endif
       const HxBuffer gk = hx_make_buffer(key + (size_t)grp * per * ggsw_c, per * ggsw_bytes);
-#if WAVE_MB_PREFETCH
-      auto touch_next_key = [&]() {
-        if constexpr (!OCTET || WAVE_MB_PREFETCH_OCTET == 1 || (WAVE_MB_PREFETCH_OCTET == 2 && LEVEL_CT != 1)) {
+      auto touch_next_key = [&]() {  // see pf_first
+        if constexpr (!OCTET || LEVEL_CT != 1) {
           HX_OPAQUE(pf_val);
-          if (grp + (uint32_t)WAVE_MB_PF_DIST < groups) {
-            const char *nk = (const char *)(key + (size_t)(grp + (uint32_t)WAVE_MB_PF_DIST) * per * ggsw_c);
+          if (grp + 1u < groups) {
+            const char *nk = (const char *)(key + (size_t)(grp + 1u) * per * ggsw_c);
             for (uint32_t off = pf_first; off < per * ggsw_bytes; off += pf_stride) pf_val ^= *(const uint32_t *)(nk + off);
           }
         }
       };
-#if WAVE_MB_PF_POS == 1
-      touch_next_key();
-#endif
-#endif
       cplx o[16];
       cplx oq_a[(SHARE || (OCTET && LEVEL_CT != 1)) ? 8 : 1], oq_b[(SHARE || (OCTET && LEVEL_CT != 1)) ? 8 : 1];  // SHARE: [point 4 u + j][column] at index 2 j + column, first / second LWE of the quad
       if constexpr (SHARE || (OCTET && LEVEL_CT != 1)) {  // OCTET, several levels: [LWE][point][column] over the two arrays
@@ -1387,7 +1121,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       (void)dv;
       for (uint32_t idx = 0; idx < level; ++idx) {
         cplx d[16];
-        HX_PRIO(WAVE_PRIO_MB_A);
+        HX_PRIO(PRIO_MB_DIGITS);
         if constexpr (STATE32) {
           HX_UNROLL
           for (int r = 0; r < 16; ++r) {
@@ -1403,10 +1137,10 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           make_digits(d, 0, idx);
         }
         MBP(1);
-        HX_PRIO(WAVE_PRIO_MB_B);
-        wave_forward<0, WAVE_LIT_MB>(d, ctx);
+        HX_PRIO(PRIO_MB_FORWARD);
+        wave_forward<0, 2>(d, ctx);
         MBP(2);
-        HX_PRIO(WAVE_PRIO_MB_C);
+        HX_PRIO(PRIO_MB_MAC);
         if constexpr (OCTET && LEVEL_CT != 1) {
           // Several levels, all eight waves sharing every key load: as the one-level form below (wave v: both columns at
           // the points 2 v, 2 v + 1 for the four LWEs), but POINT-major — the products of the levels add up in registers
@@ -1419,17 +1153,15 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           const uint32_t v8 = (uint32_t)wave;
           const uint32_t brv = ((v8 & 1u) << 2) | (v8 & 2u) | (v8 >> 2);  // bitrev4(2 v) = bitrev3(v)
           const uint32_t lvl_off = idx * 4u * (uint32_t)n * 16u + v8 * 2048u;
-          constexpr int SETS = WAVE_MB_OCTET_SETS, STEPS = 4 * (int)per;
+          constexpr int SETS = 3, STEPS = 4 * (int)per;  // SETS: register sets in rotation (a request = the 2 rows of one step)
           cplx x0[SETS], x1[SETS];
           auto request = [&](int set, int t) {  // step t = (point, subset, column): rows 0 and 1
             const uint32_t sidx = (uint32_t)((t >> 1) % (int)per), pp = (uint32_t)((t >> 1) / (int)per), c = (uint32_t)(t & 1);
             uint32_t o0 = lvl_off;
-#if WAVE_MB_ROOT_JIT
             HX_OPAQUE_S(o0);
-#endif
             const uint32_t rc = c * (uint32_t)n * 16u + pp * 1024u;
-            x0[set] = ldk(gk, lane_off, sidx * ggsw_bytes + o0 + rc);
-            x1[set] = ldk(gk, lane_off, sidx * ggsw_bytes + o0 + rc + 2u * (uint32_t)n * 16u);
+            x0[set] = ldc(gk, lane_off, sidx * ggsw_bytes + o0 + rc);
+            x1[set] = ldc(gk, lane_off, sidx * ggsw_bytes + o0 + rc + 2u * (uint32_t)n * 16u);
           };
           uint32_t dg[1][4];
           cplx bs[1][4];  // consumed into the factors before the next subset's are requested
@@ -1437,30 +1169,13 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
             HX_UNROLL
             for (int L = 0; L < 4; ++L) {
               dg[0][L] = hx_readlane(dv, L * 16 + (int)sidx);
-#if WAVE_MB_EXPERIMENT & 4  // timing experiment only (wrong results): no base requests
-              bs[0][L] = cplx{0.5, 0.25};
-              HX_OPAQUE(bs[0][L].re);
-              HX_OPAQUE(bs[0][L].im);
-#else
-              bs[0][L] = ldc(mono_lane, lane16, MB_EXP_ROW(dg[0][L]) * 1024u);
-#endif
+              bs[0][L] = ldc(mono_lane, lane16, dg[0][L] * 1024u);
             }
           };
-#if WAVE_MB_PACE_AT_KEY
-          if (idx == 0) {
-            pace_wait();
-            MBP(0);
-          }
-#endif
           HX_UNROLL
           for (int t = 0; t < SETS && t < STEPS; ++t) request(t, t);
           if (per > 1) request_bases(1);
           HX_SCHED_FENCE();
-#if !WAVE_MB_OCTET2_K_FIRST
-          HX_BLOCK_SYNC_LDS();  // all eight transforms of this level are in the buffers (mapping M3: slot lane*17 + r)
-          MBP(3);
-          HX_SCHED_FENCE();
-#endif
           const int fslot = base_m3(cx) + 2 * (int)v8;
           HX_UNROLL
           for (int pp = 0; pp < 2; ++pp) {
@@ -1473,9 +1188,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
                 HX_UNROLL
                 for (int L = 0; L < 4; ++L) {
                   uint32_t dgl = dg[0][L];
-#if WAVE_MB_ROOT_JIT && WAVE_MB_W16_SCALAR
                   HX_OPAQUE_S(dgl);
-#endif
                   mf[L] = cmul_first(bs[0][L], w16_root(((brv + 8u * (uint32_t)pp) * dgl) & 15u));
                 }
                 if (per > 2 && (si + 1 < (int)per || pp == 0)) request_bases((uint32_t)nx);
@@ -1503,7 +1216,6 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
                 HX_SCHED_FENCE();
               }
             }
-#if WAVE_MB_OCTET2_K_FIRST
             // the first point's keybundle needs the key and the mask only: the workgroup meets behind it, in front of the first
             // read of a transform — a wave that is early combines instead of waiting
             if (pp == 0) {
@@ -1512,7 +1224,6 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
               MBP(3);
               HX_SCHED_FENCE();
             }
-#endif
             // this point's products with the digit transforms of the four LWEs, added to the earlier levels'
             HX_UNROLL
             for (int L = 0; L < 4; ++L) {
@@ -1550,20 +1261,18 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           const uint32_t v8 = (uint32_t)wave;
           const uint32_t brv = ((v8 & 1u) << 2) | (v8 & 2u) | (v8 >> 2);  // bitrev4(2 v) = bitrev3(v)
           const uint32_t lvl_off = idx * 4u * (uint32_t)n * 16u + v8 * 2048u;
-          constexpr int SETS = WAVE_MB_OCTET_SETS, RW = 4, STEPS = RW * (int)per;
+          constexpr int SETS = 3, RW = 4, STEPS = RW * (int)per;  // SETS: as above
           cplx x0[SETS], x1[SETS];
           auto request = [&](int set, int t) {  // step t = (subset, point, column): rows 0 and 1
             const uint32_t sidx = (uint32_t)(t / RW);
             const uint32_t pc = (uint32_t)(t % RW);  // 2 p + c
             uint32_t o0 = lvl_off;
-#if WAVE_MB_ROOT_JIT
             // the scalar offset of a request is one addition: made here, not 2 x 4 x 2^g of them ahead of the level and carried
             // through vector-register lanes
             HX_OPAQUE_S(o0);
-#endif
             const uint32_t rc = (pc & 1u) * (uint32_t)n * 16u + (pc >> 1) * 1024u;
-            x0[set] = ldk(gk, lane_off, sidx * ggsw_bytes + o0 + rc);
-            x1[set] = ldk(gk, lane_off, sidx * ggsw_bytes + o0 + rc + 2u * (uint32_t)n * 16u);
+            x0[set] = ldc(gk, lane_off, sidx * ggsw_bytes + o0 + rc);
+            x1[set] = ldc(gk, lane_off, sidx * ggsw_bytes + o0 + rc + 2u * (uint32_t)n * 16u);
           };
           uint32_t dg[2][4];
           cplx bs[2][4];
@@ -1571,30 +1280,16 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
             HX_UNROLL
             for (int L = 0; L < 4; ++L) {
               dg[sidx & 1][L] = hx_readlane(dv, L * 16 + (int)sidx);
-#if WAVE_MB_EXPERIMENT & 4  // timing experiment only (wrong results): no base requests
-              bs[sidx & 1][L] = cplx{0.5, 0.25};
-              HX_OPAQUE(bs[sidx & 1][L].re);
-              HX_OPAQUE(bs[sidx & 1][L].im);
-#else
-              bs[sidx & 1][L] = ldc(mono_lane, lane16, MB_EXP_ROW(dg[sidx & 1][L]) * 1024u);
-#endif
+              bs[sidx & 1][L] = ldc(mono_lane, lane16, dg[sidx & 1][L] * 1024u);
             }
           };
-#if WAVE_MB_PACE_AT_KEY
-          if (idx == 0) {
-            pace_wait();
-            MBP(0);
-          }
-#endif
           HX_UNROLL
           for (int t = 0; t < SETS && t < STEPS; ++t) request(t, t);
           request_bases(1);
           HX_SCHED_FENCE();
-#if !WAVE_MB_OCTET_K_FIRST
           HX_BLOCK_SYNC_LDS();  // all eight transforms are in the buffers (mapping M3: slot lane*17 + r)
           MBP(3);
           HX_SCHED_FENCE();
-#endif
           cplx kq[4][RW][2];  // [LWE][2 p + c][row]
           HX_UNROLL
           for (int si = 0; si < (int)per; ++si) {
@@ -1605,9 +1300,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
               HX_UNROLL
               for (int L = 0; L < 4; ++L) {
                 uint32_t dgl = dg[si & 1][L];
-#if WAVE_MB_ROOT_JIT && WAVE_MB_W16_SCALAR
                 HX_OPAQUE_S(dgl);
-#endif
                 mf[L] = cmul_first(bs[si & 1][L], w16_root((brv * dgl) & 15u));
               }
             }
@@ -1644,12 +1337,6 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
               HX_SCHED_FENCE();
             }
           }
-#if WAVE_MB_OCTET_K_FIRST
-          HX_SCHED_FENCE();
-          HX_BLOCK_SYNC_LDS();  // all eight transforms are in the buffers (mapping M3: slot lane*17 + r)
-          MBP(3);
-          HX_SCHED_FENCE();
-#endif
           // products with the digit transforms of the four LWEs (rows = the two polynomials of an LWE's pair), both
           // columns, written back over the transforms they were made of; fma(a, b, -0.0) is the rounded product a b
           // with its sign of zero
@@ -1694,30 +1381,24 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           const cplx *fa0 = qbuf + fslot, *fa1 = (const cplx *)((const char *)qbuf + BUF_BYTES) + fslot;
           const cplx *fb0 = (const cplx *)((const char *)qbuf + 2 * BUF_BYTES) + fslot;
           const cplx *fb1 = (const cplx *)((const char *)qbuf + 3 * BUF_BYTES) + fslot;
-          constexpr int SETS = WAVE_MB_SHARE_SETS > 0 ? WAVE_MB_SHARE_SETS : 3, STEPS = 8 * (int)per;
+          // register sets in rotation: g = 3 / g = 4 per 4096 on one box, 2 -> 48.8 / 29.8 ms, 3 -> 43.8 / 30.3, 4 -> 43.0 / 30.7,
+          // 5 -> 43.9 / 31.3
+          constexpr int SETS = 3, STEPS = 8 * (int)per;
           cplx x0[SETS], x1[SETS];
           auto request = [&](int set, int t) {  // step t = (pair of points, subset, point of the pair, column): rows 0 and 1
             const uint32_t sidx = (uint32_t)((t >> 2) % (int)per);
             const uint32_t j = (uint32_t)((t >> 2) / (int)per) * 2u + (uint32_t)((t >> 1) & 1), c = (uint32_t)(t & 1);
             uint32_t o0 = lvl_off;
-#if WAVE_MB_ROOT_JIT
             HX_OPAQUE_S(o0);
-#endif
             const uint32_t rc = c * (uint32_t)n * 16u + j * 1024u;
-            x0[set] = ldk(gk, lane_off, sidx * ggsw_bytes + o0 + rc);
-            x1[set] = ldk(gk, lane_off, sidx * ggsw_bytes + o0 + rc + 2u * (uint32_t)n * 16u);
+            x0[set] = ldc(gk, lane_off, sidx * ggsw_bytes + o0 + rc);
+            x1[set] = ldc(gk, lane_off, sidx * ggsw_bytes + o0 + rc + 2u * (uint32_t)n * 16u);
           };
           cplx bsa[2], bsb[2];
           auto request_bases = [&](uint32_t sidx) {
             bsa[sidx & 1] = ldc(mono_lane, lane16, deg[sidx] * 1024u);
             bsb[sidx & 1] = ldc(mono_lane, lane16, deg_b[sidx] * 1024u);
           };
-#if WAVE_MB_PACE_AT_KEY
-          if (idx == 0) {
-            pace_wait();
-            MBP(0);
-          }
-#endif
           HX_UNROLL
           for (int t = 0; t < SETS && t < STEPS; ++t) request(t, t);
           if (per > 1) request_bases(1);
@@ -1739,10 +1420,8 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
                 const int nx = si + 1 < (int)per ? si + 1 : 1;
                 const cplx ba = bsa[si & 1], bb = bsb[si & 1];
                 uint32_t dga = deg[si], dgb = deg_b[si];
-#if WAVE_MB_ROOT_JIT && WAVE_MB_W16_SCALAR
                 HX_OPAQUE_S(dga);
                 HX_OPAQUE_S(dgb);
-#endif
                 const uint32_t br = (uint32_t)pr * 4u + bru;
                 mfa = cmul_first(ba, w16_root((br * dga) & 15u));
                 mfb = cmul_first(bb, w16_root((br * dgb) & 15u));
@@ -1815,39 +1494,24 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           // A step consumes one subset of one chunk of PTS points per lane (both rows).  SETS register sets
           // rotate: the set a step frees takes the request of the step SETS ahead, so SETS - 1 requests
           // (2 PTS coalesced 1 KiB wave loads each) are in flight while one set is accumulated.
-          constexpr int PTS = WAVE_MB_PTS, SETS = WAVE_MB_SETS, CHUNKS = 16 / PTS, STEPS = CHUNKS * (int)per;
+          constexpr int PTS = 2, SETS = 4, CHUNKS = 16 / PTS, STEPS = CHUNKS * (int)per;
           if constexpr (MB_BASES == 1) bases(deg, base);
           cplx x0[SETS][PTS], x1[SETS][PTS];
           auto request = [&](int set, int t) {
             const uint32_t sidx = (uint32_t)(t % (int)per);
             const int ch = t / (int)per;
-#ifdef WAVE_MB_EXPERIMENT_SKIP_LOADS  // timing experiment only (wrong results): 1 of N key requests is issued
-            if (t % WAVE_MB_EXPERIMENT_SKIP_LOADS != 0) return;
-#endif
             uint32_t o0 = row0_off, o1 = row1_off;
-#if WAVE_MB_ROOT_JIT
             HX_OPAQUE_S(o0);
             HX_OPAQUE_S(o1);
-#endif
             HX_UNROLL
             for (int j = 0; j < PTS; ++j) {
-              x0[set][j] = ldk(gk, lane_off, sidx * ggsw_bytes + o0 + (uint32_t)(ch * PTS + j) * 1024u);
-              x1[set][j] = ldk(gk, lane_off, sidx * ggsw_bytes + o1 + (uint32_t)(ch * PTS + j) * 1024u);
+              x0[set][j] = ldc(gk, lane_off, sidx * ggsw_bytes + o0 + (uint32_t)(ch * PTS + j) * 1024u);
+              x1[set][j] = ldc(gk, lane_off, sidx * ggsw_bytes + o1 + (uint32_t)(ch * PTS + j) * 1024u);
             }
           };
-#if WAVE_MB_PACE_AT_KEY
-          if (idx == 0) {
-            pace_wait();
-            MBP(0);
-          }
-#endif
           HX_UNROLL
           for (int t = 0; t < SETS && t < STEPS; ++t) request(t, t);
           HX_SCHED_FENCE();
-          if constexpr (MB_BASES == 2) {  // behind the first key requests
-            bases(deg, base);
-            HX_SCHED_FENCE();
-          }
           flag_wait(f_ready_ot, epoch);
           MBP(3);
           const cplx *row0 = (w == 0 ? buf : obuf) + base_m3(cx);
@@ -1870,9 +1534,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
                 for (int j = 0; j < PTS; ++j) {
                   constexpr uint32_t br4[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
                   uint32_t dgs = deg[sidx];
-#if WAVE_MB_ROOT_JIT && WAVE_MB_W16_SCALAR
                   HX_OPAQUE_S(dgs);
-#endif
                   const cplx wr = w16_root((br4[ch * PTS + j] * dgs) & 15u);
                   const cplx mf = cmul_first(base[sidx], wr);
                   kb0[j] = cmul_add(x0[set][j], mf, kb0[j]);
@@ -1957,20 +1619,13 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           HX_WAVE_SYNC();
         }
       }
-#if WAVE_MB_PREFETCH && WAVE_MB_PF_POS == 0
       touch_next_key();
-#endif
-#if WAVE_MB_PACE_AT_KEY
-      pace_arrive();
-#endif
       MBP(6);
-      HX_PRIO(WAVE_PRIO_MB_D);
-      wave_inverse_accumulate<0, true, false, false, 0, WAVE_LIT_MB>(o, acc_re, acc_im, ctx);
-      HX_PRIO(WAVE_PRIO_MB_K);
+      HX_PRIO(PRIO_MB_INVERSE);
+      wave_inverse_accumulate<0, true, false, false, 0, 2>(o, acc_re, acc_im, ctx);
+      HX_PRIO(PRIO_MB_KEY);
       MBP(7);
-#if !WAVE_MB_PACE_AT_KEY
       pace_arrive();
-#endif
     }
 #if WAVE_MB_PROBE
     if (g_wave_ts && lane == 0) {
@@ -1978,99 +1633,36 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
     }
 #endif
   } else if constexpr (LIMBS > 0) {
-    struct alignas(16) U64x2 { uint64_t x, y; };
     // my polynomial's 2 N words in the accumulator scratch as one buffer: slot r*64 + lane holds coefficients c and 1024 + c.
     // Buffer addressing: ONE vector register of lane offsets serves the 16 requests of a sweep (the scalar offset r * 1024
     // rides in the instruction); as 64-bit pointers the compiler kept one per 1 KB step beyond the immediate range and
     // spilled them (32 spilled registers, 51 scratch accesses per CMUX in round 4)
-#ifndef WAVE_SPLIT_ACC_BUFFER
-#define WAVE_SPLIT_ACC_BUFFER 1
-#endif
-#ifndef WAVE_SPLIT_ACC_AUX
-// cache-policy bits of the accumulator's loads and stores (hx.h: 1 = sc0, 2 = nt, 16 = sc1).  16 (agent scope: the lines do not
-// stay in the CU's vector L1, which the four LWEs' key requests share): 131.2 -> 129.6 and 132.0 -> 131.0 ms per 4096 on two
-// boxes; nt, sc0 and the combinations: no gain or worse (profiles/r05_ab_split_cache_policy.txt)
-#define WAVE_SPLIT_ACC_AUX 16
-#endif
     const uint64_t *gacc_base = a.acc_scratch ? a.acc_scratch + ((size_t)sample * 2 + (size_t)w) * N : nullptr;
     const HxBuffer gaccb = hx_make_buffer(gacc_base, (uint32_t)(N * sizeof(uint64_t)));
-    U64x2 *gacc = (U64x2 *)gacc_base + lane;
-    (void)gacc;
-    (void)gaccb;
+    // cache-policy bits of the accumulator's loads and stores (hx.h): 16 = sc1 (agent scope: the lines do not stay in the
+    // CU's vector L1, which the four LWEs' key requests share): 131.2 -> 129.6 and 132.0 -> 131.0 ms per 4096 on two boxes;
+    // nt, sc0 and the combinations: no gain or worse (profiles/r05_ab_split_cache_policy.txt)
+    constexpr int ACC_AUX = 16;
     auto acc_load = [&]() {
-#if WAVE_SPLIT_PROBE == 2  // timing probe (wrong results): no accumulator traffic
-      return;
-#endif
       int ln = ctx0.lane;
       HX_OPAQUE(ln);
       HX_UNROLL
-      for (int r = 0; r < 16; ++r) {
-#if WAVE_SPLIT_ACC_BUFFER
-        hx_buffer_load_u64x2<WAVE_SPLIT_ACC_AUX>(gaccb, (uint32_t)ln * 16u, (uint32_t)r * 1024u, acc_re[r], acc_im[r]);
-#else
-        const U64x2 v = gacc[r * 64];
-        acc_re[r] = v.x;
-        acc_im[r] = v.y;
-#endif
-      }
+      for (int r = 0; r < 16; ++r)
+        hx_buffer_load_u64x2<ACC_AUX>(gaccb, (uint32_t)ln * 16u, (uint32_t)r * 1024u, acc_re[r], acc_im[r]);
     };
     auto acc_store = [&]() {
-#if WAVE_SPLIT_PROBE == 2
-      return;
-#endif
       int ln = ctx0.lane;
       HX_OPAQUE(ln);
       HX_UNROLL
-      for (int r = 0; r < 16; ++r) {
-#if WAVE_SPLIT_ACC_BUFFER
-        hx_buffer_store_u64x2<WAVE_SPLIT_ACC_AUX>(gaccb, (uint32_t)ln * 16u, (uint32_t)r * 1024u, acc_re[r], acc_im[r]);
-#else
-        gacc[r * 64] = U64x2{acc_re[r], acc_im[r]};
-#endif
-      }
+      for (int r = 0; r < 16; ++r)
+        hx_buffer_store_u64x2<ACC_AUX>(gaccb, (uint32_t)ln * 16u, (uint32_t)r * 1024u, acc_re[r], acc_im[r]);
     };
     acc_store();
     stage_acc();  // the rotation of the first CMUX reads the staged copy
-#if WAVE_SPLIT_PACE && !defined(TFHE_HIPEMU)
-    // Pacing by mask index (the multi-bit loop's scheme, see there): every pair adds 1 to its XCD's counter per mask
-    // element, executed or skipped; speed only, bounded spins, never needed for correctness
-    uint32_t *pace_ctr = a.pace + (blockIdx.x & 7u) * 32u;
-    uint32_t pace_before = 0, pace_mine = 0;
-    bool pacing = a.pace != nullptr;
-    {
-      const uint32_t ppb = blockDim.x >> 7, xcd = blockIdx.x & 7u, my_batch = (blockIdx.x >> 3) / 32u;
-      for (uint32_t j = 0; j < (my_batch + 1) * 32u; ++j) {
-        const uint64_t first = (uint64_t)(xcd + 8u * j) * ppb;
-        const uint32_t cnt = first >= a.num_samples ? 0u : (a.num_samples - first < ppb ? (uint32_t)(a.num_samples - first) : ppb);
-        if (j < my_batch * 32u) pace_before += cnt; else pace_mine += cnt;
-      }
-    }
-    auto pace_wait = [&](uint32_t i) {
-      if (pacing && i >= (uint32_t)WAVE_SPLIT_PACE) {
-        const uint32_t need = pace_before * a.n + pace_mine * (i + 1u - (uint32_t)WAVE_SPLIT_PACE);
-        uint32_t spins = 0;
-        while (__hip_atomic_load(pace_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-          __builtin_amdgcn_s_sleep(8);
-          if (++spins > (uint32_t)WAVE_MB_PACE_SPINS) {
-            pacing = false;
-            break;
-          }
-        }
-      }
-    };
-    auto pace_arrive = [&]() {
-      if (a.pace != nullptr && w == 0 && lane == 0)
-        __hip_atomic_fetch_add(pace_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-#endif
-#ifndef WAVE_SPLIT_RES_FWD
-#define WAVE_SPLIT_RES_FWD 0  // split-key engine: forward pass F2's eight twiddles resident (ResidentTwiddles level 1)
-#endif
-#ifndef WAVE_SPLIT_RES_INV
-#define WAVE_SPLIT_RES_INV 0  // ... inverse pass I2's two twiddles resident (level 2; four inverse transforms per CMUX use them)
-#endif
-    ResidentTwiddles res_sp;
-    load_resident_twiddles<(WAVE_SPLIT_RES_INV >= 2 ? 2 : WAVE_SPLIT_RES_FWD)>(res_sp, T, lane);
+    // The engine runs unpaced: pacing the workgroups of an XCD by mask index (the multi-bit loop's scheme) measured slower,
+    // 117.8 vs 143-156 ms per 4096 (profiles/r05_ab_split_fold.txt).  Resident twiddles and literals: also slower here
+    // (profiles/r05_ab_split_lit_res.txt).
+    ResidentTwiddles res_sp;  // not read (RES = 0), but passing nullptr instead changes the register allocation
     uint32_t worst = 0;  // OR of the low words of every product's bit pattern: bit 0 = some product was not within 1/4 of an integer
     // t = S + error, S integer: the Horner state takes the raw bits of t + 1.5 2^51 (= GL_SPLIT_C0 + 2 S + q, arith.h: the
     // factor 2 is out of the key, the bias of the four limbs cancels against the states' start value GL_SPLIT_R0, q is
@@ -2088,26 +1680,20 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       const uint64_t mask_cur = mask_next;
       mask_next = lwe[i + 1];
       const uint32_t a_hat = HX_UNIFORM((uint32_t)modulus_switch(mask_cur, LOG2N2));
-#if WAVE_SPLIT_SYNC && !defined(TFHE_HIPEMU)
+#if !defined(TFHE_HIPEMU)
       // the workgroup's LWEs in step (speed only: no memory ordering rides on it; waves that have left do not count):
-      // every WAVE_SPLIT_SYNC-th mask element a bare s_barrier, executed before the a_hat == 0 skip by every wave
-      if (i % (uint32_t)WAVE_SPLIT_SYNC == 0) __builtin_amdgcn_s_barrier();
+      // every 16th mask element a bare s_barrier, executed before the a_hat == 0 skip by every wave.  Same box, ms per
+      // 4096, two interleaved rounds: none 121.0, every 1 / 4 / 8 / 16 / 32: 119.4 / 118.6 / 119.1 / 118.9 / 118.7
+      // (profiles/r05_ab_split_sync.txt)
+      if (i % 16u == 0) __builtin_amdgcn_s_barrier();
 #endif
-#if WAVE_SPLIT_PACE && !defined(TFHE_HIPEMU)
-      if (a_hat == 0) {
-        pace_arrive();
-        continue;
-      }
-      pace_wait(i);
-#else
       if (a_hat == 0) continue;
-#endif
       ++it;
       cplx d[16];
-      HX_PRIO(WAVE_PRIO_A);
+      HX_PRIO(PRIO_DIGITS);
       make_digits(d, a_hat, 0);  // both operands of the rotation from the staged copy (the registers are not the accumulator's)
-      HX_PRIO(WAVE_PRIO_B);
-      wave_forward<WAVE_SPLIT_RES_FWD, WAVE_LIT_LIMBS != 0>(d, ctx, &res_sp);  // d = F, my row of the digit transform; also in my buffer (mapping M3)
+      HX_PRIO(PRIO_FORWARD);
+      wave_forward(d, ctx);  // d = F, my row of the digit transform; also in my buffer (mapping M3)
       uint64_t R_re[16], R_im[16];
       HX_UNROLL
       for (int r = 0; r < 16; ++r) R_re[r] = R_im[r] = GL_SPLIT_R0;  // the limbs' bias cancels (arith.h)
@@ -2117,24 +1703,17 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
         constexpr bool LAST = decltype(last_tag)::value;
         cplx o[16], ka0[4], ka1[4], kb0[4], kb1[4];
         const cplx *b0, *b1;
-#if WAVE_SPLIT_PROBE == 1  // timing probe (wrong results): every key request hits the same 64 KB
-        key_rows(0, limb, b0, b1);
-#elif WAVE_SPLIT_PROBE == 3  // timing probe (wrong results): ... the same 16 KB per wave (vector L1)
-        key_rows(0, 0, b0, b1);
-#else
         key_rows(i, limb, b0, b1);
-#endif
-        HX_PRIO(WAVE_PRIO_C);
+        HX_PRIO(PRIO_MAC);
         const uint32_t epoch = (it - 1) * (uint32_t)LIMBS + limb + 1;
-#if WAVE_SPLIT_EARLY_RESTORE
         // Eight handshakes per CMUX (two per limb) instead of the classic loop's two: none of them is waited for where it is
         // posted.  "Ready" of limbs 1 .. 3 is posted by the previous limb's inverse transform as soon as its transposition
         // has left the buffer (F goes back there at once, after_load), "done" is waited for in front of the inverse
-        // transposition's first store (before_store), two butterfly stages after the products.
-        mac_impl(o, o, ka0, ka1, kb0, kb1, b0, b1, 0, epoch, std::integral_constant<bool, WAVE_FUSE_PASS1 != 0>{}, limb == 0,
-                 std::false_type{});
+        // transposition's first store (before_store), two butterfly stages after the products.  Same box, ms per 4096:
+        // 115.28 -> 114.73 against posting and waiting in place (profiles/r05_ab_split_restore.txt).
+        mac_impl(o, o, ka0, ka1, kb0, kb1, b0, b1, 0, epoch, std::true_type{}, limb == 0, std::false_type{});
         if constexpr (LAST) acc_load();
-        HX_PRIO(WAVE_PRIO_D);
+        HX_PRIO(PRIO_INVERSE);
         auto before_store = [&]() { flag_wait(r_done_ot, epoch); };
         auto after_load = [&]() {
           if constexpr (!LAST) {  // my buffer held the inverse transposition: the pair needs F again
@@ -2147,54 +1726,27 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
             if (cx.lane == 0) flag_set(f_ready_me, epoch + 1);
           }
         };
-        wave_inverse_accumulate<(WAVE_FUSE_PASS1 != 0) ? 1 : 0, false, false, true, WAVE_SPLIT_RES_INV, WAVE_LIT_LIMBS != 0>(
-            o, acc_re, acc_im, ctx, &res_sp, before_store, after_load);
+        wave_inverse_accumulate<1, false, false, true>(o, acc_re, acc_im, ctx, &res_sp, before_store, after_load);
         HX_UNROLL
         for (int r = 0; r < 16; ++r) {
           fold(R_re[r], o[r].re);
           fold(R_im[r], o[r].im);
         }
-#else
-        mac(o, o, ka0, ka1, kb0, kb1, b0, b1, 0, epoch, std::integral_constant<bool, WAVE_FUSE_PASS1 != 0>{});
-        if constexpr (LAST) acc_load();
-        HX_PRIO(WAVE_PRIO_D);
-        wave_inverse_accumulate<(WAVE_FUSE_PASS1 != 0) ? 1 : 0, false, false, true, WAVE_SPLIT_RES_INV, WAVE_LIT_LIMBS != 0>(o, acc_re, acc_im, ctx, &res_sp);
-        HX_UNROLL
-        for (int r = 0; r < 16; ++r) {
-          fold(R_re[r], o[r].re);
-          fold(R_im[r], o[r].im);
-        }
-        if constexpr (!LAST) {  // my buffer held the inverse transposition: the pair needs F again
-          WaveCtx cx = ctx0;
-          HX_OPAQUE(cx.lane);
-          cplx *p3 = buf + base_m3(cx);
-          HX_UNROLL
-          for (int r = 0; r < 16; ++r) p3[r] = d[r];
-          HX_WAVE_SYNC();
-        }
-#endif
       };
       HX_NO_UNROLL  // one body: unrolled, the scheduler overlaps the limbs and spills hundreds of registers
       for (uint32_t limb = 0; limb + 1 < (uint32_t)LIMBS; ++limb) limb_step(limb, std::false_type{});  // limb 0 = most significant
       limb_step((uint32_t)LIMBS - 1, std::true_type{});
       // acc += modswitch_to_2^64(product mod P) (ntt64.rs:162-177).  The registers hold MINUS the accumulator and the key
       // limbs are cut from MINUS the key, R = -product: modswitch(-x mod P) = -modswitch(x) mod 2^64 exactly (P odd: the
-      // rounding is symmetric), so the update is one 64-bit addition
+      // rounding is symmetric), so the update is one 64-bit addition, as arith.h's six-instruction sequence (117.8 vs 120.2
+      // ms per 4096 as the compiler lowers acc + gl_modswitch_to_pow2_lazy(R), profiles/r05_ab_split_fold.txt)
       HX_UNROLL
       for (int r = 0; r < 16; ++r) {
-#if WAVE_SPLIT_TAIL_ASM
         acc_re[r] = gl_acc_modswitch_to_pow2_lazy(acc_re[r], R_re[r]);
         acc_im[r] = gl_acc_modswitch_to_pow2_lazy(acc_im[r], R_im[r]);
-#else
-        acc_re[r] += gl_modswitch_to_pow2_lazy(R_re[r]);
-        acc_im[r] += gl_modswitch_to_pow2_lazy(R_im[r]);
-#endif
       }
       acc_store();
       stage_acc();  // for the next CMUX's rotation (my buffer is free: the last inverse transposition is over)
-#if WAVE_SPLIT_PACE && !defined(TFHE_HIPEMU)
-      pace_arrive();
-#endif
     }
     // an f64 product was not within 1/4 of an integer: reported through the scratch's flag (no trap: a trap kills the
     // whole HIP context of the process).  The bound is statistical, not a proof — worst-case magnitudes of 2^49 leave
@@ -2214,11 +1766,12 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
   } else {
     stage_acc();
     ResidentTwiddles res_tw;
-    if constexpr (LEVEL_CT == 1) load_resident_twiddles<WAVE_RESIDENT>(res_tw, T, lane);
-#if WAVE_STAGGER && !defined(TFHE_HIPEMU)
-    if (wave >= 4) {
-      for (int u = 0; u < WAVE_STAGGER; ++u) __builtin_amdgcn_s_sleep(64);
-    }
+    if constexpr (LEVEL_CT == 1) load_resident_twiddles(res_tw, T, lane);
+#if !defined(TFHE_HIPEMU)
+    // waves 4..7 (the second wave of every SIMD) start the loop 4096 cycles after waves 0..3, so that the two waves of a
+    // SIMD are in different phases of the CMUX.  Same box, ms per 4096, eight interleaved pairs of runs, by delay in units
+    // of 4096 cycles (profiles/r04_ab_stagger*.txt): 0 -> 33.50 / 32.40, 1 -> 33.33 / 32.20 (-0.5 %), 2 -> 32.50, 3 -> 32.24
+    if (wave >= 4) __builtin_amdgcn_s_sleep(64);
 #endif
     uint32_t it = 0;  // executed iterations (flag epoch)
     uint64_t mask_next = lwe[0];
@@ -2228,40 +1781,27 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
       mask_next = lwe[i + 1];
       // the same word in every lane: as a scalar, the rotation's bounds and signs cost no vector work
       const uint32_t a_hat = HX_UNIFORM((uint32_t)modulus_switch(mask_cur, LOG2N2));
-#if WAVE_CLASSIC_SYNC && !defined(TFHE_HIPEMU)
-      // the workgroup's LWEs back in step every so many mask elements (speed only, as in the split-key engine), the
-      // waves of the upper half of the workgroup de-phased again behind it (WAVE_STAGGER)
-      if (i % (uint32_t)WAVE_CLASSIC_SYNC == 0 && i != 0) {
-        __builtin_amdgcn_s_barrier();
-        if (WAVE_STAGGER && wave >= 4)
-          for (int u = 0; u < WAVE_STAGGER; ++u) __builtin_amdgcn_s_sleep(64);
-      }
-#endif
+      // (a workgroup barrier every 4 / 16 / 64 mask elements, as in the split-key engine: 34.30 / 33.42 / 33.27 ms per 4096
+      // against 33.27 without, profiles/r05_ab_classic_sync.txt)
       if (a_hat == 0) continue;  // uniform over the pair (bootstrap.rs:334)
       ++it;
       if constexpr (LEVEL_CT == 1) {
         cplx d[16], ka0[4], ka1[4], kb0[4], kb1[4];
         const cplx *b0, *b1;
         key_rows(i, 0, b0, b1);
-        if (WAVE_EARLY_CHUNKS >= 1) key_request(ka0, ka1, b0, b1, 0);
-        if (WAVE_EARLY_CHUNKS >= 2) key_request(kb0, kb1, b0, b1, 1);
+        key_request(ka0, ka1, b0, b1, 0);  // chunk 0 of the key at the top of the iteration, the rest at the MAC
         HX_SCHED_FENCE();
-        HX_PRIO(WAVE_PRIO_A);
+        HX_PRIO(PRIO_DIGITS);
         make_digits(d, a_hat, 0);
-        HX_PRIO(WAVE_PRIO_B);
-        wave_forward<WAVE_RESIDENT, WAVE_UNIFORM_LITERALS != 0>(d, ctx, &res_tw);
-        HX_PRIO(WAVE_PRIO_C);
-        // in place: d becomes the Fourier-domain output of polynomial w, first inverse pass applied
-#if WAVE_DEFER_DONE
-        mac_impl(d, d, ka0, ka1, kb0, kb1, b0, b1, 0, it, std::integral_constant<bool, WAVE_FUSE_PASS1 != 0>{}, true, std::false_type{});
-        HX_PRIO(WAVE_PRIO_D);
-        wave_inverse_accumulate<(WAVE_FUSE_PASS1 != 0) ? 1 : 0, false, NEGACC, false, WAVE_RESIDENT, WAVE_UNIFORM_LITERALS != 0>(
-            d, acc_re, acc_im, ctx, &res_tw, [&]() { flag_wait(r_done_ot, it); });
-#else
-        mac(d, d, ka0, ka1, kb0, kb1, b0, b1, 0, it, std::integral_constant<bool, WAVE_FUSE_PASS1 != 0>{});
-        HX_PRIO(WAVE_PRIO_D);
-        wave_inverse_accumulate<(WAVE_FUSE_PASS1 != 0) ? 1 : 0, false, NEGACC, false, WAVE_RESIDENT, WAVE_UNIFORM_LITERALS != 0>(d, acc_re, acc_im, ctx, &res_tw);
-#endif
+        HX_PRIO(PRIO_FORWARD);
+        wave_forward<2, 1>(d, ctx, &res_tw);
+        HX_PRIO(PRIO_MAC);
+        // in place: d becomes the Fourier-domain output of polynomial w, first inverse pass applied.  (Waiting for the
+        // partner's "done" in front of the inverse transposition's first store instead: 32.17 -> 32.16 ms per 4096,
+        // profiles/r05_ab_classic_defer.txt, not kept.)
+        mac(d, d, ka0, ka1, kb0, kb1, b0, b1, 0, it, std::true_type{});
+        HX_PRIO(PRIO_INVERSE);
+        wave_inverse_accumulate<1, false, NEGACC, false, 2, 1>(d, acc_re, acc_im, ctx, &res_tw);
       } else {
         cplx o[16];
         for (uint32_t idx = 0; idx < level; ++idx) {
@@ -2269,14 +1809,14 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
           const cplx *b0, *b1;
           key_rows(i, idx, b0, b1);
           HX_SCHED_FENCE();
-          HX_PRIO(WAVE_PRIO_A);
+          HX_PRIO(PRIO_DIGITS);
           make_digits(d, a_hat, idx);
-          HX_PRIO(WAVE_PRIO_B);
+          HX_PRIO(PRIO_FORWARD);
           wave_forward(d, ctx);
-          HX_PRIO(WAVE_PRIO_C);
+          HX_PRIO(PRIO_MAC);
           mac(o, d, ka0, ka1, kb0, kb1, b0, b1, idx, (it - 1) * level + idx + 1, std::false_type{});
         }
-        HX_PRIO(WAVE_PRIO_D);
+        HX_PRIO(PRIO_INVERSE);
         wave_inverse_accumulate<0, false, NEGACC>(o, acc_re, acc_im, ctx);
       }
     }
@@ -2370,7 +1910,7 @@ __global__ void __launch_bounds__(TPB) pbs_fft_wave_kernel(PbsArgs a, FftTables 
 
 }  // namespace wavek
 
-// host side of WAVE_UNIFORM_LITERALS: the literals are the table entries they stand for (checked when the tables are
+// host side of the literal twiddles (LIT_F1, LIT_E64): the literals are the table entries they stand for (checked when the tables are
 // built, tables.hip)
 bool wave_literal_twiddles_match(const double *fwd, const double *inv) {
   static const int fidx[8] = {1, 2, 4, 6, 8, 10, 12, 14};
@@ -2413,12 +1953,8 @@ template <int B>
 static void launch_split_t(hipStream_t st, const PbsArgs &a, const FftTables &tb) {
   using namespace wavek;
   hx_set_dynamic_smem_once<pbs_fft_wave_kernel<1, B, 0, false, NTT_SPLIT_LIMBS>>(SMEM_BYTES);
-  unsigned per_block = lwes_per_block(a.num_samples);
-  if (per_block > WAVE_SPLIT_LWES) per_block = WAVE_SPLIT_LWES;
+  const unsigned per_block = lwes_per_block(a.num_samples);
   const unsigned blocks = (a.num_samples + per_block - 1) / per_block;
-#if WAVE_SPLIT_PACE
-  if (a.pace) HX_CHECK(hipMemsetAsync(a.pace, 0, 8 * 32 * sizeof(uint32_t), st));
-#endif
   note_pbs_instantiation(1, B, 0, PBS_INST_LIMBS, per_block, 2048, 2);
   HX_LAUNCH((pbs_fft_wave_kernel<1, B, 0, false, NTT_SPLIT_LIMBS>), dim3(blocks), dim3(128 * per_block), SMEM_BYTES, st, a,
             tb);
@@ -2442,8 +1978,8 @@ static void launch_wave_mb_t(hipStream_t st, const PbsArgs &a, const FftTables &
   const bool share = !a.mb_no_share;  // hip_backend_set_fft_kernel(7) on the multi-bit entry point: pairs only (comparison)
   if (per_block == 3 && share) per_block = 4;  // 513 .. 768 LWEs: fuller workgroups that can share (4-12 % faster)
   const unsigned blocks = (a.num_samples + per_block - 1) / per_block;
-  // full workgroups of a one-level set: all eight waves share the key loads of the four LWEs (OCTET)
-  if constexpr ((L == 1 || (L >= 2 && WAVE_MB_OCTET >= 2)) && WAVE_MB_OCTET != 0) {
+  // full workgroups of a set with a compile-time level count: all eight waves share the key loads of the four LWEs (OCTET)
+  if constexpr (L != 0) {
     if (per_block == 4 && share && !a.mb_no_octet) {
       hx_set_dynamic_smem_once<pbs_fft_wave_kernel<L, B, G, false, 0, true>>(SMEM_BYTES);
       note_pbs_instantiation(L, B, G, PBS_INST_OCTET, per_block, 2048, 2);

@@ -47,14 +47,11 @@ constexpr size_t smem_bytes(int waves) { return (size_t)waves * BUF_BYTES + (siz
 
 HX_DEV cplx ldg_c(const double *t, int idx) { return cplx{t[2 * idx], t[2 * idx + 1]}; }
 
-#ifndef W3_UNIFORM_LITERALS
-// 1: the twiddles that are the same in every lane and every launch (forward stages 0..2: fwd[1..7]; inverse half = 4:
+// The twiddles that are the same in every lane and every launch (forward stages 0..2: fwd[1..7]; inverse half = 4:
 // inv[4..7]) are literals of the instruction stream instead of broadcast reads of the LDS table, as in the N = 2048
 // kernel (pbs_fft_wave.hip); the inverse butterflies whose twiddle is 1 or -i lose their products (same roundings).
 // fwd[(1 << d) + g] does not depend on N, so these are the N = 2048 kernel's values; checked against the host tables
 // when they are built (tables.hip).
-#define W3_UNIFORM_LITERALS 1
-#endif
 constexpr double W3_LIT_F[7][2] = {{0x1.6a09e667f3bcdp-1, 0x1.6a09e667f3bcdp-1},   // fwd[1]
                                    {0x1.d906bcf328d46p-1, 0x1.87de2a6aea963p-2},   // fwd[2]
                                    {-0x1.87de2a6aea963p-2, 0x1.d906bcf328d46p-1},  // fwd[3] = i fwd[2]
@@ -75,11 +72,7 @@ HX_DEV void flag_set(uint32_t *f, uint32_t v) { __hip_atomic_store(f, v, __ATOMI
 HX_DEV void flag_wait(uint32_t *f, uint32_t v) {
   while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v) __builtin_amdgcn_s_sleep(1);
 }
-#ifndef W3_PRIO_OFF
 #define W3_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define W3_PRIO(p) do { } while (0)
-#endif
 #endif
 
 // one radix-2 stage over register-index bit BIT of 8 points; tw(r) is the twiddle of the butterfly (r, r | 1<<BIT)
@@ -118,80 +111,33 @@ HX_DEV void bfly_mi_fma(cplx &a, cplx &b) {
   a.im = o1i;
 }
 
-#ifndef W3_PROBE
-#define W3_PROBE 0
-#endif
-// timing probe: what an exchange of three register bits with lane bits would cost as 48 lane swaps
-HX_DEV void w3_probe_swaps(cplx (&d)[8]) {
-  HX_UNROLL
-  for (int rep = 0; rep < 3; ++rep)
-    HX_UNROLL
-    for (int r = 0; r < 4; ++r) {
-      uint32_t a[4], b[4];
-      __builtin_memcpy(a, &d[r], 16);
-      __builtin_memcpy(b, &d[r + 4], 16);
-      HX_UNROLL
-      for (int k = 0; k < 4; ++k) {
-        if (rep == 1) hx_permlane16_swap(a[k], b[k]);
-        else hx_permlane32_swap(a[k], b[k]);
-      }
-      __builtin_memcpy(&d[r], a, 16);
-      __builtin_memcpy(&d[r + 4], b, 16);
-    }
-}
-
 struct Ctx {
   cplx *buf;      // my exchange buffer
   const cplx *T;  // table
   int lane;
 };
 
-#ifndef W3_ROT_PAIRS
-// 1: the rotation fetches the staged words of two consecutive register rows (512 bytes apart) with one two-address
-// LDS read; the ring's first 512 bytes are staged a second time behind its end (the buffer has 1,024 spare bytes), as in
-// the N = 2048 kernel (pbs_fft_wave.hip, WAVE_ROT_PAIRS)
-#define W3_ROT_PAIRS 1
-#endif
-#ifndef W3_RESIDENT
-// twiddles kept in registers for the whole launch (read once in front of the CMUX loop), as in the N = 2048 kernel:
-// 1 = forward stages 3..5 (seven values that depend on lane >> 3), 2 = also inverse half = 8, 16, 32 (seven on lane & 7)
-#define W3_RESIDENT 1
-#endif
+// the forward twiddles of stages 3..5 (seven values that depend on lane >> 3), kept in registers for the whole launch (read
+// once in front of the CMUX loop), as in the N = 2048 kernel; the inverse ones of half = 8, 16, 32 are read from the table
 struct Resident3 {
-  cplx f3, f4[2], f5[4];   // forward stages 3, 4, 5
-  cplx i8, i16[2], i32[4]; // inverse half = 8, 16, 32
+  cplx f3, f4[2], f5[4];  // forward stages 3, 4, 5
 };
-template <int LEVEL>
 HX_DEV void load_resident3(Resident3 &t, const cplx *T, int lane) {
-  const int hi3 = lane >> 3, lo3 = lane & 7;
-  if constexpr (LEVEL >= 1) {
-    t.f3 = T[T_FB3 + hi3];
-    t.f4[0] = T[T_FB4 + hi3];
-    t.f4[1] = T[T_FB4 + 8 + hi3];
-    HX_UNROLL
-    for (int q = 0; q < 4; ++q) t.f5[q] = T[T_FB5 + 8 * q + hi3];
-  }
-  if constexpr (LEVEL >= 2) {
-    t.i8 = T[T_INV + 8 + lo3];
-    t.i16[0] = T[T_INV + 16 + lo3];
-    t.i16[1] = T[T_INV + 24 + lo3];
-    HX_UNROLL
-    for (int q = 0; q < 4; ++q) t.i32[q] = T[T_INV + 32 + 8 * q + lo3];
-  }
+  const int hi3 = lane >> 3;
+  t.f3 = T[T_FB3 + hi3];
+  t.f4[0] = T[T_FB4 + hi3];
+  t.f4[1] = T[T_FB4 + 8 + hi3];
+  HX_UNROLL
+  for (int q = 0; q < 4; ++q) t.f5[q] = T[T_FB5 + 8 * q + hi3];
 }
 
 // digits (layout LA) -> transform, left in registers (layout LC) and in my buffer at the LC slots
-template <int RES = 0>
-HX_DEV void forward(cplx (&d)[8], Ctx c, const Resident3 *res = nullptr) {
+HX_DEV void forward(cplx (&d)[8], Ctx c, const Resident3 &res) {
   HX_OPAQUE(c.lane);
   const int lane = c.lane, hi3 = lane >> 3, lo3 = lane & 7;
   const cplx *T = c.T;
   {  // stages 0..2: position bits 8, 7, 6 = register bits 2, 1, 0; group = the bits above
-#if W3_UNIFORM_LITERALS
     auto tw = [](int x) { return cplx{W3_LIT_F[x][0], W3_LIT_F[x][1]}; };
-#else
-    auto tw = [&](int x) { return T[T_FA + x]; };
-#endif
     const cplx w0 = tw(0);
     stage8<2>(d, [&](int) { return w0; });
     HX_SCHED_FENCE();  // twiddle loads stay next to their stage (hoisted together they cost 80 registers)
@@ -202,33 +148,26 @@ HX_DEV void forward(cplx (&d)[8], Ctx c, const Resident3 *res = nullptr) {
     stage8<0>(d, [&](int r) { return w2[r >> 1]; });
     HX_SCHED_FENCE();
   }
-#if !(W3_PROBE & 1)  // timing probe (wrong results): bit 0 = no LA <-> LB transpositions, bit 1 = their cost as lane swaps
   {
     cplx *pa = c.buf + lane;  // LA slots of P1
     HX_UNROLL
     for (int r = 0; r < 8; ++r) pa[72 * r] = d[r];
   }
   HX_WAVE_SYNC();
-#endif
-#if W3_PROBE & 2
-  w3_probe_swaps(d);
-#endif
   {  // stages 3..5: position bits 5, 4, 3; group = hi3 . (register bits above)
-#if !(W3_PROBE & 1)
     const cplx *pb = c.buf + hi3 * 72 + lo3;  // LB slots of P1
     HX_UNROLL
     for (int r = 0; r < 8; ++r) d[r] = pb[8 * r];
     HX_WAVE_SYNC();
-#endif
-    const cplx w3 = RES >= 1 ? res->f3 : T[T_FB3 + hi3];
+    const cplx w3 = res.f3;
     stage8<2>(d, [&](int) { return w3; });
     HX_SCHED_FENCE();
-    const cplx w4[2] = {RES >= 1 ? res->f4[0] : T[T_FB4 + hi3], RES >= 1 ? res->f4[1] : T[T_FB4 + 8 + hi3]};
+    const cplx w4[2] = {res.f4[0], res.f4[1]};
     stage8<1>(d, [&](int r) { return w4[r >> 2]; });
     HX_SCHED_FENCE();
     cplx w5[4];
     HX_UNROLL
-    for (int q = 0; q < 4; ++q) w5[q] = RES >= 1 ? res->f5[q] : T[T_FB5 + 8 * q + hi3];
+    for (int q = 0; q < 4; ++q) w5[q] = res.f5[q];
     stage8<0>(d, [&](int r) { return w5[r >> 1]; });
     HX_SCHED_FENCE();
     cplx *pb2 = c.buf + hi3 * 72 + lo3;  // LB slots of P2
@@ -258,9 +197,8 @@ HX_DEV void forward(cplx (&d)[8], Ctx c, const Resident3 *res = nullptr) {
 
 // o (layout LC) -> backward transform, untwist, to the torus, added to the (negated) accumulator, which is
 // then staged for the next rotation
-template <bool NEG, int RES = 0>
-HX_DEV void inverse_accumulate(cplx (&o)[8], uint64_t (&acc_re)[8], uint64_t (&acc_im)[8], Ctx c,
-                               const Resident3 *res = nullptr) {
+template <bool NEG>
+HX_DEV void inverse_accumulate(cplx (&o)[8], uint64_t (&acc_re)[8], uint64_t (&acc_im)[8], Ctx c) {
   HX_OPAQUE(c.lane);
   const int lane = c.lane, hi3 = lane >> 3, lo3 = lane & 7;
   const cplx *T = c.T;
@@ -272,7 +210,6 @@ HX_DEV void inverse_accumulate(cplx (&o)[8], uint64_t (&acc_re)[8], uint64_t (&a
     bfly_plain(o[4], o[6]);
     bfly_mi(o[5], o[7]);
     HX_SCHED_FENCE();
-#if W3_UNIFORM_LITERALS
     {  // half = 4: twiddles 1, e^{-i pi/4}, -i, -i e^{-i pi/4}
       const cplx a1{W3_LIT_I5[0], W3_LIT_I5[1]};
       bfly_one_fma(o[0], o[4]);
@@ -280,10 +217,6 @@ HX_DEV void inverse_accumulate(cplx (&o)[8], uint64_t (&acc_re)[8], uint64_t (&a
       bfly_mi_fma(o[2], o[6]);
       bfly(o[3], o[7], cplx{a1.im, -a1.re});
     }
-#else
-    const cplx w4[4] = {T[T_INV + 4], T[T_INV + 5], T[T_INV + 6], T[T_INV + 7]};
-    stage8<2>(o, [&](int r) { return w4[r & 3]; });
-#endif
     HX_SCHED_FENCE();
     cplx *pc = c.buf + lane * 9;  // LC slots of P2
     HX_UNROLL
@@ -295,34 +228,27 @@ HX_DEV void inverse_accumulate(cplx (&o)[8], uint64_t (&acc_re)[8], uint64_t (&a
     HX_UNROLL
     for (int r = 0; r < 8; ++r) o[r] = pb2[9 * r];
     HX_WAVE_SYNC();
-    const cplx w8 = RES >= 2 ? res->i8 : T[T_INV + 8 + lo3];
+    const cplx w8 = T[T_INV + 8 + lo3];
     stage8<0>(o, [&](int) { return w8; });
     HX_SCHED_FENCE();
-    const cplx w16[2] = {RES >= 2 ? res->i16[0] : T[T_INV + 16 + lo3], RES >= 2 ? res->i16[1] : T[T_INV + 24 + lo3]};
+    const cplx w16[2] = {T[T_INV + 16 + lo3], T[T_INV + 24 + lo3]};
     stage8<1>(o, [&](int r) { return w16[r & 1]; });
     HX_SCHED_FENCE();
     cplx w32[4];
     HX_UNROLL
-    for (int q = 0; q < 4; ++q) w32[q] = RES >= 2 ? res->i32[q] : T[T_INV + 32 + 8 * q + lo3];
+    for (int q = 0; q < 4; ++q) w32[q] = T[T_INV + 32 + 8 * q + lo3];
     stage8<2>(o, [&](int r) { return w32[r & 3]; });
     HX_SCHED_FENCE();
-#if !(W3_PROBE & 1)
     cplx *pb = c.buf + hi3 * 72 + lo3;  // LB slots of P1
     HX_UNROLL
     for (int r = 0; r < 8; ++r) pb[8 * r] = o[r];
-#endif
   }
   HX_WAVE_SYNC();
-#if W3_PROBE & 2
-  w3_probe_swaps(o);
-#endif
   {  // half = 64, 128, 256: position bits 6, 7, 8 = register bits 0, 1, 2 in LA; j = (register bits below) . lane
-#if !(W3_PROBE & 1)
     const cplx *pa = c.buf + lane;  // LA slots of P1
     HX_UNROLL
     for (int r = 0; r < 8; ++r) o[r] = pa[72 * r];
     HX_WAVE_SYNC();
-#endif
     const cplx w64 = T[T_INV + 64 + lane];
     stage8<0>(o, [&](int) { return w64; });
     HX_SCHED_FENCE();
@@ -346,9 +272,7 @@ HX_DEV void inverse_accumulate(cplx (&o)[8], uint64_t (&acc_re)[8], uint64_t (&a
     from_torus_add(acc_im[r], ti, kt);
     stg[r * 64] = acc_re[r];
     stg[512 + r * 64] = acc_im[r];
-#if W3_ROT_PAIRS
     if (r == 0) stg[1024] = acc_re[0];  // the ring's first 64 words again behind its end
-#endif
     if (r & 1) HX_SCHED_FENCE();
   }
   HX_WAVE_SYNC();
@@ -444,9 +368,7 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
       p[r * 64] = acc_re[r];
       p[512 + r * 64] = acc_im[r];
     }
-#if W3_ROT_PAIRS
     p[1024] = acc_re[0];  // the ring's first 64 words again behind its end
-#endif
     HX_WAVE_SYNC();
   };
 
@@ -460,9 +382,7 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
     const uint32_t ub = (uint32_t)(((int32_t)ln - (int32_t)(a_hat & (N - 1))) * 8) + ((a_hat & N) ? 0u : 0x80000000u);
     int32_t lowest = 0;
     uint32_t vzero = 0;
-#ifndef WAVE_STAGED_SGPR_BASE
     HX_LAUNDER(vzero);  // base of the staged copy in a vector register (a scalar operand doubles the add's cost)
-#endif
     const char *staged = (const char *)buf64 + vzero;
     uint64_t sp0[2] = {0, 0}, sp1[2] = {0, 0};
     (void)sp0;
@@ -472,8 +392,10 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
       const int32_t u0 = (int32_t)(ub + r * 512u), u1 = (int32_t)(ub + r * 512u + 4096u);
       const uint32_t m0 = (uint32_t)(u0 >> 31), m1 = (uint32_t)(u1 >> 31);
       const uint64_t M0 = ((uint64_t)m0 << 32) | m0, M1 = ((uint64_t)m1 << 32) | m1;
-#if W3_ROT_PAIRS
-      if ((r & 1) == 0) {  // rows r and r + 1 of both halves: the second word sits 512 bytes behind the first
+      // rows r and r + 1 of both halves with one two-address LDS read: the second word sits 512 bytes behind the first;
+      // the ring's first 512 bytes are staged a second time behind its end (the buffer has 1,024 spare bytes), as in the
+      // N = 2048 kernel
+      if ((r & 1) == 0) {
         const uint64_t *q0 = (const uint64_t *)(staged + (u0 & 0x1ff8)), *q1 = (const uint64_t *)(staged + (u1 & 0x1ff8));
         sp0[0] = q0[0];
         sp0[1] = q0[64];
@@ -481,10 +403,6 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
         sp1[1] = q1[64];
       }
       const uint64_t s0 = sp0[r & 1], s1 = sp1[r & 1];
-#else
-      const uint64_t s0 = *(const uint64_t *)(staged + (u0 & 0x1ff8));
-      const uint64_t s1 = *(const uint64_t *)(staged + (u1 & 0x1ff8));
-#endif
       const uint64_t x0 = ((acc_re[r] ^ M0) + s0) ^ M0, x1 = ((acc_im[r] ^ M1) + s1) ^ M1;
       if constexpr (L1) {
         if constexpr (EXACT) {
@@ -517,7 +435,7 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
 
   stage_acc();
   Resident3 res3;
-  load_resident3<W3_RESIDENT>(res3, T, lane);
+  load_resident3(res3, T, lane);
   uint32_t epoch = 0;
   uint64_t mask_next = lwe[0];
   for (uint32_t i = 0; i < a.n; ++i) {
@@ -533,7 +451,7 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
       W3_PRIO(0);
       make_digits(d, a_hat, idx);
       W3_PRIO(1);
-      forward<W3_RESIDENT>(d, ctx0, &res3);
+      forward(d, ctx0, res3);
       W3_PRIO(2);
       // my transform is published: tell the others, wait for theirs
       if (lane == 0) flag_set(ready + w, epoch);
@@ -570,7 +488,7 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
         if (q != w) flag_wait(done + q, epoch);  // nobody reads my buffer any more: it may be reused
     }
     W3_PRIO(3);
-    inverse_accumulate<true, W3_RESIDENT>(o, acc_re, acc_im, ctx0, &res3);
+    inverse_accumulate<true>(o, acc_re, acc_im, ctx0);
   }
 
   // ---- sample extraction (cc/algorithms/glwe_sample_extraction.rs:119-146); many-LUT outputs
@@ -599,8 +517,8 @@ __global__ void __launch_bounds__(MAX_WAVES * 64) pbs_fft_wave3_kernel(PbsArgs a
 
 }  // namespace wave3k
 
-// host side of W3_UNIFORM_LITERALS: the literals are the table entries they stand for (tables.hip checks when it builds
-// the N = 1024 tables)
+// host side of the literal twiddles (W3_LIT_F, W3_LIT_I5): the literals are the table entries they stand for (tables.hip
+// checks when it builds the N = 1024 tables)
 bool wave3_literal_twiddles_match(const double *fwd, const double *inv) {
   for (int x = 0; x < 7; ++x)
     if (fwd[2 * (1 + x)] != wave3k::W3_LIT_F[x][0] || fwd[2 * (1 + x) + 1] != wave3k::W3_LIT_F[x][1]) return false;

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Host-emulation build of a tuning variant of one kernel file, for the CPU test tier:
+# Host-emulation build of a variant of one kernel file (extra -D flags or an edited copy of the file), for the CPU test tier:
 #   tools/build_emu_variant.sh name file.hip -DX=1 -DY=2   ->  variants/emu_<name>.so
 # run the tests on it with  TFHE_EMU_LIB=variants/emu_<name>.so python -m pytest tests -m "not gpu" -k emu
 set -e

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Builds tuning variants of one kernel file: variants/lib_<name>.so = the in-tree objects with that file
+"""Builds variants of one kernel file: variants/lib_<name>.so = the in-tree objects with that file
 (default pbs_fft_wave.hip; prefix the flags with "file.hip:" for another) recompiled under extra -D flags.
-Usage: build_variants.py name=-DX=1,-DY=2 other=pbs_fft_wave3.hip:-DZ=0 ...
+The kernel sources accept two: the measurement builds -DWAVE_PROBE_TS=1 and -DWAVE_MB_PROBE=1 (tools/probes/README.md;
+tuning A/B runs edit a copy of the tree instead, tools/ab_against_tree.sh).
+Usage: build_variants.py ts=-DWAVE_PROBE_TS=1 mbp=-DWAVE_MB_PROBE=1 ...
 Run a variant with TFHE_HIP_BACKEND_LIB=variants/lib_<name>.so python bench.py ..."""
 import os
 import subprocess
