@@ -8,11 +8,17 @@ One "step" = one batched PBS launch (modulus switch + 918 CMUXes + sample extrac
 rank owns its own 4096-LWE shard and a replica of the key; no data-path collective (weak
 scaling); the barrier/max-over-ranks timing uses torch.distributed (RCCL).
 
-Prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.  At N = 1 the line
-also carries `extra`: the single-PBS latency, the N=1024/k=2 datapoint, BASELINE.json's configs 3 (NTT engine) and
-4 (multi-bit g = 3, plus the reference's GPU default g = 4), each at batch 4096 with its oracle-parity bit, and
-config 5 on one GPU (FheUint64 add / mul through the radix layer, results decrypted), and the reference's own GPU golden
-ciphertexts (its pbs_golden test: distance in phase, tools/golden_datapoint.py) — none of them part of `value`.
+Prints ONE JSON line.  A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+--dump-outputs files if asked for, and the line with `value`, `ms_per_step` and a `roofline` whose `traffic` comes from
+the committed, build-stamped counter record.
+
+--full adds everything else, none of it part of `value`: the decrypt check of a sample of the outputs, the rocprofv3
+counter passes behind `roofline.traffic`, `cpu_baseline`, and at N = 1 `extra`: the single-PBS latency, the N=1024/k=2
+datapoint, BASELINE.json's configs 3 (NTT engine) and 4 (multi-bit g = 3, plus the reference's GPU default g = 4), each
+at batch 4096 with its oracle-parity bit, config 5 on one GPU (FheUint64 add / mul through the radix layer, results
+decrypted), and the reference's own GPU golden ciphertexts (its pbs_golden test: distance in phase,
+tools/golden_datapoint.py); at N > 1 config 5 over the N GPUs.  --no-extra, --no-cpu-baseline, --no-pmc and --no-verify
+take single legs out of a --full run.
 """
 import argparse
 import ctypes as C
@@ -264,7 +270,7 @@ def run_in_process(lib, p, keys, devices, B, steps, warmup, kernel=0, verify=Tru
     elapsed = max(r["t1"] for r in res) - min(r["t0"] for r in res)
     per_gpu = [{"shard": i, "device": r["device"], "lwes": r["lwes"], "first_lwe": r["lo"], "seconds": r["t1"] - r["t0"],
                 "pbs_per_s": r["lwes"] * steps / (r["t1"] - r["t0"]), "kernel_ms_avg": sum(r["kernel_ms"]) / len(r["kernel_ms"]),
-                "verified": not r["bad"]} for i, r in enumerate(res)]
+                "verified": (not r["bad"]) if verify else None} for i, r in enumerate(res)]
     for r in res:
         assert not verify or not r["bad"], f"PBS outputs failed to decrypt at rows {r['bad'][:8]}"
     return elapsed, per_gpu, res[0]["shard"], res[0]["kernel_ms"], res[0]["kernel_id"]
@@ -376,18 +382,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=BATCH, help="LWEs per GPU per step (default: the metric's 4096)")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 generic LDS kernel, 2 throughput kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the config-3/4/5 and N=1024 datapoints under `extra`")
-    ap.add_argument("--no-pmc", action="store_true", help="do not take rocprofv3 counter passes during the run "
-                    "(`traffic` then comes from the committed build-stamped record)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the decrypt check (timing-ablation builds only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures or checks: the decrypt check, "
+                         "the rocprofv3 counter passes, the CPU baseline and the datapoints under `extra` (minutes, most "
+                         "of them CPU-oracle work); without it the run is the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the config-3/4/5 and N=1024 datapoints under `extra`")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not take rocprofv3 counter passes during the run "
+                    "(`traffic` then comes from the committed build-stamped record, as in a plain run)")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the decrypt check")
     ap.add_argument("--parity-sample", type=int, default=0,
                     help="LWEs of the config-3 / config-4 launches compared word for word with the CPU oracle "
                          "(0 = the whole batch: about 2.5 min of CPU work on 16 threads)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="PBS count of the CPU baseline sample (0 = auto)")
     ap.add_argument("--scale-quick", action="store_true",
-                    help="headline only (= --no-extra --no-cpu-baseline --no-pmc): the form for a 1/2/4/8-GPU scaling sweep — no CPU-oracle "
-                         "legs (they are 95 %% of the default run's wall time), per-GPU ms_per_step and config 5's active-GPU count in the line")
+                    help="the form for a 1/2/4/8-GPU scaling sweep: the headline alone even under --full (of its legs only the "
+                         "decrypt check stays), per-GPU ms_per_step and config 5's active-GPU count in the line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's output ciphertexts (shard 0 of a multi-GPU run) to "
                          "DIR/*.npy as float64, a fixed sample of 1024 rows when the batch is larger")
@@ -395,8 +406,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.scale_quick:
+    if args.scale_quick or not args.full:
         args.no_extra = args.no_cpu_baseline = args.no_pmc = True
+    if not args.full:
+        args.no_verify = True
     if args.fheuint64_worker:
         import tfhe_rs_amd  # noqa: F401
         from tfhe_rs_amd import ffi

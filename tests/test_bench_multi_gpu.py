@@ -71,12 +71,12 @@ def test_more_shards_than_gpus_is_refused_unless_faked(monkeypatch):
 
 @pytest.mark.gpu
 def test_bench_command_line_with_two_fake_gpus():
-    """The driver's command shape, `python bench.py --gpus 2`, with no torch.distributed launcher around it: prints
+    """The driver's command shape, `python bench.py --gpus 2 --full`, with no torch.distributed launcher around it: prints
     n_gpus = 2, both shards verified; config 5 runs through both shardings (by the caller and inside the library)."""
     env = dict(os.environ, TFHE_BENCH_FAKE_MULTI_GPU="1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                                   "--warmup", "1"], env=env, text=True, timeout=1500)
+                                   "--warmup", "1", "--full"], env=env, text=True, timeout=1500)
     r = json.loads(out.strip().splitlines()[-1])
     assert r["n_gpus"] == 2 and r["fake_multi_gpu"] is True
     assert len(r["per_gpu"]) == 2 and all(g["verified"] for g in r["per_gpu"])
