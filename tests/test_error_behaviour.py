@@ -169,6 +169,57 @@ ABORTS = {
         """, "grouping factor in 1..4 dividing the LWE dimension"),
 }
 
+# Misuse of a radix scratch: every operation checks the handle it is given the same way (kind, size-only, cleanup)
+BSK = "ffi.CudaLweBootstrapKeyParamsFFI(12, 1, 2048, 23, 1, 2048, 1, 0)"
+KSK = "ffi.CudaLweKeyswitchKeyParamsFFI(2048, 12, 4, 4)"
+RADIX_HEAD = """
+s = ffi.CudaStreamsFFI((C.c_void_p * 1)(S), (C.c_uint32 * 1)(0), 1)
+mem = C.c_void_p()
+v = gpu.CudaVec(8 * 2049, st)
+ct = ffi.CudaRadixCiphertextFFI(v.ptr, None, None, 8, 8, 2048)
+one = (C.c_void_p * 1)(v.ptr)
+BSK, KSK = %s, %s
+""" % (BSK, KSK)
+SUB_LAUNCH = ("lib.cuda_sub_and_propagate_single_carry_64_inplace_async(s, C.byref(ct), C.byref(ct), None, None, mem, one, one, "
+              "0, 0)")
+RADIX_ABORTS = {
+    "cmux scratch handed to bitop": ("""
+        lib.scratch_cuda_cmux_64_async(s, C.byref(mem), BSK, KSK, 8, 4, 4, True, 0)
+        lib.cuda_integer_bitop_inplace_64_async(s, C.byref(ct), C.byref(ct), mem, one, one)
+        """, "integer_bitop: foreign scratch pointer"),
+    "propagate scratch handed to sub": ("""
+        lib.scratch_cuda_propagate_single_carry_64_inplace_async(s, C.byref(mem), BSK, KSK, 8, 4, 4, 0, True, 0)
+        %s
+        """ % SUB_LAUNCH, "sub_and_propagate_single_carry: foreign scratch pointer"),
+    "launch on a size-only sub scratch": ("""
+        lib.scratch_cuda_sub_and_propagate_single_carry_64_inplace_async(s, C.byref(mem), BSK, KSK, 8, 4, 4, 0, False, 0)
+        %s
+        """ % SUB_LAUNCH, "sub_and_propagate_single_carry: scratch was created with allocate_gpu_memory=false"),
+    "launch on a size-only comparison scratch": ("""
+        lib.scratch_cuda_integer_comparison_64_async(s, C.byref(mem), BSK, KSK, 8, 4, 4, 0, False, False, 0)
+        lib.cuda_integer_comparison_64_async(s, C.byref(ct), C.byref(ct), C.byref(ct), mem, one, one)
+        """, "integer_comparison: scratch was created with allocate_gpu_memory=false"),
+    "launch on a size-only scalar comparison scratch": ("""
+        lib.scratch_cuda_integer_scalar_comparison_64_async(s, C.byref(mem), BSK, KSK, 8, 4, 4, 0, False, False, 0)
+        lib.cuda_integer_scalar_comparison_64_async(s, C.byref(ct), C.byref(ct), None, None, mem, one, one, 0)
+        """, "integer_scalar_comparison: scratch was created with allocate_gpu_memory=false"),
+    "radix cleanup of zeroed host memory": ("""
+        junk = (C.c_uint64 * 64)()
+        p = C.c_void_p(C.addressof(junk))
+        lib.cleanup_cuda_cmux_64(s, C.byref(p))
+        """, "cleanup cmux: foreign scratch pointer"),
+    "second radix cleanup of the same variable": ("""
+        lib.scratch_cuda_cmux_64_async(s, C.byref(mem), BSK, KSK, 8, 4, 4, True, 0)
+        lib.cleanup_cuda_cmux_64(s, C.byref(mem))
+        assert not mem.value, mem.value             # the first cleanup nulled the caller's pointer
+        lib.cleanup_cuda_cmux_64(s, C.byref(mem))
+        """, "cleanup cmux: foreign scratch pointer"),
+    "radix scratch creation through a null mem_ptr": ("""
+        lib.scratch_cuda_propagate_single_carry_64_inplace_async(s, None, BSK, KSK, 8, 4, 4, 0, True, 0)
+        """, "propagate_single_carry: null pointer"),
+}
+ABORTS.update({name: (RADIX_HEAD + textwrap.dedent(body), needle) for name, (body, needle) in RADIX_ABORTS.items()})
+
 
 @pytest.mark.parametrize("name", sorted(ABORTS))
 def test_misuse_prints_and_aborts(name):

@@ -90,6 +90,7 @@ static void axpy(hipStream_t st, uint64_t *out, const uint64_t *out_idx, const u
 struct Params {
   uint32_t big_n, small_n, k, N, pbs_base_log, pbs_level, ks_base_log, ks_level, msg, carry, ms_type;
   uint32_t grouping;  // 0: classic PBS; g >= 1: multi-bit PBS with that grouping factor (pbs_type = MULTI_BIT)
+  uint64_t delta() const { return ((uint64_t)1 << 63) / ((uint64_t)msg * carry); }  // scaling factor of a block's value
 };
 
 static Params make_params(CudaLweBootstrapKeyParamsFFI b, CudaLweKeyswitchKeyParamsFFI k, uint32_t msg, uint32_t carry,
@@ -112,7 +113,7 @@ static Params make_params(CudaLweBootstrapKeyParamsFFI b, CudaLweKeyswitchKeyPar
 // cuda/src/integer/integer.cuh:1266-1305 (generate_lookup_table_with_encoding, same in/out encoding)
 static void generate_lut(const Params &p, uint64_t *acc, const std::function<uint64_t(uint64_t)> &f) {
   const uint32_t sup = p.msg * p.carry, box = p.N / sup;
-  const uint64_t delta = ((uint64_t)1 << 63) / sup;
+  const uint64_t delta = p.delta();
   std::fill(acc, acc + (size_t)p.k * p.N, 0);
   uint64_t *body = acc + (size_t)p.k * p.N;
   for (uint32_t i = 0; i < sup; ++i)
@@ -128,7 +129,7 @@ static void generate_lut(const Params &p, uint64_t *acc, const std::function<uin
 static uint32_t many_lut_stride(const Params &p, uint32_t fn) { return p.N / fn; }
 static void generate_many_lut(const Params &p, uint64_t *acc, const std::vector<std::function<uint64_t(uint64_t)>> &fs) {
   const uint32_t sup = p.msg * p.carry, box = p.N / sup, fn = (uint32_t)fs.size(), inputs = sup / fn;
-  const uint64_t delta = ((uint64_t)1 << 63) / sup;
+  const uint64_t delta = p.delta();
   std::fill(acc, acc + (size_t)(p.k + 1) * p.N, 0);
   uint64_t *body = acc + (size_t)p.k * p.N;
   for (uint32_t t = 0; t < fn; ++t)
@@ -154,7 +155,7 @@ static T *dev_upload(hipStream_t st, const std::vector<T> &h) {
   T *d = nullptr;
   if (h.empty()) return d;
   if (t_dry) {
-    t_bytes += h.size() * sizeof(T);
+    t_bytes += h.size() * sizeof(T);  // (counted by a size query only: a real creation returns less, see scratch_create)
     return d;
   }
   d = (T *)scratch_alloc(h.size() * sizeof(T));
@@ -224,8 +225,6 @@ static uint32_t num_inputs_on_gpu(uint32_t total, uint32_t gpu, uint32_t gpus) {
 }
 
 struct LutDriver {
-  static constexpr uint32_t kMagic = 0x52445231;  // "RDR1"
-  uint32_t magic = kMagic;
   Params p{};
   uint32_t cap = 0, num_luts = 0, many_max = 1;
   struct PerGpu {
@@ -242,7 +241,7 @@ struct LutDriver {
   };
   std::vector<PerGpu> gpus;
 
-  void scratch_pbs(hipStream_t st, PerGpu &g) {
+  void scratch_pbs(hipStream_t st, PerGpu &g) {  // (the byte counts the PBS scratch functions return are dropped)
     if (p.grouping)
       scratch_cuda_multi_bit_programmable_bootstrap_64_async(st, g.gpu, &g.pbs_buf, p.k, p.N, p.pbs_level, cap, !t_dry);
     else
@@ -462,7 +461,6 @@ struct LutDriver {
         if (d) scratch_free(d);
     }
     gpus.clear();
-    magic = 0;
   }
 };
 
@@ -475,15 +473,73 @@ static uint32_t G0(const CudaStreamsFFI &s) { return s.gpu_indexes ? s.gpu_index
 // uploads act on the thread's CURRENT device, which a host alternating between GPUs may have left elsewhere
 static void first_gpu(const CudaStreamsFFI &s) { HX_CHECK(hipSetDevice((int)G0(s))); }
 
+// ------------------------------------------------------------------ scratch protocol
+// Every object handed out through `int8_t **mem_ptr` starts with this header; a struct M of the layer derives from it,
+// names its kMagic, fills itself in a callable given to scratch_create and frees what it declares in
+// release(const CudaStreamsFFI &).  Only the header of the object that was handed out is stamped and checked: a
+// scratch that is a member of another one keeps its release() and nothing else of the protocol.
+struct ScratchHeader {
+  uint32_t magic = 0;      // M::kMagic while the object is alive (offset 0: scratch_magic tells BoolMulMem from MulMem)
+  bool size_only = false;  // created with allocate_gpu_memory = false: sized, nothing allocated
+};
+static uint32_t scratch_magic(const int8_t *mem_ptr) {
+  return mem_ptr ? reinterpret_cast<const ScratchHeader *>(mem_ptr)->magic : 0;
+}
+
+// create: the only place that sets the thread's dry-run state; `fill` allocates through radix_alloc / dev_upload.
+// Known and kept, a fix changes returned values: a size query counts the index uploads, a real creation does not
+// (dev_upload), so the two modes return different numbers; the reference returns one size_tracker in both.
+template <class M, class Fill>
+static uint64_t scratch_create(const CudaStreamsFFI &s, int8_t **mem_ptr, bool allocate_gpu_memory, const char *who,
+                               Fill &&fill) {
+  first_gpu(s);
+  HX_PANIC_IF_FALSE(mem_ptr != nullptr, "%s: null pointer", who);
+  t_dry = !allocate_gpu_memory;
+  t_bytes = 0;
+  M *m = new M();
+  m->magic = M::kMagic;
+  fill(*m);
+  m->size_only = t_dry;
+  t_dry = false;
+  *mem_ptr = reinterpret_cast<int8_t *>(static_cast<ScratchHeader *>(m));
+  return t_bytes;
+}
+template <class M>
+static M *scratch_cast(int8_t *mem_ptr, const char *who) {
+  auto *h = reinterpret_cast<ScratchHeader *>(mem_ptr);
+  HX_PANIC_IF_FALSE(h && h->magic == M::kMagic, "%s: foreign scratch pointer", who);
+  return static_cast<M *>(h);
+}
+// use: the scratch a launch was handed, refused if it is of another kind or was only sized
+template <class M>
+static M *scratch_use(int8_t *mem_ptr, const char *who) {
+  M *m = scratch_cast<M>(mem_ptr, who);
+  HX_PANIC_IF_FALSE(!m->size_only, "%s: scratch was created with allocate_gpu_memory=false", who);
+  return m;
+}
+// destroy (`who` = "cleanup <operation>"): the first stream is idle before anything is freed
+template <class M>
+static void scratch_destroy(const CudaStreamsFFI &s, int8_t **mem_ptr, const char *who) {
+  first_gpu(s);
+  M *m = scratch_cast<M>(*mem_ptr, who);
+  HX_CHECK(hipStreamSynchronize(S0(s)));
+  m->release(s);
+  m->magic = 0;
+  delete m;
+  *mem_ptr = nullptr;
+}
+
 // ------------------------------------------------------------------ apply a univariate LUT
-struct ApplyLutMem {
+struct ApplyLutMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x4C555431;  // "LUT1"
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;
   uint64_t *d_lut_idx = nullptr;  // all zero
   uint64_t degree = 0;
   uint32_t num_many_lut = 1;      // apply_many_univariate_lut: functions packed in the accumulator
+  void release(const CudaStreamsFFI &s) {
+    drv.release(s);
+    if (d_lut_idx) scratch_free(d_lut_idx);
+  }
 };
 
 // ------------------------------------------------------------------ carry propagation
@@ -531,11 +587,9 @@ enum : uint64_t {
   LUT_PROP_COUNT = 26
 };
 
-struct PropagateMem {
+struct PropagateMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x50524F50;  // "PROP"
   static constexpr uint32_t G = 3, TOP = 4;       // children per group; elements the top level resolves directly
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;
   uint32_t blocks = 0;   // blocks per integer
   uint32_t max_cts = 0;  // integers the scratch was sized for
@@ -874,19 +928,17 @@ struct PropagateMem {
     drv.release(ss);
     for (auto *d : dev_arrays) scratch_free(d);
     dev_arrays.clear();
+    cached_cts = 0;  // no index arrays are left
     for (uint64_t *d : {d_pool, d_p, d_pack})
       if (d) scratch_free(d);
-    magic = 0;
   }
 };
 
 // ------------------------------------------------------------------ multiplication
 // radix_parallel/mul.rs: block products (low / high halves through bivariate LUTs), column sums in
 // groups that fit the carry space, final carry propagation.
-struct MulMem {
+struct MulMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x4D554C31;  // "MUL1"
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;       // LUTs: 0 product low, 1 product high, 2 message, 3 carry
   PropagateMem prop;
   uint32_t blocks = 0, max_cts = 0, sub = 0;  // sub = integers per pass
@@ -1165,20 +1217,16 @@ struct MulMem {
     free_pass();
     drv.release(ss);
     prop.release(ss);
-    if (d_pool) scratch_free(d_pool);
-    if (d_pack) scratch_free(d_pack);
-    if (d_sum) scratch_free(d_sum);
-    magic = 0;
+    for (uint64_t *d : {d_pool, d_pack, d_sum})
+      if (d) scratch_free(d);
   }
 };
 
 // Multiplication by an encrypted boolean (integer.h:173-177 is_boolean_left / is_boolean_right; multiplication.h:28-49,
 // cmux.cuh:13-46 zero_out_if): every block of the integer packed with the boolean's single block, one bivariate
 // table (condition == 0 ? 0 : block): one KS -> PBS round of `blocks` bootstraps per integer.
-struct BoolMulMem {
+struct BoolMulMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x424D554C;  // "BMUL"
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;
   uint32_t blocks = 0, max_cts = 0;
   uint64_t *d_pack = nullptr, *d_cond_idx = nullptr, *d_lut_idx = nullptr;
@@ -1192,7 +1240,7 @@ struct BoolMulMem {
     const uint32_t T = cts * num_blocks;
     drv.init(ss, p, std::min<uint32_t>(T, 1u << 16), luts);
     radix_alloc((void **)&d_pack, (size_t)T * (p.big_n + 1) * sizeof(uint64_t));
-    if (!t_dry) {
+    if (!t_dry) {  // (so a size query leaves these two uploads out, unlike every other scratch)
       std::vector<uint64_t> ci(T), li(T, 0);
       for (uint32_t i = 0; i < T; ++i) ci[i] = i / num_blocks;  // the boolean of integer c is block c of its operand
       d_cond_idx = dev_upload(S0(ss), ci);
@@ -1214,20 +1262,22 @@ struct BoolMulMem {
     drv.release(ss);
     for (uint64_t *d : {d_pack, d_cond_idx, d_lut_idx})
       if (d) scratch_free(d);
-    magic = 0;
   }
 };
 
 // ------------------------------------------------------------------ bitwise operations, subtraction, full propagation
 // bitwise_ops.h:101-178 (int_bitop_buffer): one bivariate table of (lhs, rhs) packed msg * lhs + rhs for the ciphertext
 // forms, one univariate table per clear block value for the scalar forms (the clear blocks are the LUT indexes)
-struct BitopMem {
+struct BitopMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x42495431;  // "BIT1"
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;
   uint32_t op = 0;
   uint64_t *d_pack = nullptr, *d_lut_idx = nullptr;  // packed operands; all-zero LUT indexes (ciphertext forms)
+  void release(const CudaStreamsFFI &s) {
+    drv.release(s);
+    for (uint64_t *d : {d_pack, d_lut_idx})
+      if (d) scratch_free(d);
+  }
 };
 static uint64_t bitop_apply(uint32_t op, uint64_t a, uint64_t b) {
   switch (op % 3) {
@@ -1246,21 +1296,27 @@ static uint64_t bitop_degree(uint32_t op, uint64_t a, uint64_t b) {
 }
 
 // subtraction.cuh:31-47: the negation of rhs with its correcting term, then the addition's carry propagation
-struct SubMem {
+struct SubMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x53554231;  // "SUB1"
-  uint32_t magic = kMagic;
   PropagateMem prop;
   uint64_t *d_neg = nullptr;
+  void release(const CudaStreamsFFI &s) {
+    prop.release(s);
+    if (d_neg) scratch_free(d_neg);
+  }
 };
 
 // integer.cuh:1924-1983 (host_full_propagate_inplace): block after block, message and carry of the block by one
 // two-input bootstrap round, the carry added to the next block
-struct FullPropMem {
+struct FullPropMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x46505031;  // "FPP1"
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;  // LUTs: 0 message, 1 carry
   uint64_t *d_two = nullptr, *d_lut_idx = nullptr;  // the block twice -> (message, carry); indexes {0, 1}
+  void release(const CudaStreamsFFI &s) {
+    drv.release(s);
+    for (uint64_t *d : {d_two, d_lut_idx})
+      if (d) scratch_free(d);
+  }
 };
 
 // comparison.cuh / integer.h:246-276, unsigned operands.  Orderings ride on the subtraction's carry tree:
@@ -1269,10 +1325,7 @@ struct FullPropMem {
 // subtraction, 5 rounds), LE swaps the operands, LT / GT are 1 - that (levelled).  The reference reduces block orderings
 // pairwise (63 bootstraps in 6 rounds for 32 blocks: comparison.cuh).  Equality: one bivariate round, then sums of up to
 // (msg * carry - 1) / (msg - 1) = 5 block results against their count, level by level (32 + 7 + 2 + 1 bootstraps in 4 rounds).
-struct CompareMem {
-  static constexpr uint32_t kMagic = 0x434D5031;  // "CMP1"
-  uint32_t magic = kMagic;
-  bool size_only = false;
+struct CompareMem {  // only ever a member of CompareScratch: no header
   uint32_t op = 0, blocks = 0;
   PropagateMem prop;  // orderings
   LutDriver eq;       // equality: LUT 0 a == b, 1 a != b (packed pairs); 2 + (c - 1): sum == c; 2 + G + (c - 1): sum != c
@@ -1288,6 +1341,7 @@ struct CompareMem {
   uint32_t last_slot = 0;
 
   bool ordering() const { return op >= GT && op <= LE; }
+  const Params &params() const { return ordering() ? prop.drv.p : eq.p; }
 
   void init(const CudaStreamsFFI &ss, const Params &p, uint32_t L, uint32_t operation) {
     op = operation;
@@ -1361,7 +1415,7 @@ struct CompareMem {
     if (ordering()) {
       const Params &p = prop.drv.p;
       const uint32_t w = p.big_n + 1;
-      const uint64_t delta = ((uint64_t)1 << 63) / ((uint64_t)p.msg * p.carry);
+      const uint64_t delta = p.delta();
       const bool swap = op == LE || op == GT;       // LE(a, b) = GE(b, a); GT(a, b) = LT(b, a)
       const bool invert = op == LT || op == GT;     // LT = 1 - GE
       const uint64_t *x = swap ? b : a, *y = swap ? a : b;
@@ -1392,17 +1446,14 @@ struct CompareMem {
     dev_arrays.clear();
     for (uint64_t *d : {d_tmp, d_neg, d_bool, d_pack, d_pool, d_sum})
       if (d) scratch_free(d);
-    magic = 0;
   }
 };
 
 // cmux.cuh / integer.h:349-365: out <- condition ? true : false.  Both branches packed with the condition's single block
 // (block + msg * condition), one round over the 2 L packed blocks keeps a branch's block or zeroes it, the halves are added
 // and a message-extraction round returns the sum to nominal noise (the reference's int_cmux_buffer does the same three steps)
-struct CmuxMem {
+struct CmuxMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x434D5831;  // "CMX1"
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;  // LUTs: 0 keep if the condition is 1, 1 keep if it is 0, 2 message
   uint32_t blocks = 0;
   uint64_t *d_pack = nullptr, *d_zero_idx = nullptr, *d_lut_idx = nullptr, *d_lut2 = nullptr;
@@ -1438,19 +1489,21 @@ struct CmuxMem {
     drv.release(ss);
     for (uint64_t *d : {d_pack, d_zero_idx, d_lut_idx, d_lut2})
       if (d) scratch_free(d);
-    magic = 0;
   }
 };
 
 // scalar_shifts.cuh / integer.h:200-228: logical shift of an unsigned integer by a clear amount = a move by whole blocks
 // and, when bits remain, ONE bivariate round over (block, its lower / upper neighbour)
-struct ScalarShiftMem {
+struct ScalarShiftMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x53484631;  // "SHF1"
-  uint32_t magic = kMagic;
-  bool size_only = false;
   LutDriver drv;  // LUT r - 1: the shift by r bits inside a block (r = 1 .. bits per block - 1), this scratch's direction
   uint32_t blocks = 0, bits = 0, left = 0;
   uint64_t *d_pack = nullptr, *d_lut_idx = nullptr;  // packed pairs / block copy; one constant index array per r
+  void release(const CudaStreamsFFI &s) {
+    drv.release(s);
+    for (uint64_t *d : {d_pack, d_lut_idx})
+      if (d) scratch_free(d);
+  }
 };
 
 static uint32_t batch_of(const CudaRadixCiphertextFFI *ct, uint32_t blocks, const char *what) {
@@ -1458,6 +1511,31 @@ static uint32_t batch_of(const CudaRadixCiphertextFFI *ct, uint32_t blocks, cons
   HX_PANIC_IF_FALSE(blocks != 0 && ct->num_radix_blocks % blocks == 0,
                     "%s: %u blocks is not a whole number of %u-block integers", what, ct->num_radix_blocks, blocks);
   return ct->num_radix_blocks / blocks;
+}
+
+// ------------------------------------------------------------------ bookkeeping the entry points share
+// degree and noise level of blocks [first, first + count) after a launch; a caller that tracks neither passes no arrays
+static void set_block_info(CudaRadixCiphertextFFI *ct, uint32_t first, uint32_t count, uint64_t degree, uint64_t noise) {
+  for (uint32_t i = first; i < first + count; ++i) {
+    if (ct->degrees) ct->degrees[i] = degree;
+    if (ct->noise_levels) ct->noise_levels[i] = noise;
+  }
+}
+// an optional carry operand that a flag of the call makes mandatory: one block per integer, same LWE dimension
+static uint64_t *carry_blocks(const CudaRadixCiphertextFFI *carry, uint32_t cts, const CudaRadixCiphertextFFI *like,
+                              const char *complaint) {
+  HX_PANIC_IF_FALSE(carry && carry->ptr && carry->num_radix_blocks >= cts && carry->lwe_dimension == like->lwe_dimension,
+                    "%s", complaint);
+  return (uint64_t *)carry->ptr;
+}
+// the operations that pack two blocks into one take clean operands: the first n blocks have degree <= msg - 1
+static void check_clean(std::initializer_list<const CudaRadixCiphertextFFI *> operands, uint32_t n, uint32_t msg,
+                        const char *who, const char *tail) {
+  for (const CudaRadixCiphertextFFI *op : operands)
+    if (op->degrees)
+      for (uint32_t i = 0; i < n; ++i)
+        HX_PANIC_IF_FALSE(op->degrees[i] <= msg - 1, "%s: block %u has degree %llu, %s", who, i,
+                          (unsigned long long)op->degrees[i], tail);
 }
 
 }  // namespace radix
@@ -1475,22 +1553,17 @@ static uint64_t scratch_apply_lut(CudaStreamsFFI streams, int8_t **mem_ptr, void
                                   uint64_t lut_degree, bool allocate_gpu_memory, uint32_t noise_reduction_type) {
   HX_PANIC_IF_FALSE(input_lut != nullptr && mem_ptr != nullptr, "apply_univariate_lut: null pointer");
   HX_PANIC_IF_FALSE(num_many_lut >= 1, "apply_many_univariate_lut: num_many_lut must be at least 1");
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
   const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, noise_reduction_type);
-  auto *m = new ApplyLutMem();
-  const size_t lw = (size_t)(p.k + 1) * p.N;
-  std::vector<std::vector<uint64_t>> luts(1);
-  luts[0].assign((const uint64_t *)input_lut, (const uint64_t *)input_lut + lw);
-  m->drv.init(streams, p, std::max<uint32_t>(1, count), luts);
-  m->degree = lut_degree;
-  m->num_many_lut = num_many_lut;
-  radix_alloc((void **)&m->d_lut_idx, std::max<uint32_t>(1, count) * sizeof(uint64_t));
-  if (!t_dry) HX_CHECK(hipMemsetAsync(m->d_lut_idx, 0, std::max<uint32_t>(1, count) * sizeof(uint64_t), S0(streams)));
-  m->size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  return scratch_create<ApplyLutMem>(streams, mem_ptr, allocate_gpu_memory, "apply_univariate_lut", [&](ApplyLutMem &m) {
+    const size_t lw = (size_t)(p.k + 1) * p.N, idx_bytes = std::max<uint32_t>(1, count) * sizeof(uint64_t);
+    std::vector<std::vector<uint64_t>> luts(1);
+    luts[0].assign((const uint64_t *)input_lut, (const uint64_t *)input_lut + lw);
+    m.drv.init(streams, p, std::max<uint32_t>(1, count), luts);
+    m.degree = lut_degree;
+    m.num_many_lut = num_many_lut;
+    radix_alloc((void **)&m.d_lut_idx, idx_bytes);
+    if (!t_dry) HX_CHECK(hipMemsetAsync(m.d_lut_idx, 0, idx_bytes, S0(streams)));
+  });
 }
 
 uint64_t scratch_cuda_apply_univariate_lut_64_async(CudaStreamsFFI streams, int8_t **mem_ptr, void const *input_lut,
@@ -1500,7 +1573,6 @@ uint64_t scratch_cuda_apply_univariate_lut_64_async(CudaStreamsFFI streams, int8
                                                     uint32_t carry_modulus, uint64_t lut_degree,
                                                     bool allocate_gpu_memory,
                                                     enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
   return scratch_apply_lut(streams, mem_ptr, input_lut, bsk_params, ksk_params, input_lwe_ciphertext_count,
                            message_modulus, carry_modulus, 1, lut_degree, allocate_gpu_memory,
                            (uint32_t)noise_reduction_type);
@@ -1515,7 +1587,6 @@ uint64_t scratch_cuda_apply_many_univariate_lut_64_async(CudaStreamsFFI streams,
                                                          uint32_t carry_modulus, uint32_t num_many_lut,
                                                          uint64_t lut_degree, bool allocate_gpu_memory,
                                                          enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
   return scratch_apply_lut(streams, mem_ptr, input_lut, bsk_params, ksk_params, num_radix_blocks, message_modulus,
                            carry_modulus, num_many_lut, lut_degree, allocate_gpu_memory, (uint32_t)noise_reduction_type);
 }
@@ -1524,9 +1595,7 @@ void cuda_apply_univariate_lut_64_async(CudaStreamsFFI streams, CudaRadixCiphert
                                         CudaRadixCiphertextFFI const *input_radix_lwe, int8_t *mem_ptr,
                                         void *const *ksks, void *const *bsks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<ApplyLutMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == ApplyLutMem::kMagic, "apply_univariate_lut: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "apply_univariate_lut: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<ApplyLutMem>(mem_ptr, "apply_univariate_lut");
   HX_PANIC_IF_FALSE(output_radix_lwe && input_radix_lwe && ksks && bsks, "apply_univariate_lut: null pointer");
   HX_PANIC_IF_FALSE(output_radix_lwe->lwe_dimension == input_radix_lwe->lwe_dimension,
                     "input and output radix ciphertexts should have the same lwe dimension");
@@ -1536,21 +1605,11 @@ void cuda_apply_univariate_lut_64_async(CudaStreamsFFI streams, CudaRadixCiphert
                     "blocks");
   m->drv.round(streams, (uint64_t *)output_radix_lwe->ptr, nullptr, (const uint64_t *)input_radix_lwe->ptr, nullptr,
                m->d_lut_idx, n, ksks, bsks);
-  if (output_radix_lwe->degrees)
-    for (uint32_t i = 0; i < n; ++i) output_radix_lwe->degrees[i] = m->degree;
-  if (output_radix_lwe->noise_levels)
-    for (uint32_t i = 0; i < n; ++i) output_radix_lwe->noise_levels[i] = 1;
+  set_block_info(output_radix_lwe, 0, n, m->degree, 1);
 }
 
 void cleanup_cuda_apply_univariate_lut_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<ApplyLutMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == ApplyLutMem::kMagic, "cleanup apply_univariate_lut: foreign scratch pointer");
-  m->drv.release(streams);
-  if (m->d_lut_idx) scratch_free(m->d_lut_idx);
-  m->magic = 0;
-  delete m;
-  *mem_ptr_void = nullptr;
+  scratch_destroy<ApplyLutMem>(streams, mem_ptr_void, "cleanup apply_univariate_lut");
 }
 
 // integer.cuh:1002-1110: the output holds num_many_lut * n blocks, function t of input block s in block t * n + s
@@ -1559,9 +1618,7 @@ void cuda_apply_many_univariate_lut_64_async(CudaStreamsFFI streams, CudaRadixCi
                                              void *const *ksks, void *const *bsks, uint32_t num_luts,
                                              uint32_t lut_stride) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<ApplyLutMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == ApplyLutMem::kMagic, "apply_many_univariate_lut: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "apply_many_univariate_lut: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<ApplyLutMem>(mem_ptr, "apply_many_univariate_lut");
   HX_PANIC_IF_FALSE(output_radix_lwe && input_radix_lwe && ksks && bsks, "apply_many_univariate_lut: null pointer");
   HX_PANIC_IF_FALSE(num_luts >= 1 && num_luts <= m->num_many_lut,
                     "apply_many_univariate_lut: more functions than the scratch was created for");
@@ -1574,15 +1631,10 @@ void cuda_apply_many_univariate_lut_64_async(CudaStreamsFFI streams, CudaRadixCi
                     "apply_many_univariate_lut: lut_stride * (num_luts - 1) reaches past the polynomial");
   m->drv.round_many(streams, (uint64_t *)output_radix_lwe->ptr, (const uint64_t *)input_radix_lwe->ptr, m->d_lut_idx, n,
                     ksks, bsks, num_luts, lut_stride);
-  const uint32_t total = n * num_luts;
-  if (output_radix_lwe->degrees)
-    for (uint32_t i = 0; i < total; ++i) output_radix_lwe->degrees[i] = m->degree;
-  if (output_radix_lwe->noise_levels)
-    for (uint32_t i = 0; i < total; ++i) output_radix_lwe->noise_levels[i] = 1;
+  set_block_info(output_radix_lwe, 0, n * num_luts, m->degree, 1);
 }
 
 void cleanup_cuda_apply_many_univariate_lut_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
   cleanup_cuda_apply_univariate_lut_64(streams, mem_ptr_void);
 }
 
@@ -1607,8 +1659,7 @@ void cuda_add_lwe_ciphertext_vector_inplace_64(void *stream, uint32_t gpu_index,
 // The carry tree's first bootstrap holds two functions in its accumulator, so a block's value must stay below
 // msg * carry / 2: at most 2 msg - 2 (two clean blocks added), one more for block 0 of an integer when an input carry
 // is added to it.  A caller that tracks degrees gets the call refused instead of an incorrect result.
-static void check_propagation_degrees(const CudaRadixCiphertextFFI *ct, uint32_t msg, bool /*with_carry_in*/,
-                                      uint32_t /*blocks_per_integer*/, const char *who) {
+static void check_propagation_degrees(const CudaRadixCiphertextFFI *ct, uint32_t msg, const char *who) {
   if (ct == nullptr || ct->degrees == nullptr) return;
   for (uint32_t i = 0; i < ct->num_radix_blocks; ++i) {
     const uint64_t limit = 2ull * msg - 2;  // (the input carry itself comes on top of block 0: 2 msg - 1 there is fine)
@@ -1623,6 +1674,7 @@ static void check_propagation_degrees(const CudaRadixCiphertextFFI *ct, uint32_t
 // of integers up to the capacity given through hip_integer_scratch_batch (default 1).
 // read by the NEXT scratch_* call of the same host thread (the radix scratch entry points have no batch parameter in
 // the reference's prototypes): thread-local, so that concurrent host threads size their own scratches
+// (comparison and cmux ignore it: one integer per call)
 static thread_local uint32_t g_scratch_batch = 1;
 void hip_integer_scratch_batch(uint32_t num_integers) { g_scratch_batch = num_integers ? num_integers : 1; }
 // blocks per GPU from which a KS -> PBS round spreads over one more GPU of the stream set; 0 restores the default, the
@@ -1645,17 +1697,10 @@ uint64_t scratch_cuda_propagate_single_carry_64_inplace_async(CudaStreamsFFI str
                                                               uint32_t carry_modulus, uint32_t requested_flag,
                                                               bool allocate_gpu_memory,
                                                               enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
   HX_PANIC_IF_FALSE(requested_flag <= 2, "propagate_single_carry: unknown output flag %u", requested_flag);
   const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  auto *m = new PropagateMem();
-  m->init(streams, p, num_blocks, g_scratch_batch);
-  m->size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  return scratch_create<PropagateMem>(streams, mem_ptr, allocate_gpu_memory, "propagate_single_carry",
+                                      [&](PropagateMem &m) { m.init(streams, p, num_blocks, g_scratch_batch); });
 }
 uint64_t scratch_cuda_add_and_propagate_single_carry_64_inplace_async(
     CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
@@ -1672,42 +1717,25 @@ void cuda_propagate_single_carry_64_inplace_async(CudaStreamsFFI streams, CudaRa
                                                   void *const *bsks, void *const *ksks, uint32_t requested_flag,
                                                   uint32_t uses_carry) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<PropagateMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == PropagateMem::kMagic, "propagate_single_carry: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "propagate_single_carry: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<PropagateMem>(mem_ptr, "propagate_single_carry");
   // integer.cuh:2368-2370: the overflow flag needs the operands of the addition
   HX_PANIC_IF_FALSE(requested_flag != 1, "single carry propagation is not supported for overflow, try using "
                                          "add_and_propagate_single_carry");
   HX_PANIC_IF_FALSE(requested_flag == 0 || requested_flag == 2, "propagate_single_carry: unknown output flag %u",
                     requested_flag);
   const uint32_t cts = batch_of(lwe_array, m->blocks, "propagate_single_carry");
-  check_propagation_degrees(lwe_array, m->drv.p.msg, uses_carry != 0, m->blocks, "propagate_single_carry");
+  check_propagation_degrees(lwe_array, m->drv.p.msg, "propagate_single_carry");
   // the reference's Rust caller always hands over carry_in / carry_out structs (integer/gpu/ffi.rs:2213-2237);
   // they are read / written only when uses_carry / requested_flag say so
   const uint64_t *cin = nullptr;
   uint64_t *cout = nullptr;
-  if (uses_carry != 0) {
-    HX_PANIC_IF_FALSE(carry_in && carry_in->ptr && carry_in->num_radix_blocks >= cts &&
-                          carry_in->lwe_dimension == lwe_array->lwe_dimension,
-                      "propagate_single_carry: uses_carry needs one input carry block per integer");
-    cin = (const uint64_t *)carry_in->ptr;
-  }
-  if (requested_flag == 2) {
-    HX_PANIC_IF_FALSE(carry_out && carry_out->ptr && carry_out->num_radix_blocks >= cts &&
-                          carry_out->lwe_dimension == lwe_array->lwe_dimension,
-                      "propagate_single_carry: FLAG_CARRY needs one output carry block per integer");
-    cout = (uint64_t *)carry_out->ptr;
-  }
+  if (uses_carry != 0)
+    cin = carry_blocks(carry_in, cts, lwe_array, "propagate_single_carry: uses_carry needs one input carry block per integer");
+  if (requested_flag == 2)
+    cout = carry_blocks(carry_out, cts, lwe_array, "propagate_single_carry: FLAG_CARRY needs one output carry block per integer");
   m->run(streams, (uint64_t *)lwe_array->ptr, cts, ksks, bsks, cin, cout);
-  if (cout)
-    for (uint32_t i = 0; i < cts; ++i) {
-      if (carry_out->degrees) carry_out->degrees[i] = 1;
-      if (carry_out->noise_levels) carry_out->noise_levels[i] = 1;
-    }
-  for (uint32_t i = 0; i < lwe_array->num_radix_blocks; ++i) {
-    if (lwe_array->degrees) lwe_array->degrees[i] = m->drv.p.msg - 1;
-    if (lwe_array->noise_levels) lwe_array->noise_levels[i] = 1;
-  }
+  if (cout) set_block_info(carry_out, 0, cts, 1, 1);
+  set_block_info(lwe_array, 0, lwe_array->num_radix_blocks, m->drv.p.msg - 1, 1);
 }
 
 void cuda_add_and_propagate_single_carry_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lhs_array,
@@ -1727,16 +1755,13 @@ void cuda_add_and_propagate_single_carry_64_inplace_async(CudaStreamsFFI streams
   // lhs + rhs (+ carry_in) — the carry into the sign bit against the carry out of the last block.  The operands' last
   // blocks are read before the addition; both operands are clean (degrees <= msg - 1: the preparation is a bivariate
   // table of the two last blocks).
-  auto *m = reinterpret_cast<PropagateMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == PropagateMem::kMagic, "add_and_propagate_single_carry: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "add_and_propagate_single_carry: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<PropagateMem>(mem_ptr, "add_and_propagate_single_carry");
   HX_PANIC_IF_FALSE(lhs_array && rhs_array && lhs_array->num_radix_blocks == rhs_array->num_radix_blocks &&
                         lhs_array->lwe_dimension == rhs_array->lwe_dimension,
                     "add_and_propagate_single_carry: operands must have the same shape");
   const uint32_t cts = batch_of(lhs_array, m->blocks, "add_and_propagate_single_carry");
-  HX_PANIC_IF_FALSE(carry_out && carry_out->ptr && carry_out->num_radix_blocks >= cts &&
-                        carry_out->lwe_dimension == lhs_array->lwe_dimension,
-                    "when requesting FLAG_CARRY or FLAG_OVERFLOW, carry_out must be a valid pointer (one block per integer)");
+  uint64_t *ovf = carry_blocks(carry_out, cts, lhs_array,
+                               "when requesting FLAG_CARRY or FLAG_OVERFLOW, carry_out must be a valid pointer (one block per integer)");
   const uint32_t msg = m->drv.p.msg;
   for (const CudaRadixCiphertextFFI *op : {(const CudaRadixCiphertextFFI *)lhs_array, rhs_array})
     if (op->degrees)
@@ -1745,36 +1770,20 @@ void cuda_add_and_propagate_single_carry_64_inplace_async(CudaStreamsFFI streams
                           "add_and_propagate_single_carry: FLAG_OVERFLOW needs clean last blocks (degree %llu > %u)",
                           (unsigned long long)op->degrees[(size_t)(c + 1) * m->blocks - 1], msg - 1);
   const uint64_t *cin = nullptr;
-  if (uses_carry != 0) {
-    HX_PANIC_IF_FALSE(carry_in && carry_in->ptr && carry_in->num_radix_blocks >= cts &&
-                          carry_in->lwe_dimension == lhs_array->lwe_dimension,
-                      "add_and_propagate_single_carry: uses_carry needs one input carry block per integer");
-    cin = (const uint64_t *)carry_in->ptr;
-  }
+  if (uses_carry != 0)
+    cin = carry_blocks(carry_in, cts, lhs_array, "add_and_propagate_single_carry: uses_carry needs one input carry block per integer");
   m->pack_last_blocks(streams, (const uint64_t *)lhs_array->ptr, (const uint64_t *)rhs_array->ptr, cts);
   cuda_add_lwe_ciphertext_vector_inplace_64(streams.streams[0], G0(streams), lhs_array, rhs_array);
-  check_propagation_degrees(lhs_array, msg, uses_carry != 0, m->blocks, "add_and_propagate_single_carry");
-  m->run(streams, (uint64_t *)lhs_array->ptr, cts, ksks, bsks, cin, nullptr, (uint64_t *)carry_out->ptr);
-  for (uint32_t i = 0; i < cts; ++i) {
-    if (carry_out->degrees) carry_out->degrees[i] = 1;
-    if (carry_out->noise_levels) carry_out->noise_levels[i] = 1;
-  }
-  for (uint32_t i = 0; i < lhs_array->num_radix_blocks; ++i) {
-    if (lhs_array->degrees) lhs_array->degrees[i] = msg - 1;
-    if (lhs_array->noise_levels) lhs_array->noise_levels[i] = 1;
-  }
+  check_propagation_degrees(lhs_array, msg, "add_and_propagate_single_carry");
+  m->run(streams, (uint64_t *)lhs_array->ptr, cts, ksks, bsks, cin, nullptr, ovf);
+  set_block_info(carry_out, 0, cts, 1, 1);
+  set_block_info(lhs_array, 0, lhs_array->num_radix_blocks, msg - 1, 1);
 }
 
 void cleanup_cuda_propagate_single_carry_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<PropagateMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == PropagateMem::kMagic, "cleanup propagate_single_carry: foreign scratch pointer");
-  m->release(streams);
-  delete m;
-  *mem_ptr_void = nullptr;
+  scratch_destroy<PropagateMem>(streams, mem_ptr_void, "cleanup propagate_single_carry");
 }
 void cleanup_cuda_add_and_propagate_single_carry_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
   cleanup_cuda_propagate_single_carry_64_inplace(streams, mem_ptr_void);
 }
 
@@ -1786,24 +1795,12 @@ uint64_t scratch_cuda_integer_mult_inplace_64_async(CudaStreamsFFI streams, int8
                                                     CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
                                                     bool allocate_gpu_memory,
                                                     enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
   const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  if (is_boolean_left || is_boolean_right) {  // one operand is an encrypted boolean: a select, not a product
-    auto *bm = new BoolMulMem();
-    bm->init(streams, p, num_blocks, g_scratch_batch);
-    bm->size_only = t_dry;
-    t_dry = false;
-    *mem_ptr = reinterpret_cast<int8_t *>(bm);
-    return t_bytes;
-  }
-  auto *m = new MulMem();
-  m->init(streams, p, num_blocks, g_scratch_batch);
-  m->size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  if (is_boolean_left || is_boolean_right)  // one operand is an encrypted boolean: a select, not a product
+    return scratch_create<BoolMulMem>(streams, mem_ptr, allocate_gpu_memory, "integer_mult",
+                                      [&](BoolMulMem &m) { m.init(streams, p, num_blocks, g_scratch_batch); });
+  return scratch_create<MulMem>(streams, mem_ptr, allocate_gpu_memory, "integer_mult",
+                                [&](MulMem &m) { m.init(streams, p, num_blocks, g_scratch_batch); });
 }
 
 void cuda_integer_mult_inplace_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *radix_lwe_inout,
@@ -1815,10 +1812,9 @@ void cuda_integer_mult_inplace_64_async(CudaStreamsFFI streams, CudaRadixCiphert
     // multiplication.cuh:508-520: the boolean operand is ONE block (here: one per integer of the batch, packed at the
     // start of its ciphertext); the other operand's blocks are kept or zeroed.  In place on radix_lwe_inout, which
     // holds the full-width integers either way (as the left operand, or as the destination when it is the boolean).
-    auto *bm = reinterpret_cast<BoolMulMem *>(mem_ptr);
-    HX_PANIC_IF_FALSE(bm && bm->magic == BoolMulMem::kMagic,
+    HX_PANIC_IF_FALSE(scratch_magic(mem_ptr) == BoolMulMem::kMagic,
                       "integer_mult: boolean operands need a scratch created with is_boolean_left / is_boolean_right");
-    HX_PANIC_IF_FALSE(!bm->size_only, "integer_mult: scratch was created with allocate_gpu_memory=false");
+    auto *bm = scratch_use<BoolMulMem>(mem_ptr, "integer_mult");
     HX_PANIC_IF_FALSE(polynomial_size == bm->drv.p.N && num_blocks == bm->blocks, "integer_mult: call does not match the scratch");
     HX_PANIC_IF_FALSE(radix_lwe_inout && radix_lwe_right && radix_lwe_inout->lwe_dimension == radix_lwe_right->lwe_dimension,
                       "integer_mult: input and output lwe dimensions should be the same");
@@ -1840,40 +1836,23 @@ void cuda_integer_mult_inplace_64_async(CudaStreamsFFI streams, CudaRadixCiphert
     // (a boolean that sits in the destination is read by the packing launch before the bootstrap overwrites it)
     bm->run(streams, (uint64_t *)radix_lwe_inout->ptr, (const uint64_t *)value->ptr, (const uint64_t *)cond->ptr, cts,
             ksks, bsks);
-    for (uint32_t i = 0; i < cts * bm->blocks; ++i) {
-      if (radix_lwe_inout->degrees) radix_lwe_inout->degrees[i] = bm->drv.p.msg - 1;
-      if (radix_lwe_inout->noise_levels) radix_lwe_inout->noise_levels[i] = 1;
-    }
+    set_block_info(radix_lwe_inout, 0, cts * bm->blocks, bm->drv.p.msg - 1, 1);
     return;
   }
-  auto *m = reinterpret_cast<MulMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == MulMem::kMagic, "integer_mult: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "integer_mult: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<MulMem>(mem_ptr, "integer_mult");
   HX_PANIC_IF_FALSE(polynomial_size == m->drv.p.N && num_blocks == m->blocks, "integer_mult: call does not match the scratch");
   const uint32_t cts = batch_of(radix_lwe_inout, m->blocks, "integer_mult");
   HX_PANIC_IF_FALSE(radix_lwe_right && radix_lwe_right->num_radix_blocks == radix_lwe_inout->num_radix_blocks,
                     "integer_mult: operands must have the same shape");
   m->run(streams, (uint64_t *)radix_lwe_inout->ptr, (const uint64_t *)radix_lwe_right->ptr, cts, ksks, bsks);
-  for (uint32_t i = 0; i < radix_lwe_inout->num_radix_blocks; ++i) {
-    if (radix_lwe_inout->degrees) radix_lwe_inout->degrees[i] = m->drv.p.msg - 1;
-    if (radix_lwe_inout->noise_levels) radix_lwe_inout->noise_levels[i] = 1;
-  }
+  set_block_info(radix_lwe_inout, 0, radix_lwe_inout->num_radix_blocks, m->drv.p.msg - 1, 1);
 }
 
 void cleanup_cuda_integer_mult_inplace_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  if (*mem_ptr_void && reinterpret_cast<BoolMulMem *>(*mem_ptr_void)->magic == BoolMulMem::kMagic) {
-    auto *bm = reinterpret_cast<BoolMulMem *>(*mem_ptr_void);
-    bm->release(streams);
-    delete bm;
-    *mem_ptr_void = nullptr;
-    return;
-  }
-  auto *m = reinterpret_cast<MulMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == MulMem::kMagic, "cleanup integer_mult: foreign scratch pointer");
-  m->release(streams);
-  delete m;
-  *mem_ptr_void = nullptr;
+  if (scratch_magic(*mem_ptr_void) == BoolMulMem::kMagic)
+    scratch_destroy<BoolMulMem>(streams, mem_ptr_void, "cleanup integer_mult");
+  else
+    scratch_destroy<MulMem>(streams, mem_ptr_void, "cleanup integer_mult");
 }
 
 // ---- cuda/include/integer/integer.h:189-198, :312-316 ------------------------------------------
@@ -1946,35 +1925,28 @@ static uint64_t scratch_bitop(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweB
                               CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t count, uint32_t message_modulus,
                               uint32_t carry_modulus, uint32_t op, bool scalar, bool allocate_gpu_memory,
                               uint32_t noise_reduction_type) {
-  first_gpu(streams);
-  HX_PANIC_IF_FALSE(mem_ptr != nullptr, "bitop: null pointer");
-  HX_PANIC_IF_FALSE(scalar ? (op >= SCALAR_BITAND && op <= SCALAR_BITXOR) : op <= BITXOR,
-                    "bitop: operation %u does not belong to this entry point", op);
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, noise_reduction_type);
-  auto *m = new BitopMem();
-  m->op = op;
-  const size_t lw = (size_t)(p.k + 1) * p.N;
-  const uint32_t cap = std::max<uint32_t>(1, count) * g_scratch_batch;
-  std::vector<std::vector<uint64_t>> luts(scalar ? p.msg : 1, std::vector<uint64_t>(lw));
-  if (scalar) {
-    for (uint32_t c = 0; c < p.msg; ++c)
-      generate_lut(p, luts[c].data(), [op, c](uint64_t x) { return bitop_apply(op, x, c); });
-  } else {
-    const uint32_t msg = p.msg;
-    generate_lut(p, luts[0].data(), [op, msg](uint64_t x) { return bitop_apply(op, x / msg, x % msg); });
-  }
-  m->drv.init(streams, p, cap, luts);
-  if (!scalar) {
-    radix_alloc((void **)&m->d_pack, (size_t)cap * (p.big_n + 1) * sizeof(uint64_t));
-    radix_alloc((void **)&m->d_lut_idx, (size_t)cap * sizeof(uint64_t));
-    if (!t_dry) HX_CHECK(hipMemsetAsync(m->d_lut_idx, 0, (size_t)cap * sizeof(uint64_t), S0(streams)));
-  }
-  m->size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  return scratch_create<BitopMem>(streams, mem_ptr, allocate_gpu_memory, "bitop", [&](BitopMem &m) {
+    HX_PANIC_IF_FALSE(scalar ? (op >= SCALAR_BITAND && op <= SCALAR_BITXOR) : op <= BITXOR,
+                      "bitop: operation %u does not belong to this entry point", op);
+    const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, noise_reduction_type);
+    m.op = op;
+    const size_t lw = (size_t)(p.k + 1) * p.N;
+    const uint32_t cap = std::max<uint32_t>(1, count) * g_scratch_batch;
+    std::vector<std::vector<uint64_t>> luts(scalar ? p.msg : 1, std::vector<uint64_t>(lw));
+    if (scalar) {
+      for (uint32_t c = 0; c < p.msg; ++c)
+        generate_lut(p, luts[c].data(), [op, c](uint64_t x) { return bitop_apply(op, x, c); });
+    } else {
+      const uint32_t msg = p.msg;
+      generate_lut(p, luts[0].data(), [op, msg](uint64_t x) { return bitop_apply(op, x / msg, x % msg); });
+    }
+    m.drv.init(streams, p, cap, luts);
+    if (!scalar) {
+      radix_alloc((void **)&m.d_pack, (size_t)cap * (p.big_n + 1) * sizeof(uint64_t));
+      radix_alloc((void **)&m.d_lut_idx, (size_t)cap * sizeof(uint64_t));
+      if (!t_dry) HX_CHECK(hipMemsetAsync(m.d_lut_idx, 0, (size_t)cap * sizeof(uint64_t), S0(streams)));
+    }
+  });
 }
 uint64_t scratch_cuda_integer_bitop_inplace_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
                                                      CudaLweBootstrapKeyParamsFFI bsk_params,
@@ -2002,9 +1974,8 @@ void cuda_integer_bitop_inplace_64_async(CudaStreamsFFI streams, CudaRadixCipher
                                          CudaRadixCiphertextFFI const *lwe_array_2, int8_t *mem_ptr,
                                          void *const *bsks, void *const *ksks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<BitopMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == BitopMem::kMagic && m->op <= BITXOR, "integer_bitop: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "integer_bitop: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<BitopMem>(mem_ptr, "integer_bitop");
+  HX_PANIC_IF_FALSE(m->op <= BITXOR, "integer_bitop: foreign scratch pointer");  // a scratch of the scalar form
   HX_PANIC_IF_FALSE(lwe_array_inout && lwe_array_2 && lwe_array_inout->ptr && lwe_array_2->ptr && bsks && ksks,
                     "integer_bitop: null pointer");
   HX_PANIC_IF_FALSE(lwe_array_inout->num_radix_blocks == lwe_array_2->num_radix_blocks,
@@ -2037,9 +2008,8 @@ void cuda_integer_scalar_bitop_inplace_64_async(CudaStreamsFFI streams, CudaRadi
                                                 uint32_t num_clear_blocks, int8_t *mem_ptr, void *const *bsks,
                                                 void *const *ksks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<BitopMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == BitopMem::kMagic && m->op >= SCALAR_BITAND, "integer_scalar_bitop: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "integer_scalar_bitop: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<BitopMem>(mem_ptr, "integer_scalar_bitop");
+  HX_PANIC_IF_FALSE(m->op >= SCALAR_BITAND, "integer_scalar_bitop: foreign scratch pointer");  // of the ciphertext form
   HX_PANIC_IF_FALSE(lwe_array_inout && lwe_array_inout->ptr && bsks && ksks, "integer_scalar_bitop: null pointer");
   const uint32_t nb = lwe_array_inout->num_radix_blocks;
   HX_PANIC_IF_FALSE(num_clear_blocks <= nb && num_clear_blocks <= m->drv.cap,
@@ -2063,29 +2033,15 @@ void cuda_integer_scalar_bitop_inplace_64_async(CudaStreamsFFI streams, CudaRadi
   if (m->op == SCALAR_BITAND && num_clear_blocks < nb) {
     HX_CHECK(hipMemsetAsync(v + (size_t)num_clear_blocks * w, 0, (size_t)(nb - num_clear_blocks) * w * sizeof(uint64_t),
                             S0(streams)));
-    for (uint32_t i = num_clear_blocks; i < nb; ++i) {
-      if (lwe_array_inout->degrees) lwe_array_inout->degrees[i] = 0;
-      if (lwe_array_inout->noise_levels) lwe_array_inout->noise_levels[i] = 0;
-    }
+    set_block_info(lwe_array_inout, num_clear_blocks, nb - num_clear_blocks, 0, 0);
   }
 }
 
-static void cleanup_bitop(CudaStreamsFFI streams, int8_t **mem_ptr_void, const char *who) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<BitopMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == BitopMem::kMagic, "%s: foreign scratch pointer", who);
-  m->drv.release(streams);
-  for (uint64_t *d : {m->d_pack, m->d_lut_idx})
-    if (d) scratch_free(d);
-  m->magic = 0;
-  delete m;
-  *mem_ptr_void = nullptr;
-}
 void cleanup_cuda_integer_bitop_inplace_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  cleanup_bitop(streams, mem_ptr_void, "cleanup integer_bitop");
+  scratch_destroy<BitopMem>(streams, mem_ptr_void, "cleanup integer_bitop");
 }
 void cleanup_cuda_integer_scalar_bitop_inplace_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  cleanup_bitop(streams, mem_ptr_void, "cleanup integer_scalar_bitop");
+  scratch_destroy<BitopMem>(streams, mem_ptr_void, "cleanup integer_scalar_bitop");
 }
 
 // ---- cuda/include/integer/integer.h:559-573 -----------------------------------------------------
@@ -2097,20 +2053,13 @@ uint64_t scratch_cuda_sub_and_propagate_single_carry_64_inplace_async(
     CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
     CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks, uint32_t message_modulus, uint32_t carry_modulus,
     uint32_t requested_flag, bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
-  HX_PANIC_IF_FALSE(mem_ptr != nullptr, "sub_and_propagate_single_carry: null pointer");
-  HX_PANIC_IF_FALSE(requested_flag == 0 || requested_flag == 2,
-                    "sub_and_propagate_single_carry: output flag %u is not wired (0 = none, 2 = carry)", requested_flag);
-  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  auto *m = new SubMem();
-  m->prop.init(streams, p, num_blocks, g_scratch_batch);
-  radix_alloc((void **)&m->d_neg, (size_t)num_blocks * g_scratch_batch * (p.big_n + 1) * sizeof(uint64_t));
-  m->prop.size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  return scratch_create<SubMem>(streams, mem_ptr, allocate_gpu_memory, "sub_and_propagate_single_carry", [&](SubMem &m) {
+    HX_PANIC_IF_FALSE(requested_flag == 0 || requested_flag == 2,
+                      "sub_and_propagate_single_carry: output flag %u is not wired (0 = none, 2 = carry)", requested_flag);
+    const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+    m.prop.init(streams, p, num_blocks, g_scratch_batch);
+    radix_alloc((void **)&m.d_neg, (size_t)num_blocks * g_scratch_batch * (p.big_n + 1) * sizeof(uint64_t));
+  });
 }
 
 void cuda_sub_and_propagate_single_carry_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lhs_array,
@@ -2121,9 +2070,7 @@ void cuda_sub_and_propagate_single_carry_64_inplace_async(CudaStreamsFFI streams
                                                           uint32_t requested_flag, uint32_t uses_carry) {
   first_gpu(streams);
   (void)carry_in;
-  auto *m = reinterpret_cast<SubMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == SubMem::kMagic, "sub_and_propagate_single_carry: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->prop.size_only, "sub_and_propagate_single_carry: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<SubMem>(mem_ptr, "sub_and_propagate_single_carry");
   HX_PANIC_IF_FALSE(requested_flag == 0 || requested_flag == 2,
                     "sub_and_propagate_single_carry: output flag %u is not wired (0 = none, 2 = carry)", requested_flag);
   HX_PANIC_IF_FALSE(uses_carry == 0, "sub_and_propagate_single_carry: an input carry is not wired (block 0 already holds the "
@@ -2134,47 +2081,24 @@ void cuda_sub_and_propagate_single_carry_64_inplace_async(CudaStreamsFFI streams
                     "sub_and_propagate_single_carry: operands must have the same shape");
   const uint32_t L = m->prop.blocks, cts = batch_of(lhs_array, L, "sub_and_propagate_single_carry");
   const Params &p = m->prop.drv.p;
-  for (const CudaRadixCiphertextFFI *op : {(const CudaRadixCiphertextFFI *)lhs_array, rhs_array})
-    if (op->degrees)
-      for (uint32_t i = 0; i < op->num_radix_blocks; ++i)
-        HX_PANIC_IF_FALSE(op->degrees[i] <= p.msg - 1,
-                          "sub_and_propagate_single_carry: block %u has degree %llu, the subtraction takes clean operands "
-                          "(propagate them first)", i, (unsigned long long)op->degrees[i]);
+  check_clean({lhs_array, rhs_array}, lhs_array->num_radix_blocks, p.msg, "sub_and_propagate_single_carry",
+              "the subtraction takes clean operands (propagate them first)");
   uint64_t *cout = nullptr;
-  if (requested_flag == 2) {
-    HX_PANIC_IF_FALSE(carry_out && carry_out->ptr && carry_out->num_radix_blocks >= cts &&
-                          carry_out->lwe_dimension == lhs_array->lwe_dimension,
-                      "sub_and_propagate_single_carry: FLAG_CARRY needs one output carry block per integer");
-    cout = (uint64_t *)carry_out->ptr;
-  }
+  if (requested_flag == 2)
+    cout = carry_blocks(carry_out, cts, lhs_array, "sub_and_propagate_single_carry: FLAG_CARRY needs one output carry block per integer");
   const hipStream_t st = S0(streams);
   const uint32_t w = p.big_n + 1, T = cts * L;
-  const uint64_t delta = ((uint64_t)1 << 63) / ((uint64_t)p.msg * p.carry);
   HX_LAUNCH(lwe_negate_const_kernel, dim3(T), dim3(256), 0, st, m->d_neg, (const uint64_t *)rhs_array->ptr, w, T, L,
-            (uint64_t)p.msg * delta, (uint64_t)(p.msg - 1) * delta);
+            (uint64_t)p.msg * p.delta(), (uint64_t)(p.msg - 1) * p.delta());
   uint64_t *v = (uint64_t *)lhs_array->ptr;
   axpy(st, v, nullptr, v, nullptr, 1, m->d_neg, nullptr, w, T);
   m->prop.run(streams, v, cts, ksks, bsks, nullptr, cout);
-  if (cout)
-    for (uint32_t i = 0; i < cts; ++i) {
-      if (carry_out->degrees) carry_out->degrees[i] = 1;
-      if (carry_out->noise_levels) carry_out->noise_levels[i] = 1;
-    }
-  for (uint32_t i = 0; i < lhs_array->num_radix_blocks; ++i) {
-    if (lhs_array->degrees) lhs_array->degrees[i] = p.msg - 1;
-    if (lhs_array->noise_levels) lhs_array->noise_levels[i] = 1;
-  }
+  if (cout) set_block_info(carry_out, 0, cts, 1, 1);
+  set_block_info(lhs_array, 0, lhs_array->num_radix_blocks, p.msg - 1, 1);
 }
 
 void cleanup_cuda_sub_and_propagate_single_carry_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<SubMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == SubMem::kMagic, "cleanup sub_and_propagate_single_carry: foreign scratch pointer");
-  m->prop.release(streams);
-  if (m->d_neg) scratch_free(m->d_neg);
-  m->magic = 0;
-  delete m;
-  *mem_ptr_void = nullptr;
+  scratch_destroy<SubMem>(streams, mem_ptr_void, "cleanup sub_and_propagate_single_carry");
 }
 
 // ---- cuda/include/integer/integer.h:415-431 -----------------------------------------------------
@@ -2208,12 +2132,11 @@ void cuda_integer_overflowing_sub_64_inplace_async(CudaStreamsFFI streams, CudaR
   HX_PANIC_IF_FALSE(overflow_block && overflow_block->ptr && lhs_array, "integer_overflowing_sub: the overflow block is missing");
   cuda_sub_and_propagate_single_carry_64_inplace_async(streams, lhs_array, rhs_array, overflow_block, input_borrow, mem_ptr, bsks,
                                                        ksks, 2, 0);
-  auto *m = reinterpret_cast<SubMem *>(mem_ptr);
+  auto *m = scratch_use<SubMem>(mem_ptr, "integer_overflowing_sub");
   const Params &p = m->prop.drv.p;
   const uint32_t cts = lhs_array->num_radix_blocks / m->prop.blocks;
-  const uint64_t delta = ((uint64_t)1 << 63) / ((uint64_t)p.msg * p.carry);
   HX_LAUNCH(lwe_negate_const_kernel, dim3(cts), dim3(256), 0, S0(streams), (uint64_t *)overflow_block->ptr,
-            (const uint64_t *)overflow_block->ptr, p.big_n + 1, cts, 1, delta, delta);  // 1 - carry
+            (const uint64_t *)overflow_block->ptr, p.big_n + 1, cts, 1, p.delta(), p.delta());  // 1 - carry
 }
 void cleanup_cuda_integer_overflowing_sub_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
   cleanup_cuda_sub_and_propagate_single_carry_64_inplace(streams, mem_ptr_void);
@@ -2226,33 +2149,23 @@ uint64_t scratch_cuda_full_propagation_64_inplace_async(CudaStreamsFFI streams, 
                                                         uint32_t message_modulus, uint32_t carry_modulus,
                                                         bool allocate_gpu_memory,
                                                         enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
-  HX_PANIC_IF_FALSE(mem_ptr != nullptr, "full_propagation: null pointer");
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
-  auto *m = new FullPropMem();
-  const size_t lw = (size_t)(p.k + 1) * p.N;
-  std::vector<std::vector<uint64_t>> luts(2, std::vector<uint64_t>(lw));
-  const uint32_t msg = p.msg;
-  generate_lut(p, luts[0].data(), [msg](uint64_t x) { return x % msg; });
-  generate_lut(p, luts[1].data(), [msg](uint64_t x) { return x / msg; });
-  m->drv.init(streams, p, 2, luts);
-  radix_alloc((void **)&m->d_two, 2 * (size_t)(p.big_n + 1) * sizeof(uint64_t));
-  m->d_lut_idx = dev_upload(S0(streams), std::vector<uint64_t>{0, 1});
-  m->size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  return scratch_create<FullPropMem>(streams, mem_ptr, allocate_gpu_memory, "full_propagation", [&](FullPropMem &m) {
+    const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+    std::vector<std::vector<uint64_t>> luts(2, std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
+    const uint32_t msg = p.msg;
+    generate_lut(p, luts[0].data(), [msg](uint64_t x) { return x % msg; });
+    generate_lut(p, luts[1].data(), [msg](uint64_t x) { return x / msg; });
+    m.drv.init(streams, p, 2, luts);
+    radix_alloc((void **)&m.d_two, 2 * (size_t)(p.big_n + 1) * sizeof(uint64_t));
+    m.d_lut_idx = dev_upload(S0(streams), std::vector<uint64_t>{0, 1});
+  });
 }
 
 void cuda_full_propagation_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *input_blocks,
                                             int8_t *mem_ptr, void *const *ksks, void *const *bsks,
                                             uint32_t num_blocks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<FullPropMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == FullPropMem::kMagic, "full_propagation: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "full_propagation: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<FullPropMem>(mem_ptr, "full_propagation");
   HX_PANIC_IF_FALSE(input_blocks && input_blocks->ptr && ksks && bsks && num_blocks <= input_blocks->num_radix_blocks,
                     "full_propagation: null pointer or more blocks than the ciphertext holds");
   const Params &p = m->drv.p;
@@ -2265,8 +2178,7 @@ void cuda_full_propagation_64_inplace_async(CudaStreamsFFI streams, CudaRadixCip
     HX_CHECK(hipMemcpyAsync(m->d_two + w, blk, w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
     m->drv.round(streams, m->d_two, nullptr, m->d_two, nullptr, m->d_lut_idx, 2, ksks, bsks);
     HX_CHECK(hipMemcpyAsync(blk, m->d_two, w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    if (input_blocks->degrees) input_blocks->degrees[i] = p.msg - 1;
-    if (input_blocks->noise_levels) input_blocks->noise_levels[i] = 1;
+    set_block_info(input_blocks, i, 1, p.msg - 1, 1);
     if (i + 1 < num_blocks) {
       axpy(st, blk + w, nullptr, blk + w, nullptr, 1, m->d_two + w, nullptr, (uint32_t)w, 1);
       if (input_blocks->degrees) input_blocks->degrees[i + 1] += p.carry - 1;
@@ -2276,28 +2188,74 @@ void cuda_full_propagation_64_inplace_async(CudaStreamsFFI streams, CudaRadixCip
 }
 
 void cleanup_cuda_full_propagation_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<FullPropMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == FullPropMem::kMagic, "cleanup full_propagation: foreign scratch pointer");
-  m->drv.release(streams);
-  for (uint64_t *d : {m->d_two, m->d_lut_idx})
-    if (d) scratch_free(d);
-  m->magic = 0;
-  delete m;
-  *mem_ptr_void = nullptr;
+  scratch_destroy<FullPropMem>(streams, mem_ptr_void, "cleanup full_propagation");
 }
 
 // ---- cuda/include/integer/integer.h:246-276 (comparison), :349-365 (cmux) ----------------------------
 // Unsigned operands; the boolean lands in block 0 of lwe_array_out (its other blocks are cleared), as the single-block
 // result of the reference's EQ ... LE.  MAX / MIN: the ordering's flag drives a cmux of the operands.
-struct CompareScratch {
+namespace {
+struct CompareScratch : ScratchHeader {
   static constexpr uint32_t kMagic = 0x43535231;  // "CSR1"
-  uint32_t magic = kMagic;
   uint32_t op = 0;
   CompareMem cmp;
   CmuxMem mux;  // MAX / MIN only
   uint64_t *d_flag = nullptr;
+
+  bool select() const { return op == MAX || op == MIN; }
+  // shared by the ciphertext and the scalar form (one integer per call: hip_integer_scratch_batch is not read)
+  void init(const CudaStreamsFFI &streams, CudaLweBootstrapKeyParamsFFI bsk_params, CudaLweKeyswitchKeyParamsFFI ksk_params,
+            uint32_t count, uint32_t message_modulus, uint32_t carry_modulus, uint32_t op_type, bool is_signed,
+            uint32_t noise_reduction_type) {
+    HX_PANIC_IF_FALSE(count >= 1, "integer_comparison: null pointer or no blocks");
+    HX_PANIC_IF_FALSE(!is_signed, "integer_comparison: signed operands are not wired");
+    HX_PANIC_IF_FALSE(op_type <= MIN, "integer_comparison: unknown operation %u", op_type);
+    const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, noise_reduction_type);
+    op = op_type;
+    cmp.init(streams, p, count, select() ? (uint32_t)GE : op_type);
+    if (select()) {
+      mux.init(streams, p, count);
+      radix_alloc((void **)&d_flag, (size_t)(p.big_n + 1) * sizeof(uint64_t));
+    }
+  }
+  void run(const CudaStreamsFFI &streams, CudaRadixCiphertextFFI *lwe_array_out, CudaRadixCiphertextFFI const *lwe_array_1,
+           CudaRadixCiphertextFFI const *lwe_array_2, void *const *bsks, void *const *ksks) {
+    HX_PANIC_IF_FALSE(lwe_array_out && lwe_array_1 && lwe_array_2 && lwe_array_out->ptr && lwe_array_1->ptr &&
+                          lwe_array_2->ptr && bsks && ksks,
+                      "integer_comparison: null pointer");
+    const uint32_t L = cmp.blocks;
+    HX_PANIC_IF_FALSE(lwe_array_1->num_radix_blocks == L && lwe_array_2->num_radix_blocks == L,
+                      "integer_comparison: the operands must hold the %u blocks the scratch was made for", L);
+    HX_PANIC_IF_FALSE(lwe_array_1->lwe_dimension == lwe_array_2->lwe_dimension &&
+                          lwe_array_out->lwe_dimension == lwe_array_1->lwe_dimension,
+                      "input and output lwe dimension must be equal");
+    const Params &p = cmp.params();
+    check_clean({lwe_array_1, lwe_array_2}, L, p.msg, "integer_comparison",
+                "the comparison takes clean operands (propagate them first)");
+    const size_t w = (size_t)p.big_n + 1;
+    uint64_t *out = (uint64_t *)lwe_array_out->ptr;
+    const uint64_t *a = (const uint64_t *)lwe_array_1->ptr, *b = (const uint64_t *)lwe_array_2->ptr;
+    if (select()) {
+      HX_PANIC_IF_FALSE(lwe_array_out->num_radix_blocks >= L, "integer_comparison: MAX / MIN need %u output blocks", L);
+      cmp.run(streams, d_flag, a, b, ksks, bsks);  // a >= b
+      mux.run(streams, out, d_flag, op == MAX ? a : b, op == MAX ? b : a, ksks, bsks);
+      set_block_info(lwe_array_out, 0, L, p.msg - 1, 1);
+      return;
+    }
+    HX_PANIC_IF_FALSE(lwe_array_out->num_radix_blocks >= 1, "integer_comparison: the output needs a block");
+    cmp.run(streams, out, a, b, ksks, bsks);
+    if (lwe_array_out->num_radix_blocks > 1)
+      HX_CHECK(hipMemsetAsync(out + w, 0, (size_t)(lwe_array_out->num_radix_blocks - 1) * w * sizeof(uint64_t), S0(streams)));
+    set_block_info(lwe_array_out, 0, 1, 1, 1);
+    set_block_info(lwe_array_out, 1, lwe_array_out->num_radix_blocks - 1, 0, 0);
+  }
+  void release(const CudaStreamsFFI &s) {
+    cmp.release(s);
+    if (select()) mux.release(s);
+    if (d_flag) scratch_free(d_flag);
+  }
 };
+}  // namespace
 uint64_t scratch_cuda_integer_comparison_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
                                                   CudaLweBootstrapKeyParamsFFI bsk_params,
                                                   CudaLweKeyswitchKeyParamsFFI ksk_params,
@@ -2305,25 +2263,10 @@ uint64_t scratch_cuda_integer_comparison_64_async(CudaStreamsFFI streams, int8_t
                                                   uint32_t carry_modulus, enum COMPARISON_TYPE op_type, bool is_signed,
                                                   bool allocate_gpu_memory,
                                                   enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
-  HX_PANIC_IF_FALSE(mem_ptr != nullptr && lwe_ciphertext_count >= 1, "integer_comparison: null pointer or no blocks");
-  HX_PANIC_IF_FALSE(!is_signed, "integer_comparison: signed operands are not wired");
-  HX_PANIC_IF_FALSE((uint32_t)op_type <= MIN, "integer_comparison: unknown operation %u", (uint32_t)op_type);
-  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  auto *m = new CompareScratch();
-  m->op = (uint32_t)op_type;
-  const bool select = op_type == MAX || op_type == MIN;
-  m->cmp.init(streams, p, lwe_ciphertext_count, select ? (uint32_t)GE : (uint32_t)op_type);
-  if (select) {
-    m->mux.init(streams, p, lwe_ciphertext_count);
-    radix_alloc((void **)&m->d_flag, (size_t)(p.big_n + 1) * sizeof(uint64_t));
-  }
-  m->cmp.size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  return scratch_create<CompareScratch>(streams, mem_ptr, allocate_gpu_memory, "integer_comparison", [&](CompareScratch &m) {
+    m.init(streams, bsk_params, ksk_params, lwe_ciphertext_count, message_modulus, carry_modulus, (uint32_t)op_type,
+           is_signed, (uint32_t)noise_reduction_type);
+  });
 }
 
 void cuda_integer_comparison_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out,
@@ -2331,57 +2274,27 @@ void cuda_integer_comparison_64_async(CudaStreamsFFI streams, CudaRadixCiphertex
                                       CudaRadixCiphertextFFI const *lwe_array_2, int8_t *mem_ptr, void *const *bsks,
                                       void *const *ksks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<CompareScratch *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == CompareScratch::kMagic, "integer_comparison: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->cmp.size_only, "integer_comparison: scratch was created with allocate_gpu_memory=false");
-  HX_PANIC_IF_FALSE(lwe_array_out && lwe_array_1 && lwe_array_2 && lwe_array_out->ptr && lwe_array_1->ptr &&
-                        lwe_array_2->ptr && bsks && ksks,
-                    "integer_comparison: null pointer");
-  const uint32_t L = m->cmp.blocks;
-  HX_PANIC_IF_FALSE(lwe_array_1->num_radix_blocks == L && lwe_array_2->num_radix_blocks == L,
-                    "integer_comparison: the operands must hold the %u blocks the scratch was made for", L);
-  HX_PANIC_IF_FALSE(lwe_array_1->lwe_dimension == lwe_array_2->lwe_dimension &&
-                        lwe_array_out->lwe_dimension == lwe_array_1->lwe_dimension,
-                    "input and output lwe dimension must be equal");
-  const Params &p = m->cmp.ordering() ? m->cmp.prop.drv.p : m->cmp.eq.p;
-  for (const CudaRadixCiphertextFFI *op : {lwe_array_1, lwe_array_2})
-    if (op->degrees)
-      for (uint32_t i = 0; i < L; ++i)
-        HX_PANIC_IF_FALSE(op->degrees[i] <= p.msg - 1, "integer_comparison: block %u has degree %llu, the comparison takes "
-                          "clean operands (propagate them first)", i, (unsigned long long)op->degrees[i]);
-  const size_t w = (size_t)p.big_n + 1;
-  uint64_t *out = (uint64_t *)lwe_array_out->ptr;
-  const uint64_t *a = (const uint64_t *)lwe_array_1->ptr, *b = (const uint64_t *)lwe_array_2->ptr;
-  if (m->op == MAX || m->op == MIN) {
-    HX_PANIC_IF_FALSE(lwe_array_out->num_radix_blocks >= L, "integer_comparison: MAX / MIN need %u output blocks", L);
-    m->cmp.run(streams, m->d_flag, a, b, ksks, bsks);  // a >= b
-    m->mux.run(streams, out, m->d_flag, m->op == MAX ? a : b, m->op == MAX ? b : a, ksks, bsks);
-    for (uint32_t i = 0; i < L; ++i) {
-      if (lwe_array_out->degrees) lwe_array_out->degrees[i] = p.msg - 1;
-      if (lwe_array_out->noise_levels) lwe_array_out->noise_levels[i] = 1;
-    }
-    return;
-  }
-  HX_PANIC_IF_FALSE(lwe_array_out->num_radix_blocks >= 1, "integer_comparison: the output needs a block");
-  m->cmp.run(streams, out, a, b, ksks, bsks);
-  if (lwe_array_out->num_radix_blocks > 1)
-    HX_CHECK(hipMemsetAsync(out + w, 0, (size_t)(lwe_array_out->num_radix_blocks - 1) * w * sizeof(uint64_t), S0(streams)));
-  for (uint32_t i = 0; i < lwe_array_out->num_radix_blocks; ++i) {
-    if (lwe_array_out->degrees) lwe_array_out->degrees[i] = i == 0 ? 1 : 0;
-    if (lwe_array_out->noise_levels) lwe_array_out->noise_levels[i] = i == 0 ? 1 : 0;
-  }
+  scratch_use<CompareScratch>(mem_ptr, "integer_comparison")->run(streams, lwe_array_out, lwe_array_1, lwe_array_2, bsks, ksks);
+}
+
+void cleanup_cuda_integer_comparison_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<CompareScratch>(streams, mem_ptr_void, "cleanup integer_comparison");
 }
 
 // integer.h:254-274: the scalar comes as its clear blocks (one per radix block, least significant first, the caller stops at
 // the last non-zero one: integer/gpu/server_key/radix/scalar_comparison.rs:129-157).  They become trivial ciphertexts (zero
 // masks) in the scratch and take the ciphertext path: the same rounds, the same tables.
-struct ScalarCompareScratch {
+namespace {
+struct ScalarCompareScratch : ScratchHeader {
   static constexpr uint32_t kMagic = 0x53435231;  // "SCR1"
-  uint32_t magic = kMagic;
-  int8_t *inner = nullptr;  // a CompareScratch
+  CompareScratch cmp;
   uint64_t *d_triv = nullptr;
-  uint32_t blocks = 0, big_n = 0, msg = 0, carry = 0;
+  void release(const CudaStreamsFFI &s) {
+    cmp.release(s);
+    if (d_triv) scratch_free(d_triv);
+  }
 };
+}  // namespace
 uint64_t scratch_cuda_integer_scalar_comparison_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
                                                          CudaLweBootstrapKeyParamsFFI bsk_params,
                                                          CudaLweKeyswitchKeyParamsFFI ksk_params,
@@ -2389,19 +2302,12 @@ uint64_t scratch_cuda_integer_scalar_comparison_64_async(CudaStreamsFFI streams,
                                                          uint32_t carry_modulus, enum COMPARISON_TYPE op_type, bool is_signed,
                                                          bool allocate_gpu_memory,
                                                          enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  HX_PANIC_IF_FALSE(mem_ptr != nullptr, "integer_scalar_comparison: null pointer");
-  auto *m = new ScalarCompareScratch();
-  uint64_t bytes = scratch_cuda_integer_comparison_64_async(streams, &m->inner, bsk_params, ksk_params, lwe_ciphertext_count,
-                                                            message_modulus, carry_modulus, op_type, is_signed,
-                                                            allocate_gpu_memory, noise_reduction_type);
-  m->blocks = lwe_ciphertext_count;
-  m->big_n = ksk_params.input_lwe_dimension;
-  m->msg = message_modulus;
-  m->carry = carry_modulus;
-  const size_t sz = (size_t)lwe_ciphertext_count * (m->big_n + 1) * sizeof(uint64_t);
-  if (allocate_gpu_memory) m->d_triv = (uint64_t *)scratch_alloc(sz);
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return bytes + sz;
+  return scratch_create<ScalarCompareScratch>(
+      streams, mem_ptr, allocate_gpu_memory, "integer_scalar_comparison", [&](ScalarCompareScratch &m) {
+        m.cmp.init(streams, bsk_params, ksk_params, lwe_ciphertext_count, message_modulus, carry_modulus, (uint32_t)op_type,
+                   is_signed, (uint32_t)noise_reduction_type);
+        radix_alloc((void **)&m.d_triv, (size_t)lwe_ciphertext_count * (m.cmp.cmp.params().big_n + 1) * sizeof(uint64_t));
+      });
 }
 
 void cuda_integer_scalar_comparison_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out,
@@ -2409,66 +2315,41 @@ void cuda_integer_scalar_comparison_64_async(CudaStreamsFFI streams, CudaRadixCi
                                              void const *h_scalar_blocks, int8_t *mem_ptr, void *const *bsks,
                                              void *const *ksks, uint32_t num_scalar_blocks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<ScalarCompareScratch *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == ScalarCompareScratch::kMagic, "integer_scalar_comparison: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(m->d_triv != nullptr, "integer_scalar_comparison: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<ScalarCompareScratch>(mem_ptr, "integer_scalar_comparison");
+  const Params &p = m->cmp.cmp.params();
+  const uint32_t L = m->cmp.cmp.blocks;
   HX_PANIC_IF_FALSE(lwe_array_in && lwe_array_in->ptr && (num_scalar_blocks == 0 || (scalar_blocks && h_scalar_blocks)),
                     "integer_scalar_comparison: null pointer");
-  HX_PANIC_IF_FALSE(num_scalar_blocks <= m->blocks, "integer_scalar_comparison: %u scalar blocks for %u radix blocks (the caller "
-                    "truncates the scalar to the ciphertext's length)", num_scalar_blocks, m->blocks);
+  HX_PANIC_IF_FALSE(num_scalar_blocks <= L, "integer_scalar_comparison: %u scalar blocks for %u radix blocks (the caller "
+                    "truncates the scalar to the ciphertext's length)", num_scalar_blocks, L);
   for (uint32_t i = 0; i < num_scalar_blocks; ++i)
-    HX_PANIC_IF_FALSE(((const uint64_t *)h_scalar_blocks)[i] < m->msg, "integer_scalar_comparison: scalar block %u is %llu, not below "
+    HX_PANIC_IF_FALSE(((const uint64_t *)h_scalar_blocks)[i] < p.msg, "integer_scalar_comparison: scalar block %u is %llu, not below "
                       "the message modulus", i, (unsigned long long)((const uint64_t *)h_scalar_blocks)[i]);
   const hipStream_t st = S0(streams);
-  const uint32_t w = m->big_n + 1;
-  HX_CHECK(hipMemsetAsync(m->d_triv, 0, (size_t)m->blocks * w * sizeof(uint64_t), st));
+  const uint32_t w = p.big_n + 1;
+  HX_CHECK(hipMemsetAsync(m->d_triv, 0, (size_t)L * w * sizeof(uint64_t), st));
   if (num_scalar_blocks)
     HX_LAUNCH(lwe_body_add_scalars_kernel, dim3((num_scalar_blocks + 255) / 256), dim3(256), 0, st, m->d_triv,
-              (const uint64_t *)scalar_blocks, w, num_scalar_blocks, ((uint64_t)1 << 63) / ((uint64_t)m->msg * m->carry));
-  std::vector<uint64_t> deg(m->blocks, 0), noise(m->blocks, 0);
+              (const uint64_t *)scalar_blocks, w, num_scalar_blocks, p.delta());
+  std::vector<uint64_t> deg(L, 0), noise(L, 0);
   for (uint32_t i = 0; i < num_scalar_blocks; ++i) deg[i] = ((const uint64_t *)h_scalar_blocks)[i];
-  CudaRadixCiphertextFFI triv{m->d_triv, deg.data(), noise.data(), m->blocks, m->blocks, m->big_n};
-  cuda_integer_comparison_64_async(streams, lwe_array_out, lwe_array_in, &triv, m->inner, bsks, ksks);
+  CudaRadixCiphertextFFI triv{m->d_triv, deg.data(), noise.data(), L, L, p.big_n};
+  m->cmp.run(streams, lwe_array_out, lwe_array_in, &triv, bsks, ksks);
 }
 
 void cleanup_cuda_integer_scalar_comparison_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<ScalarCompareScratch *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == ScalarCompareScratch::kMagic, "cleanup integer_scalar_comparison: foreign scratch pointer");
-  cleanup_cuda_integer_comparison_64(streams, &m->inner);
-  if (m->d_triv) scratch_free(m->d_triv);
-  m->magic = 0;
-  delete m;
-  *mem_ptr_void = nullptr;
-}
-
-void cleanup_cuda_integer_comparison_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<CompareScratch *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == CompareScratch::kMagic, "cleanup integer_comparison: foreign scratch pointer");
-  m->cmp.release(streams);
-  if (m->op == MAX || m->op == MIN) m->mux.release(streams);
-  if (m->d_flag) scratch_free(m->d_flag);
-  m->magic = 0;
-  delete m;
-  *mem_ptr_void = nullptr;
+  scratch_destroy<ScalarCompareScratch>(streams, mem_ptr_void, "cleanup integer_scalar_comparison");
 }
 
 uint64_t scratch_cuda_cmux_64_async(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
                                     CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t lwe_ciphertext_count,
                                     uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
                                     enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
   HX_PANIC_IF_FALSE(mem_ptr != nullptr && lwe_ciphertext_count >= 1, "cmux: null pointer or no blocks");
   const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  auto *m = new CmuxMem();
-  m->init(streams, p, lwe_ciphertext_count);
-  m->size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  // (one integer per call: hip_integer_scratch_batch is not read)
+  return scratch_create<CmuxMem>(streams, mem_ptr, allocate_gpu_memory, "cmux",
+                                 [&](CmuxMem &m) { m.init(streams, p, lwe_ciphertext_count); });
 }
 
 void cuda_cmux_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out,
@@ -2476,9 +2357,7 @@ void cuda_cmux_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_arra
                         CudaRadixCiphertextFFI const *lwe_array_false, int8_t *mem_ptr, void *const *bsks,
                         void *const *ksks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<CmuxMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == CmuxMem::kMagic, "cmux: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "cmux: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<CmuxMem>(mem_ptr, "cmux");
   HX_PANIC_IF_FALSE(lwe_array_out && lwe_condition && lwe_array_true && lwe_array_false && lwe_array_out->ptr &&
                         lwe_condition->ptr && lwe_array_true->ptr && lwe_array_false->ptr && bsks && ksks,
                     "cmux: null pointer");
@@ -2491,29 +2370,17 @@ void cuda_cmux_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_arra
                         lwe_condition->lwe_dimension == lwe_array_true->lwe_dimension,
                     "input and output lwe dimension must be equal");
   const Params &p = m->drv.p;
-  for (const CudaRadixCiphertextFFI *op : {lwe_array_true, lwe_array_false})
-    if (op->degrees)
-      for (uint32_t i = 0; i < L; ++i)
-        HX_PANIC_IF_FALSE(op->degrees[i] <= p.msg - 1, "cmux: block %u has degree %llu, the branches must be clean", i,
-                          (unsigned long long)op->degrees[i]);
+  check_clean({lwe_array_true, lwe_array_false}, L, p.msg, "cmux", "the branches must be clean");
   if (lwe_condition->degrees)
     HX_PANIC_IF_FALSE(lwe_condition->degrees[0] <= 1, "cmux: the condition must be a boolean block (degree %llu)",
                       (unsigned long long)lwe_condition->degrees[0]);
   m->run(streams, (uint64_t *)lwe_array_out->ptr, (const uint64_t *)lwe_condition->ptr,
          (const uint64_t *)lwe_array_true->ptr, (const uint64_t *)lwe_array_false->ptr, ksks, bsks);
-  for (uint32_t i = 0; i < L; ++i) {
-    if (lwe_array_out->degrees) lwe_array_out->degrees[i] = p.msg - 1;
-    if (lwe_array_out->noise_levels) lwe_array_out->noise_levels[i] = 1;
-  }
+  set_block_info(lwe_array_out, 0, L, p.msg - 1, 1);
 }
 
 void cleanup_cuda_cmux_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<CmuxMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == CmuxMem::kMagic, "cleanup cmux: foreign scratch pointer");
-  m->release(streams);
-  delete m;
-  *mem_ptr_void = nullptr;
+  scratch_destroy<CmuxMem>(streams, mem_ptr_void, "cleanup cmux");
 }
 
 // ---- cuda/include/integer/integer.h:200-228 -------------------------------------------------------
@@ -2523,51 +2390,40 @@ uint64_t scratch_cuda_logical_scalar_shift_64_inplace_async(CudaStreamsFFI strea
                                                             uint32_t message_modulus, uint32_t carry_modulus,
                                                             enum SHIFT_OR_ROTATE_TYPE shift_type, bool allocate_gpu_memory,
                                                             enum PBS_MS_REDUCTION_T noise_reduction_type) {
-  first_gpu(streams);
   HX_PANIC_IF_FALSE(mem_ptr != nullptr && num_blocks >= 1, "logical_scalar_shift: null pointer or no blocks");
   HX_PANIC_IF_FALSE(shift_type == LEFT_SHIFT || shift_type == RIGHT_SHIFT,
                     "logical_scalar_shift: shift type %u is a rotation (scalar_rotate is not wired)", (uint32_t)shift_type);
   HX_PANIC_IF_FALSE((message_modulus & (message_modulus - 1)) == 0, "logical_scalar_shift: the message modulus must be a power of two");
   const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
-  t_dry = !allocate_gpu_memory;
-  t_bytes = 0;
-  auto *m = new ScalarShiftMem();
-  m->blocks = num_blocks;
-  m->bits = (uint32_t)__builtin_ctz(p.msg);
-  m->left = shift_type == LEFT_SHIFT;
-  const uint32_t msg = p.msg, bits = m->bits;
-  const bool left = m->left != 0;
-  std::vector<std::vector<uint64_t>> luts(std::max(1u, bits - 1), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
-  for (uint32_t r = 1; r < bits; ++r)  // packed msg * current + neighbour (lower neighbour for a left shift, upper for a right one)
-    generate_lut(p, luts[r - 1].data(), [msg, bits, r, left](uint64_t x) -> uint64_t {
-      const uint64_t cur = x / msg, nb = x % msg;
-      return (left ? ((cur << r) | (nb >> (bits - r))) : ((cur >> r) | (nb << (bits - r)))) % msg;
-    });
-  m->drv.init(streams, p, num_blocks, luts);
-  radix_alloc((void **)&m->d_pack, (size_t)num_blocks * (p.big_n + 1) * sizeof(uint64_t));
-  std::vector<uint64_t> li((size_t)std::max(1u, bits - 1) * num_blocks);
-  for (size_t i = 0; i < li.size(); ++i) li[i] = i / num_blocks;
-  m->d_lut_idx = dev_upload(S0(streams), li);
-  m->size_only = t_dry;
-  t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(m);
-  return t_bytes;
+  return scratch_create<ScalarShiftMem>(streams, mem_ptr, allocate_gpu_memory, "logical_scalar_shift", [&](ScalarShiftMem &m) {
+    m.blocks = num_blocks;
+    m.bits = (uint32_t)__builtin_ctz(p.msg);
+    m.left = shift_type == LEFT_SHIFT;
+    const uint32_t msg = p.msg, bits = m.bits;
+    const bool left = m.left != 0;
+    std::vector<std::vector<uint64_t>> luts(std::max(1u, bits - 1), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
+    for (uint32_t r = 1; r < bits; ++r)  // packed msg * current + neighbour (lower neighbour for a left shift, upper for a right one)
+      generate_lut(p, luts[r - 1].data(), [msg, bits, r, left](uint64_t x) -> uint64_t {
+        const uint64_t cur = x / msg, nb = x % msg;
+        return (left ? ((cur << r) | (nb >> (bits - r))) : ((cur >> r) | (nb << (bits - r)))) % msg;
+      });
+    m.drv.init(streams, p, num_blocks, luts);
+    radix_alloc((void **)&m.d_pack, (size_t)num_blocks * (p.big_n + 1) * sizeof(uint64_t));
+    std::vector<uint64_t> li((size_t)std::max(1u, bits - 1) * num_blocks);
+    for (size_t i = 0; i < li.size(); ++i) li[i] = i / num_blocks;
+    m.d_lut_idx = dev_upload(S0(streams), li);
+  });
 }
 
 void cuda_logical_scalar_shift_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array, uint32_t shift,
                                                 int8_t *mem_ptr, void *const *bsks, void *const *ksks) {
   first_gpu(streams);
-  auto *m = reinterpret_cast<ScalarShiftMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == ScalarShiftMem::kMagic, "logical_scalar_shift: foreign scratch pointer");
-  HX_PANIC_IF_FALSE(!m->size_only, "logical_scalar_shift: scratch was created with allocate_gpu_memory=false");
+  auto *m = scratch_use<ScalarShiftMem>(mem_ptr, "logical_scalar_shift");
   HX_PANIC_IF_FALSE(lwe_array && lwe_array->ptr && bsks && ksks, "logical_scalar_shift: null pointer");
   const uint32_t L = m->blocks;
   HX_PANIC_IF_FALSE(lwe_array->num_radix_blocks >= L, "input does not have enough blocks");
   const Params &p = m->drv.p;
-  if (lwe_array->degrees)
-    for (uint32_t i = 0; i < L; ++i)
-      HX_PANIC_IF_FALSE(lwe_array->degrees[i] <= p.msg - 1, "logical_scalar_shift: block %u has degree %llu, the shift takes "
-                        "clean blocks", i, (unsigned long long)lwe_array->degrees[i]);
+  check_clean({lwe_array}, L, p.msg, "logical_scalar_shift", "the shift takes clean blocks");
   if (shift == 0) return;
   const hipStream_t st = S0(streams);
   const uint32_t w = p.big_n + 1;
@@ -2575,10 +2431,7 @@ void cuda_logical_scalar_shift_64_inplace_async(CudaStreamsFFI streams, CudaRadi
   auto clear = [&](uint32_t first, uint32_t count) {
     if (count == 0) return;
     HX_CHECK(hipMemsetAsync(v + (size_t)first * w, 0, (size_t)count * w * sizeof(uint64_t), st));
-    for (uint32_t i = first; i < first + count; ++i) {
-      if (lwe_array->degrees) lwe_array->degrees[i] = 0;
-      if (lwe_array->noise_levels) lwe_array->noise_levels[i] = 0;
-    }
+    set_block_info(lwe_array, first, count, 0, 0);
   };
   if ((uint64_t)shift >= (uint64_t)m->bits * L) {  // every bit leaves
     clear(0, L);
@@ -2612,33 +2465,19 @@ void cuda_logical_scalar_shift_64_inplace_async(CudaStreamsFFI streams, CudaRadi
     axpy(st, m->d_pack + (size_t)(n - 1) * w, nullptr, v + (size_t)(L - 1) * w, nullptr, p.msg, nullptr, nullptr, w, 1);
     m->drv.round(streams, v, nullptr, m->d_pack, nullptr, lut, n, ksks, bsks);
   }
-  for (uint32_t i = (m->left ? q : 0); i < (m->left ? L : n); ++i) {
-    if (lwe_array->degrees) lwe_array->degrees[i] = p.msg - 1;
-    if (lwe_array->noise_levels) lwe_array->noise_levels[i] = 1;
-  }
+  set_block_info(lwe_array, m->left ? q : 0, n, p.msg - 1, 1);
   clear(m->left ? 0 : n, q);
 }
 
 void cleanup_cuda_logical_scalar_shift_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
-  first_gpu(streams);
-  auto *m = reinterpret_cast<ScalarShiftMem *>(*mem_ptr_void);
-  HX_PANIC_IF_FALSE(m && m->magic == ScalarShiftMem::kMagic, "cleanup logical_scalar_shift: foreign scratch pointer");
-  HX_CHECK(hipStreamSynchronize(S0(streams)));
-  m->drv.release(streams);
-  for (uint64_t *d : {m->d_pack, m->d_lut_idx})
-    if (d) scratch_free(d);
-  m->magic = 0;
-  delete m;
-  *mem_ptr_void = nullptr;
+  scratch_destroy<ScalarShiftMem>(streams, mem_ptr_void, "cleanup logical_scalar_shift");
 }
 
 // number of PBS one carry propagation / one multiplication of `num_blocks` blocks issues (for benches)
 uint64_t hip_integer_propagate_pbs_count(uint32_t num_blocks) { return PropagateMem::pbs_count(num_blocks); }
 uint64_t hip_integer_mult_pbs_count(int8_t *mem_ptr) {
-  if (mem_ptr && reinterpret_cast<BoolMulMem *>(mem_ptr)->magic == BoolMulMem::kMagic)
-    return reinterpret_cast<BoolMulMem *>(mem_ptr)->blocks;
-  auto *m = reinterpret_cast<MulMem *>(mem_ptr);
-  HX_PANIC_IF_FALSE(m && m->magic == MulMem::kMagic, "hip_integer_mult_pbs_count: foreign scratch pointer");
+  if (scratch_magic(mem_ptr) == BoolMulMem::kMagic) return scratch_cast<BoolMulMem>(mem_ptr, "hip_integer_mult_pbs_count")->blocks;
+  auto *m = scratch_cast<MulMem>(mem_ptr, "hip_integer_mult_pbs_count");
   uint64_t n = m->prod_slot.size();
   for (auto &s : m->steps)
     for (size_t g = 0; g < s.msg_slot.size(); ++g) n += 1 + (s.carry_slot[g] != ~(uint64_t)0);
