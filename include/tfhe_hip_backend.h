@@ -609,6 +609,75 @@ uint32_t hip_integer_active_gpu_count(uint32_t num_blocks, uint32_t gpu_count, u
 uint64_t hip_integer_mult_pbs_count(int8_t *mem_ptr);
 uint64_t hip_integer_propagate_pbs_count(uint32_t num_blocks);
 
+/* ------------------------------------------------------------------ ciphertext compression (extensions)
+ * What tfhe/src/shortint/list_compression/compression.rs:17-254 computes and the reference's GPU backend serves with
+ * the packing keyswitch of cuda/include/keyswitch/keyswitch.h and the compress / decompress entry points of
+ * cuda/include/integer/compression/compression.h — here under hip_ names and with argument lists of this library's
+ * own: scalars, device pointers and the FFI structs above.  The reference-named compression symbols remain link stubs
+ * (INTEGRATION.md).  Single GPU: everything runs on entry 0 of
+ * `streams`; the multi-GPU round of the decompression bootstrap is not implemented.
+ *
+ * Packing keyswitch key: [input_lwe_dimension][level_count][(glwe_dimension + 1) * polynomial_size] u64 on the device,
+ * row idx of an input element holding level level_count - idx (lwe_packing_keyswitch_key.rs; a plain memcpy uploads it).
+ * glwe_dimension >= 1, polynomial_size a power of two >= 16, base_log * level_count < 64.
+ *
+ * hip_packing_keyswitch_lwe_list_to_glwe_64_async (core level; core_crypto/algorithms/lwe_packing_keyswitch.rs:102-187,
+ * 296-379): lwe_array_in holds num_lwes contiguous LWEs; every chunk of lwe_per_glwe of them (the last may be partial)
+ * becomes one GLWE  sum_i X^i * G_i  of glwe_array_out ((glwe_dimension + 1) * polynomial_size words each, not modulus
+ * switched).  Panics: lwe_per_glwe > polynomial_size, num_lwes above the scratch's, parameters other than the scratch's. */
+uint64_t hip_scratch_packing_keyswitch_lwe_list_to_glwe_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t base_log, uint32_t level_count, uint32_t num_lwes, bool allocate_gpu_memory);
+void hip_packing_keyswitch_lwe_list_to_glwe_64_async(
+    CudaStreamsFFI streams, void *glwe_array_out, void const *lwe_array_in, void const *fp_ksk, int8_t *mem_ptr,
+    uint32_t input_lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t base_log,
+    uint32_t level_count, uint32_t num_lwes, uint32_t lwe_per_glwe);
+void hip_cleanup_packing_keyswitch_lwe_list_to_glwe_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* Compress (compression.rs:17-133): every block of lwe_array_in (clean: degrees, when given, must be below
+ * message_modulus) is multiplied by message_modulus, chunks of lwe_per_glwe blocks are packed into GLWEs, the first
+ * glwe_dimension * polynomial_size + lwe_per_glwe values of each are switched to storage_log_modulus (1..63) bits and
+ * bit-packed, least significant first (compressed_modulus_switched_glwe_ciphertext.rs:171-250), at a uniform stride of
+ * ceil(values * bits / 64) words per GLWE; the padding bits are zero.  packed_out: device array of
+ * hip_integer_compressed_size_words(...) words.  fp_ksks: one packing key per stream of the set (entry 0 is used).
+ * Panics: more blocks than the scratch's num_radix_blocks, a block with a carry, another input LWE dimension. */
+uint64_t hip_scratch_integer_compress_radix_ciphertext_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t input_lwe_dimension, uint32_t compression_glwe_dimension,
+    uint32_t compression_polynomial_size, uint32_t ks_base_log, uint32_t ks_level, uint32_t num_radix_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
+    bool allocate_gpu_memory);
+void hip_integer_compress_radix_ciphertext_64_async(
+    CudaStreamsFFI streams, void *packed_out, CudaRadixCiphertextFFI const *lwe_array_in, void *const *fp_ksks,
+    int8_t *mem_ptr);
+void hip_cleanup_integer_compress_radix_ciphertext_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* Decompress (compression.rs:164-254): for every h_indexes[i] (a HOST array, as in the reference) the LWE of dimension
+ * compression_glwe_dimension * compression_polynomial_size at that position of the packed list is extracted straight
+ * from the packed words and bootstrapped — no keyswitch — with the decompression key bsks[0] (classic or multi-bit by
+ * bsk_params.pbs_type, Fourier domain as the conversion functions above leave it; its input_lwe_dimension is the
+ * compression GLWE's) and the rescaling identity table (compression.rs:137-162) into block i of lwe_array_out, a clean
+ * block under the big compute key.  total_lwe_bodies_count: the blocks the list was compressed from.
+ * Panics: an index at or above total_lwe_bodies_count, more indexes than the scratch's num_blocks_to_decompress or the
+ * output's blocks, indexes that are not non-decreasing in GLWE index (index / lwe_per_glwe; the order within a GLWE is
+ * free), message_modulus != carry_modulus. */
+uint64_t hip_scratch_integer_decompress_radix_ciphertext_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+    uint32_t compression_glwe_dimension, uint32_t compression_polynomial_size, uint32_t lwe_per_glwe,
+    uint32_t storage_log_modulus, uint32_t num_blocks_to_decompress, uint32_t message_modulus, uint32_t carry_modulus,
+    bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_decompress_radix_ciphertext_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out, void const *packed_in,
+    uint32_t total_lwe_bodies_count, uint32_t const *h_indexes, uint32_t num_indexes, void *const *bsks,
+    int8_t *mem_ptr);
+void hip_cleanup_integer_decompress_radix_ciphertext_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* GLWE glwe_index of a packed list, unpacked (values shifted back to the top of the word) into
+ * (glwe_dimension + 1) * polynomial_size words; the body coefficients beyond that GLWE's count are zero. */
+void hip_integer_extract_glwe_64_async(
+    CudaStreamsFFI streams, void *glwe_out, void const *packed_in, uint32_t glwe_index, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus, uint32_t total_lwe_bodies_count);
+/* pure host helper: u64 words of the packed list of total_blocks blocks */
+uint64_t hip_integer_compressed_size_words(
+    uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
+    uint32_t total_blocks);
+
 /* Select which f64 kernel serves cuda_programmable_bootstrap_64_async (all give identical bits):
  * 0 = automatic (N=2048,k=1: latency kernel up to 256 LWEs, throughput kernel beyond; N=1024,k<=2: its
  *     throughput kernel; generic otherwise),

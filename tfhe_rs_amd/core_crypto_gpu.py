@@ -254,6 +254,58 @@ class CudaLweKeyswitchKey:
         return self
 
 
+class CudaLwePackingKeyswitchKey:
+    """gpu/entities/lwe_packing_keyswitch_key.rs: [input_lwe_dimension][level][(glwe_dimension + 1) * polynomial_size]
+    u64 words on every GPU of `streams`, uploaded as they are."""
+
+    @classmethod
+    def from_lwe_packing_keyswitch_key(cls, h_pksk, input_key_lwe_dimension, output_glwe_dimension, output_polynomial_size,
+                                       decomp_base_log, decomp_level_count, streams):
+        self = cls()
+        self.input_key_lwe_dimension = int(input_key_lwe_dimension)
+        self.output_glwe_dimension = int(output_glwe_dimension)
+        self.output_polynomial_size = int(output_polynomial_size)
+        self.decomp_base_log = int(decomp_base_log)
+        self.decomp_level_count = int(decomp_level_count)
+        h_pksk = np.ascontiguousarray(h_pksk, dtype=U64)
+        assert h_pksk.size == (self.input_key_lwe_dimension * self.decomp_level_count *
+                               (self.output_glwe_dimension + 1) * self.output_polynomial_size), \
+            "packing keyswitch key container has the wrong size"
+        self.d_vecs = [CudaVec.from_cpu_async(h_pksk.reshape(-1), streams, i) for i in range(len(streams))]
+        self.d_vec = self.d_vecs[0]
+        return self
+
+
+def _streams_ffi(streams):
+    ptrs = (C.c_void_p * len(streams))(*streams.ptr)
+    idx = (C.c_uint32 * len(streams))(*streams.gpu_indexes)
+    return ffi.CudaStreamsFFI(ptrs, idx, len(streams)), (ptrs, idx)
+
+
+def cuda_keyswitch_lwe_ciphertext_list_and_pack_in_glwe_ciphertext(pksk, input_lwe_list, output_glwe_list, streams,
+                                                                   lwe_per_glwe=None):
+    """gpu/algorithms/lwe_packing_keyswitch.rs: the LWEs of `input_lwe_list`, in chunks of `lwe_per_glwe` (default: all
+    of them in one GLWE), are keyswitched and packed, LWE i of a chunk at X^i, into the GLWEs of `output_glwe_list`
+    (scratch -> launch -> cleanup)."""
+    assert pksk.input_key_lwe_dimension == input_lwe_list.lwe_dimension, (
+        f"Mismatched input LweDimension. LwePackingKeyswitchKey input LweDimension: {pksk.input_key_lwe_dimension}, "
+        f"input LweCiphertext LweDimension {input_lwe_list.lwe_dimension}.")
+    assert (pksk.output_glwe_dimension == output_glwe_list.glwe_dimension and
+            pksk.output_polynomial_size == output_glwe_list.polynomial_size), "Mismatched output GlweSize / PolynomialSize"
+    n = input_lwe_list.lwe_ciphertext_count
+    per = n if lwe_per_glwe is None else int(lwe_per_glwe)
+    assert output_glwe_list.glwe_ciphertext_count * per >= n, "output GLWE list too short"
+    s, keep = _streams_ffi(streams)
+    mem = C.c_void_p()
+    shape = (pksk.input_key_lwe_dimension, pksk.output_glwe_dimension, pksk.output_polynomial_size, pksk.decomp_base_log,
+             pksk.decomp_level_count)
+    lib = _lib()
+    lib.hip_scratch_packing_keyswitch_lwe_list_to_glwe_64_async(s, C.byref(mem), *shape, n, True)
+    lib.hip_packing_keyswitch_lwe_list_to_glwe_64_async(s, output_glwe_list.d_vec.ptr, input_lwe_list.d_vec.ptr,
+                                                        pksk.d_vec.ptr, mem, *shape, n, per)
+    lib.hip_cleanup_packing_keyswitch_lwe_list_to_glwe_64(s, C.byref(mem))
+
+
 # ciphertexts of the last split-key bootstrap that went through the integer kernel (cuda_programmable_bootstrap_lwe_ciphertext)
 last_split_recomputed = 0
 

@@ -147,6 +147,56 @@ void launch_closest_representable(hipStream_t st, const uint64_t *in, uint64_t *
   HX_LAUNCH(closest_representable_kernel, dim3(1), dim3(1), 0, st, in, out, base_log, level);
 }
 
+// ------------------------------------------------------------------ compressed GLWE lists: unpack (+ sample extract)
+// Value v of a packed GLWE: `bits` bits at bit offset v * bits of its words, least significant first (PackedIntegers,
+// cc/entities/compressed_modulus_switched_glwe_ciphertext.rs:171-250), shifted back up to the top of the word
+// (compression.cuh:293-340 does the same in a launch of its own).
+HX_DEV uint64_t unpack_value(const uint64_t *words, uint32_t v, uint32_t bits) {
+  const uint64_t bit = (uint64_t)v * bits;
+  const uint32_t w = (uint32_t)(bit >> 6), off = (uint32_t)(bit & 63);
+  uint64_t x = words[w] >> off;
+  if (off + bits > 64) x |= words[w + 1] << (64 - off);  // (the value's last bit is in range, so is word w + 1)
+  return (x & (((uint64_t)1 << bits) - 1)) << (64 - bits);
+}
+
+// One workgroup per requested index t: GLWE t / lwe_per_glwe of the packed list, coefficient nth = t % lwe_per_glwe, is
+// extracted into an LWE of dimension k*N straight from the packed words — the mask reversal of the sample extraction
+// (cc/algorithms/glwe_sample_extraction.rs:89-164) reads value nth - j or, negated, N + nth - j of every mask
+// polynomial, the body is value k*N + nth.  The body values beyond the GLWE's count, which decompression treats as
+// zero (compression.rs:164-227), are never read: nth is below the count (checked by the caller).
+__global__ void __launch_bounds__(256) unpack_extract_kernel(uint64_t *lwe_out, const uint64_t *packed,
+                                                             const uint32_t *indexes, uint32_t k, uint32_t N,
+                                                             uint32_t lwe_per_glwe, uint32_t bits, uint32_t words_per_glwe) {
+  const uint32_t t = indexes[blockIdx.x], nth = t % lwe_per_glwe;
+  const uint64_t *words = packed + (size_t)(t / lwe_per_glwe) * words_per_glwe;
+  uint64_t *out = lwe_out + (size_t)blockIdx.x * ((size_t)k * N + 1);
+  for (uint32_t e = threadIdx.x; e < k * N; e += blockDim.x) {
+    const uint32_t q = e / N, j = e - q * N;
+    out[e] = j <= nth ? unpack_value(words, q * N + nth - j, bits)
+                      : (uint64_t)0 - unpack_value(words, q * N + N + nth - j, bits);
+  }
+  if (threadIdx.x == 0) out[(size_t)k * N] = unpack_value(words, k * N + nth, bits);
+}
+
+// One GLWE of a packed list as (k+1)*N words: the k*N mask values and `bodies` body values, the tail zero
+__global__ void __launch_bounds__(256) unpack_glwe_kernel(uint64_t *glwe_out, const uint64_t *words, uint32_t k, uint32_t N,
+                                                          uint32_t bodies, uint32_t bits) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < (k + 1) * N) glwe_out[v] = v < k * N + bodies ? unpack_value(words, v, bits) : 0;
+}
+
+void launch_unpack_extract(hipStream_t st, uint64_t *lwe_out, const uint64_t *packed, const uint32_t *indexes,
+                           uint32_t count, uint32_t k, uint32_t N, uint32_t lwe_per_glwe, uint32_t bits,
+                           uint32_t words_per_glwe) {
+  if (!count) return;
+  HX_LAUNCH(unpack_extract_kernel, dim3(count), dim3(256), 0, st, lwe_out, packed, indexes, k, N, lwe_per_glwe, bits,
+            words_per_glwe);
+}
+void launch_unpack_glwe(hipStream_t st, uint64_t *glwe_out, const uint64_t *words, uint32_t k, uint32_t N, uint32_t bodies,
+                        uint32_t bits) {
+  HX_LAUNCH(unpack_glwe_kernel, dim3(((k + 1) * N + 255) / 256), dim3(256), 0, st, glwe_out, words, k, N, bodies, bits);
+}
+
 __global__ void iota_u64_kernel(uint64_t *out, uint32_t count) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) out[i] = i;

@@ -1538,6 +1538,93 @@ static void check_clean(std::initializer_list<const CudaRadixCiphertextFFI *> op
                           (unsigned long long)op->degrees[i], tail);
 }
 
+// ------------------------------------------------------------------ ciphertext compression
+// tfhe/src/shortint/list_compression/compression.rs:17-133 (compress), :137-254 (decompress); the reference's GPU flow is
+// cuda/src/integer/compression/compression.cuh:199-291 and :293-554.  The kernels are keyswitch.hip (packing keyswitch
+// and its fused rotate / sum / modulus switch / bit-pack epilogue) and ciphertext.hip (unpack + sample extract).
+struct CompressionShape {
+  uint32_t n_in = 0, k = 0, N = 0, base_log = 0, level = 0;  // packing key: [n_in][level][(k+1)*N]
+  uint32_t ncols() const { return (k + 1) * N; }
+};
+static void check_compression_glwe(uint32_t k, uint32_t N, const char *who) {
+  HX_PANIC_IF_FALSE(k >= 1 && N >= 16 && (N & (N - 1)) == 0,
+                    "%s: compression GLWE needs glwe_dimension >= 1 and a power-of-two polynomial_size >= 16 (got %u, %u)", who,
+                    k, N);
+}
+static void check_storage(uint32_t N, uint32_t lwe_per_glwe, uint32_t bits, const char *who) {
+  HX_PANIC_IF_FALSE(lwe_per_glwe >= 1 && lwe_per_glwe <= N, "%s: lwe_per_glwe %u must be in 1..polynomial_size (%u)", who,
+                    lwe_per_glwe, N);
+  HX_PANIC_IF_FALSE(bits >= 1 && bits <= 63, "%s: storage_log_modulus %u must be in 1..63", who, bits);
+}
+static uint32_t packed_words_per_glwe(uint32_t k, uint32_t N, uint32_t lwe_per_glwe, uint32_t bits) {
+  return (uint32_t)((((uint64_t)k * N + lwe_per_glwe) * bits + 63) / 64);
+}
+
+// core level: LWE list -> unswitched GLWEs
+struct PackingKsMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x504B5331;  // "PKS1"
+  CompressionShape sh;
+  uint32_t cap = 0;  // LWEs per call
+  uint64_t *d_rows = nullptr, *d_trivial = nullptr;
+  void init(const CudaStreamsFFI &s, const CompressionShape &shape, uint32_t capacity) {
+    sh = shape;
+    cap = std::max(1u, capacity);
+    radix_alloc((void **)&d_rows, (size_t)cap * sh.ncols() * sizeof(uint64_t));
+    std::vector<uint64_t> triv(cap);
+    for (uint32_t i = 0; i < cap; ++i) triv[i] = i;
+    d_trivial = dev_upload(S0(s), triv);
+  }
+  void release(const CudaStreamsFFI &) {
+    for (uint64_t *d : {d_rows, d_trivial})
+      if (d) scratch_free(d);
+  }
+};
+
+struct CompressMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x434D5052;  // "CMPR"
+  PackingKsMem pks;  // member: no header of its own in use
+  uint32_t msg = 0, carry = 0, lwe_per_glwe = 0, bits = 0;
+  uint64_t *d_scaled = nullptr;  // the input blocks times message_modulus
+  void release(const CudaStreamsFFI &s) {
+    pks.release(s);
+    if (d_scaled) scratch_free(d_scaled);
+  }
+};
+
+struct DecompressMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x44434D50;  // "DCMP"
+  Params p{};          // the compute set; small_n = k_c * N_c, the decompression key's input dimension
+  uint32_t kc = 0, Nc = 0, lwe_per_glwe = 0, bits = 0, cap = 0, gpu = 0;
+  uint64_t *d_extracted = nullptr, *d_lut = nullptr, *d_trivial = nullptr, *d_lut_idx = nullptr;
+  uint32_t *d_indexes = nullptr, *h_indexes = nullptr;  // h_indexes: pinned staging of the caller's host array
+  hipEvent_t uploaded = nullptr;                         // behind the last copy out of h_indexes
+  int8_t *pbs_buf = nullptr;
+  void release(const CudaStreamsFFI &s) {
+    const hipStream_t st = S0(s);
+    if (pbs_buf) {
+      if (p.grouping) cleanup_cuda_multi_bit_programmable_bootstrap_64(st, gpu, &pbs_buf);
+      else cleanup_cuda_programmable_bootstrap_64(st, gpu, &pbs_buf);
+    }
+    for (void *d : {(void *)d_extracted, (void *)d_lut, (void *)d_trivial, (void *)d_lut_idx, (void *)d_indexes})
+      if (d) scratch_free(d);
+    if (h_indexes) HX_CHECK(hipHostFree(h_indexes));
+    if (uploaded) HX_CHECK(hipEventDestroy(uploaded));
+  }
+};
+
+// compression.rs:137-162 (rescaling_lut): the identity from the encoding the blocks have after the multiplication by
+// message_modulus (plaintext modulus `carry`, no carry space) to the compute encoding (delta = 2^63 / (msg * carry))
+static void generate_rescaling_lut(const Params &p, uint64_t *acc) {
+  const uint32_t sup = p.carry, box = p.N / sup;
+  std::fill(acc, acc + (size_t)p.k * p.N, 0);
+  uint64_t *body = acc + (size_t)p.k * p.N;
+  for (uint32_t i = 0; i < sup; ++i)
+    for (uint32_t j = i * box; j < (i + 1) * box; ++j) body[j] = (uint64_t)i * p.delta();
+  const uint32_t half = box / 2;
+  for (uint32_t i = 0; i < half; ++i) body[i] = (uint64_t)0 - body[i];
+  std::rotate(body, body + half, body + p.N);
+}
+
 }  // namespace radix
 }  // namespace tfhe_hip
 
@@ -2482,6 +2569,214 @@ uint64_t hip_integer_mult_pbs_count(int8_t *mem_ptr) {
   for (auto &s : m->steps)
     for (size_t g = 0; g < s.msg_slot.size(); ++g) n += 1 + (s.carry_slot[g] != ~(uint64_t)0);
   return n + PropagateMem::pbs_count(m->blocks);
+}
+
+// ---- ciphertext compression (hip_ names: the reference-named compression symbols stay link stubs) ---------------------
+uint64_t hip_integer_compressed_size_words(uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe,
+                                           uint32_t storage_log_modulus, uint32_t total_blocks) {
+  check_compression_glwe(glwe_dimension, polynomial_size, "compressed_size_words");
+  check_storage(polynomial_size, lwe_per_glwe, storage_log_modulus, "compressed_size_words");
+  const uint64_t glwes = ((uint64_t)total_blocks + lwe_per_glwe - 1) / lwe_per_glwe;
+  return glwes * packed_words_per_glwe(glwe_dimension, polynomial_size, lwe_per_glwe, storage_log_modulus);
+}
+
+static CompressionShape compression_shape(uint32_t n_in, uint32_t k, uint32_t N, uint32_t base_log, uint32_t level,
+                                          const char *who) {
+  check_compression_glwe(k, N, who);
+  HX_PANIC_IF_FALSE(n_in >= 1 && base_log >= 1 && level >= 1 && base_log * level < 64,
+                    "%s: unsupported packing key (input dimension %u, base_log %u, level %u)", who, n_in, base_log, level);
+  CompressionShape sh;
+  sh.n_in = n_in, sh.k = k, sh.N = N, sh.base_log = base_log, sh.level = level;
+  return sh;
+}
+
+uint64_t hip_scratch_packing_keyswitch_lwe_list_to_glwe_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                                                 uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+                                                                 uint32_t polynomial_size, uint32_t base_log,
+                                                                 uint32_t level_count, uint32_t num_lwes,
+                                                                 bool allocate_gpu_memory) {
+  const CompressionShape sh = compression_shape(input_lwe_dimension, glwe_dimension, polynomial_size, base_log, level_count,
+                                                "packing_keyswitch");
+  return scratch_create<PackingKsMem>(streams, mem_ptr, allocate_gpu_memory, "packing_keyswitch",
+                                      [&](PackingKsMem &m) { m.init(streams, sh, num_lwes); });
+}
+
+void hip_packing_keyswitch_lwe_list_to_glwe_64_async(CudaStreamsFFI streams, void *glwe_array_out, void const *lwe_array_in,
+                                                     void const *fp_ksk, int8_t *mem_ptr, uint32_t input_lwe_dimension,
+                                                     uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t base_log,
+                                                     uint32_t level_count, uint32_t num_lwes, uint32_t lwe_per_glwe) {
+  first_gpu(streams);
+  auto *m = scratch_use<PackingKsMem>(mem_ptr, "packing_keyswitch");
+  HX_PANIC_IF_FALSE(glwe_array_out && lwe_array_in && fp_ksk, "packing_keyswitch: null pointer");
+  HX_PANIC_IF_FALSE(m->sh.n_in == input_lwe_dimension && m->sh.k == glwe_dimension && m->sh.N == polynomial_size &&
+                        m->sh.base_log == base_log && m->sh.level == level_count,
+                    "packing_keyswitch: parameters differ from the ones the scratch was created with");
+  HX_PANIC_IF_FALSE(lwe_per_glwe >= 1 && lwe_per_glwe <= polynomial_size,
+                    "packing_keyswitch: cannot pack more than polynomial_size (%u) LWEs per GLWE, %u requested", polynomial_size,
+                    lwe_per_glwe);
+  HX_PANIC_IF_FALSE(num_lwes <= m->cap, "packing_keyswitch: %u LWEs exceed the scratch capacity %u", num_lwes, m->cap);
+  launch_packing_keyswitch(S0(streams), (uint64_t *)glwe_array_out, m->d_rows, m->d_trivial, (const uint64_t *)lwe_array_in,
+                           (const uint64_t *)fp_ksk, m->sh.n_in, m->sh.k, m->sh.N, m->sh.base_log, m->sh.level, num_lwes,
+                           lwe_per_glwe, 0);
+}
+
+void hip_cleanup_packing_keyswitch_lwe_list_to_glwe_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<PackingKsMem>(streams, mem_ptr_void, "cleanup packing_keyswitch");
+}
+
+uint64_t hip_scratch_integer_compress_radix_ciphertext_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t input_lwe_dimension, uint32_t compression_glwe_dimension,
+    uint32_t compression_polynomial_size, uint32_t ks_base_log, uint32_t ks_level, uint32_t num_radix_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
+    bool allocate_gpu_memory) {
+  const CompressionShape sh = compression_shape(input_lwe_dimension, compression_glwe_dimension, compression_polynomial_size,
+                                                ks_base_log, ks_level, "integer_compress");
+  check_storage(compression_polynomial_size, lwe_per_glwe, storage_log_modulus, "integer_compress");
+  // compression.rs:51-56: the message moves into the carry space
+  HX_PANIC_IF_FALSE(message_modulus >= 2 && message_modulus <= carry_modulus,
+                    "integer_compress: GLWE packing is implemented with messages in carries, so carry_modulus (=%u) must be "
+                    "greater than or equal to message_modulus (=%u)", carry_modulus, message_modulus);
+  return scratch_create<CompressMem>(streams, mem_ptr, allocate_gpu_memory, "integer_compress", [&](CompressMem &m) {
+    m.pks.init(streams, sh, num_radix_blocks);
+    m.msg = message_modulus, m.carry = carry_modulus, m.lwe_per_glwe = lwe_per_glwe, m.bits = storage_log_modulus;
+    radix_alloc((void **)&m.d_scaled, (size_t)m.pks.cap * (sh.n_in + 1) * sizeof(uint64_t));
+  });
+}
+
+void hip_integer_compress_radix_ciphertext_64_async(CudaStreamsFFI streams, void *packed_out,
+                                                    CudaRadixCiphertextFFI const *lwe_array_in, void *const *fp_ksks,
+                                                    int8_t *mem_ptr) {
+  first_gpu(streams);
+  auto *m = scratch_use<CompressMem>(mem_ptr, "integer_compress");
+  HX_PANIC_IF_FALSE(packed_out && lwe_array_in && lwe_array_in->ptr && fp_ksks && fp_ksks[0], "integer_compress: null pointer");
+  const CompressionShape &sh = m->pks.sh;
+  HX_PANIC_IF_FALSE(lwe_array_in->lwe_dimension == sh.n_in,
+                    "integer_compress: ciphertexts do not have the lwe dimension of the packing keyswitch key (%u, key %u)",
+                    lwe_array_in->lwe_dimension, sh.n_in);
+  const uint32_t n = lwe_array_in->num_radix_blocks;
+  HX_PANIC_IF_FALSE(n <= m->pks.cap, "integer_compress: %u blocks exceed the scratch capacity %u", n, m->pks.cap);
+  check_clean({lwe_array_in}, n, m->msg, "integer_compress", "ciphertexts must have empty carries to be compressed");
+  const hipStream_t st = S0(streams);
+  axpy(st, m->d_scaled, nullptr, (const uint64_t *)lwe_array_in->ptr, nullptr, m->msg, nullptr, nullptr, sh.n_in + 1, n);
+  launch_packing_keyswitch(st, (uint64_t *)packed_out, m->pks.d_rows, m->pks.d_trivial, m->d_scaled,
+                           (const uint64_t *)fp_ksks[0], sh.n_in, sh.k, sh.N, sh.base_log, sh.level, n, m->lwe_per_glwe,
+                           m->bits);
+}
+
+void hip_cleanup_integer_compress_radix_ciphertext_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<CompressMem>(streams, mem_ptr_void, "cleanup integer_compress");
+}
+
+uint64_t hip_scratch_integer_decompress_radix_ciphertext_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params, uint32_t compression_glwe_dimension,
+    uint32_t compression_polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
+    uint32_t num_blocks_to_decompress, uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  check_compression_glwe(compression_glwe_dimension, compression_polynomial_size, "integer_decompress");
+  check_storage(compression_polynomial_size, lwe_per_glwe, storage_log_modulus, "integer_decompress");
+  HX_PANIC_IF_FALSE(bsk_params.input_lwe_dimension == compression_glwe_dimension * compression_polynomial_size,
+                    "integer_decompress: the decompression key's input dimension %u is not the compression GLWE's %u x %u",
+                    bsk_params.input_lwe_dimension, compression_glwe_dimension, compression_polynomial_size);
+  // compression.rs:182-188
+  HX_PANIC_IF_FALSE(message_modulus == carry_modulus,
+                    "integer_decompress: message modulus (%u) != carry modulus (%u) is not supported", message_modulus,
+                    carry_modulus);
+  // no keyswitch in front of this bootstrap: the key parameters below only restate the bootstrap's own dimensions
+  const CudaLweKeyswitchKeyParamsFFI no_ks{bsk_params.glwe_dimension * bsk_params.polynomial_size,
+                                           bsk_params.input_lwe_dimension, 1, 1};
+  const Params p = make_params(bsk_params, no_ks, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<DecompressMem>(streams, mem_ptr, allocate_gpu_memory, "integer_decompress", [&](DecompressMem &m) {
+    const hipStream_t st = S0(streams);
+    m.p = p;
+    m.kc = compression_glwe_dimension, m.Nc = compression_polynomial_size;
+    m.lwe_per_glwe = lwe_per_glwe, m.bits = storage_log_modulus;
+    m.cap = std::max(1u, num_blocks_to_decompress);
+    m.gpu = G0(streams);
+    radix_alloc((void **)&m.d_extracted, (size_t)m.cap * (p.small_n + 1) * sizeof(uint64_t));
+    radix_alloc((void **)&m.d_indexes, (size_t)m.cap * sizeof(uint32_t));
+    radix_alloc((void **)&m.d_lut_idx, (size_t)m.cap * sizeof(uint64_t));
+    std::vector<uint64_t> lut((size_t)(p.k + 1) * p.N), triv(m.cap);
+    generate_rescaling_lut(p, lut.data());
+    for (uint32_t i = 0; i < m.cap; ++i) triv[i] = i;
+    m.d_lut = dev_upload(st, lut);
+    m.d_trivial = dev_upload(st, triv);
+    if (!t_dry) {
+      HX_CHECK(hipMemsetAsync(m.d_lut_idx, 0, (size_t)m.cap * sizeof(uint64_t), st));
+      HX_CHECK(hipHostMalloc((void **)&m.h_indexes, (size_t)m.cap * sizeof(uint32_t), 0));
+      HX_CHECK(hipEventCreateWithFlags(&m.uploaded, hipEventDisableTiming));
+    }
+    if (p.grouping)
+      scratch_cuda_multi_bit_programmable_bootstrap_64_async(st, m.gpu, &m.pbs_buf, p.k, p.N, p.pbs_level, m.cap, !t_dry);
+    else
+      scratch_cuda_programmable_bootstrap_64_async(st, m.gpu, &m.pbs_buf, p.small_n, p.k, p.N, p.pbs_level, m.cap, !t_dry,
+                                                   (enum PBS_MS_REDUCTION_T)p.ms_type);
+  });
+}
+
+void hip_integer_decompress_radix_ciphertext_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out,
+                                                      void const *packed_in, uint32_t total_lwe_bodies_count,
+                                                      uint32_t const *h_indexes, uint32_t num_indexes, void *const *bsks,
+                                                      int8_t *mem_ptr) {
+  first_gpu(streams);
+  auto *m = scratch_use<DecompressMem>(mem_ptr, "integer_decompress");
+  HX_PANIC_IF_FALSE(lwe_array_out && lwe_array_out->ptr && packed_in && (h_indexes || num_indexes == 0) && bsks && bsks[0],
+                    "integer_decompress: null pointer");
+  const Params &p = m->p;
+  HX_PANIC_IF_FALSE(lwe_array_out->lwe_dimension == p.big_n,
+                    "integer_decompress: output blocks of lwe dimension %u, the decompression key writes %u",
+                    lwe_array_out->lwe_dimension, p.big_n);
+  HX_PANIC_IF_FALSE(num_indexes <= m->cap && num_indexes <= lwe_array_out->num_radix_blocks,
+                    "integer_decompress: %u indexes exceed the scratch capacity %u or the output's %u blocks", num_indexes,
+                    m->cap, lwe_array_out->num_radix_blocks);
+  for (uint32_t i = 0; i < num_indexes; ++i) {
+    // compression.rs:169-175
+    HX_PANIC_IF_FALSE(h_indexes[i] < total_lwe_bodies_count,
+                      "integer_decompress: tried getting index %u for a compressed list with %u elements, out of bound access",
+                      h_indexes[i], total_lwe_bodies_count);
+    // compression.cuh:381-400 walks the GLWEs in order; here any order would do (a workgroup per index reads its own
+    // GLWE), the check keeps the reference's contract
+    HX_PANIC_IF_FALSE(i == 0 || h_indexes[i] / m->lwe_per_glwe >= h_indexes[i - 1] / m->lwe_per_glwe,
+                      "integer_decompress: indexes must be non-decreasing in GLWE index (index %u after %u)", h_indexes[i],
+                      h_indexes[i - 1]);
+  }
+  if (num_indexes == 0) return;
+  const hipStream_t st = S0(streams);
+  HX_CHECK(hipEventSynchronize(m->uploaded));  // the previous call's copy out of the staging buffer (no-op before the first)
+  std::copy(h_indexes, h_indexes + num_indexes, m->h_indexes);
+  HX_CHECK(hipMemcpyAsync(m->d_indexes, m->h_indexes, (size_t)num_indexes * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HX_CHECK(hipEventRecord(m->uploaded, st));
+  launch_unpack_extract(st, m->d_extracted, (const uint64_t *)packed_in, m->d_indexes, num_indexes, m->kc, m->Nc,
+                        m->lwe_per_glwe, m->bits, packed_words_per_glwe(m->kc, m->Nc, m->lwe_per_glwe, m->bits));
+  uint64_t *out = (uint64_t *)lwe_array_out->ptr;
+  if (p.grouping)
+    cuda_multi_bit_programmable_bootstrap_64_async(st, m->gpu, out, m->d_trivial, m->d_lut, m->d_lut_idx, m->d_extracted,
+                                                   m->d_trivial, bsks[0], m->pbs_buf, p.small_n, p.k, p.N, p.grouping,
+                                                   p.pbs_base_log, p.pbs_level, num_indexes, 1, 0);
+  else
+    cuda_programmable_bootstrap_64_async(st, m->gpu, out, m->d_trivial, m->d_lut, m->d_lut_idx, m->d_extracted, m->d_trivial,
+                                         bsks[0], m->pbs_buf, p.small_n, p.k, p.N, p.pbs_base_log, p.pbs_level, num_indexes,
+                                         1, 0);
+  set_block_info(lwe_array_out, 0, num_indexes, p.msg - 1, 1);
+}
+
+void hip_cleanup_integer_decompress_radix_ciphertext_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<DecompressMem>(streams, mem_ptr_void, "cleanup integer_decompress");
+}
+
+void hip_integer_extract_glwe_64_async(CudaStreamsFFI streams, void *glwe_out, void const *packed_in, uint32_t glwe_index,
+                                       uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe,
+                                       uint32_t storage_log_modulus, uint32_t total_lwe_bodies_count) {
+  first_gpu(streams);
+  HX_PANIC_IF_FALSE(glwe_out && packed_in, "integer_extract_glwe: null pointer");
+  check_compression_glwe(glwe_dimension, polynomial_size, "integer_extract_glwe");
+  check_storage(polynomial_size, lwe_per_glwe, storage_log_modulus, "integer_extract_glwe");
+  HX_PANIC_IF_FALSE((uint64_t)glwe_index * lwe_per_glwe < total_lwe_bodies_count,
+                    "integer_extract_glwe: GLWE %u of a compressed list with %u elements, out of bound access", glwe_index,
+                    total_lwe_bodies_count);
+  const uint32_t bodies = std::min(lwe_per_glwe, total_lwe_bodies_count - glwe_index * lwe_per_glwe);
+  const uint32_t words = packed_words_per_glwe(glwe_dimension, polynomial_size, lwe_per_glwe, storage_log_modulus);
+  launch_unpack_glwe(S0(streams), (uint64_t *)glwe_out, (const uint64_t *)packed_in + (size_t)glwe_index * words,
+                     glwe_dimension, polynomial_size, bodies, storage_log_modulus);
 }
 
 }  // extern "C"

@@ -53,6 +53,12 @@ void launch_keyswitch(hipStream_t st, uint64_t *lwe_out, const uint64_t *out_idx
 void launch_keyswitch_64_32(hipStream_t st, uint32_t *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
                             const uint64_t *in_idx, const uint32_t *ksk, uint32_t n_in, uint32_t n_out,
                             uint32_t base_log, uint32_t level, uint32_t num_samples);
+// packing keyswitch (LWE list -> GLWEs, lwe_per_glwe LWEs each) with its fused rotate / sum / modulus switch / bit-pack
+// epilogue; rows: [num_lwes][(glwe_dim+1)*N] scratch, trivial: 0 .. num_lwes-1; storage_log_modulus 0 = unswitched GLWEs
+void launch_packing_keyswitch(hipStream_t st, uint64_t *out, uint64_t *rows, const uint64_t *trivial,
+                              const uint64_t *lwe_in, const uint64_t *pksk, uint32_t n_in, uint32_t glwe_dim, uint32_t N,
+                              uint32_t base_log, uint32_t level, uint32_t num_lwes, uint32_t lwe_per_glwe,
+                              uint32_t storage_log_modulus);
 
 // cache of the matrix-core key layout (keyswitch.hip): drop what overlaps device memory about to be freed / written
 void ksm_invalidate_range(int device, const void *p, size_t bytes);
@@ -97,6 +103,13 @@ void launch_sample_extract(hipStream_t st, uint64_t *lwe_out, const uint64_t *gl
                            uint32_t num_nths, uint32_t lwe_per_glwe, uint32_t stored_per_glwe, uint32_t glwe_dim,
                            uint32_t N);
 void launch_closest_representable(hipStream_t st, const uint64_t *in, uint64_t *out, uint32_t base_log, uint32_t level);
+// compressed GLWE lists (values of `bits` bits packed least significant first, words_per_glwe words per GLWE): the LWEs
+// at `indexes` (device array) extracted straight from the packed words; one GLWE unpacked, body tail zeroed
+void launch_unpack_extract(hipStream_t st, uint64_t *lwe_out, const uint64_t *packed, const uint32_t *indexes,
+                           uint32_t count, uint32_t k, uint32_t N, uint32_t lwe_per_glwe, uint32_t bits,
+                           uint32_t words_per_glwe);
+void launch_unpack_glwe(hipStream_t st, uint64_t *glwe_out, const uint64_t *words, uint32_t k, uint32_t N, uint32_t bodies,
+                        uint32_t bits);
 
 // multi-bit — multibit.hip
 struct MultiBitArgs {

@@ -1010,6 +1010,86 @@ void launch_keyswitch(hipStream_t st, uint64_t *lwe_out, const uint64_t *out_idx
   }
 }
 
+// ------------------------------------------------------------------ packing keyswitch: LWE list -> GLWE
+// cc/algorithms/lwe_packing_keyswitch.rs:102-187 (one LWE into a GLWE), :296-379 (a list: out = sum_i X^i * G_i).
+// Replaces backends/tfhe-cuda-backend/cuda/src/crypto/packing_keyswitch.cuh + the five launches of
+// cuda/src/integer/compression/compression.cuh:199-291 (memset, negate-and-rotate, accumulate, strided modulus switch,
+// pack).  A packing key [n_in][level][(k+1)*N] is, word for word, an LWE keyswitch key with (k+1)*N columns, so G_i is
+// what launch_keyswitch computes with n_out = (k+1)*N - 1, except for where the input body lands: launch_keyswitch adds
+// b_i to the LAST column, the packing keyswitch wants it at coefficient 0 of the body polynomial (column k*N).  The
+// epilogue below moves it while it reads the rows (two compares per load), so the keyswitch kernels stay as they are.
+//
+// pks_rotate_pack_kernel: one workgroup per 64 consecutive output values of one GLWE.  Value v of the GLWE (polynomial
+// q = v / N, coefficient p = v % N) is  sum_i  +-G_i[q][(p - i) mod N]  (minus where p < i: the monic monomial X^i,
+// negacyclic); the four waves take every fourth LWE and add their shares through LDS (wrapping integer sums: any order
+// gives the same words).  Then, storage_log_modulus = s > 0: the values are switched to s bits
+// ((x + 2^(63-s)) >> (64-s)) and the 64 of them are packed, least significant first, into exactly s output words (64
+// values * s bits: workgroups never share a word) — the layout of PackedIntegers
+// (cc/entities/compressed_modulus_switched_glwe_ciphertext.rs:171-250); values past `nvals` count as zero and words
+// past `words_per_glwe` are not written.  s = 0: the 64 raw words are stored (the unswitched GLWE).
+// The rows of a chunk (up to N * (k+1)*N words: 2.6 MB at k = 4, N = 256) were just written by the GEMM: L2 hits.
+__global__ void __launch_bounds__(256) pks_rotate_pack_kernel(uint64_t *out, const uint64_t *rows, const uint64_t *lwe_in,
+                                                              uint32_t n_in, uint32_t k, uint32_t N, uint32_t num_lwes,
+                                                              uint32_t lwe_per_glwe, uint32_t nvals, uint32_t s,
+                                                              uint32_t words_per_glwe) {
+  __shared__ uint64_t part[4][64];
+  const uint32_t c = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  const uint32_t glwe = blockIdx.y, v = blockIdx.x * 64 + c;
+  const uint32_t ncols = (k + 1) * N, first = glwe * lwe_per_glwe;
+  const uint32_t m = num_lwes - first < lwe_per_glwe ? num_lwes - first : lwe_per_glwe;  // LWEs of this GLWE
+  uint64_t acc = 0;
+  if (v < nvals) {
+    const uint32_t q = v / N, p = v - q * N;
+    for (uint32_t i = sl; i < m; i += 4) {
+      const uint32_t idx = (p - i) & (N - 1), col = q * N + idx;
+      uint64_t g = rows[(size_t)(first + i) * ncols + col];
+      if (q == k && (idx == 0 || col == ncols - 1)) {  // the body: out of the last column, into coefficient 0
+        const uint64_t b = lwe_in[(size_t)(first + i) * (n_in + 1) + n_in];
+        g = idx == 0 ? g + b : g - b;
+      }
+      acc += p >= i ? g : (uint64_t)0 - g;
+    }
+  }
+  part[sl][c] = acc;
+  __syncthreads();
+  if (sl == 0) {
+    const uint64_t x = part[0][c] + part[1][c] + part[2][c] + part[3][c];
+    if (s == 0) {
+      if (v < nvals) out[(size_t)glwe * ncols + v] = x;
+    } else {
+      part[0][c] = v < nvals ? modulus_switch(x, s) : 0;
+    }
+  }
+  if (s == 0) return;
+  __syncthreads();
+  const uint32_t j = threadIdx.x, w = blockIdx.x * s + j;  // word j of this workgroup's s words
+  if (j < s && w < words_per_glwe) {
+    const uint32_t t_lo = (64 * j) / s, t_hi = (64 * j + 63) / s < 63 ? (64 * j + 63) / s : 63;
+    uint64_t word = 0;
+    for (uint32_t t = t_lo; t <= t_hi; ++t) {
+      const int sh = (int)(t * s) - (int)(64 * j);
+      word |= sh >= 0 ? part[0][t] << sh : part[0][t] >> (-sh);
+    }
+    out[(size_t)glwe * words_per_glwe + w] = word;
+  }
+}
+
+// num_lwes LWEs in chunks of lwe_per_glwe -> ceil(num_lwes / lwe_per_glwe) GLWEs; rows: [num_lwes][(k+1)*N] scratch,
+// trivial: 0, 1, ..., num_lwes - 1.  storage_log_modulus 0: `out` receives the GLWEs as they are ((k+1)*N words each);
+// otherwise their first k*N + lwe_per_glwe values switched to that many bits and packed, ceil(that * bits / 64) words each.
+void launch_packing_keyswitch(hipStream_t st, uint64_t *out, uint64_t *rows, const uint64_t *trivial,
+                              const uint64_t *lwe_in, const uint64_t *pksk, uint32_t n_in, uint32_t glwe_dim, uint32_t N,
+                              uint32_t base_log, uint32_t level, uint32_t num_lwes, uint32_t lwe_per_glwe,
+                              uint32_t storage_log_modulus) {
+  if (num_lwes == 0) return;
+  const uint32_t ncols = (glwe_dim + 1) * N, glwes = (num_lwes + lwe_per_glwe - 1) / lwe_per_glwe;
+  launch_keyswitch(st, rows, trivial, lwe_in, trivial, pksk, n_in, ncols - 1, base_log, level, num_lwes);
+  const uint32_t s = storage_log_modulus, nvals = s ? glwe_dim * N + lwe_per_glwe : ncols;
+  const uint32_t words = s ? (uint32_t)(((uint64_t)nvals * s + 63) / 64) : ncols;
+  HX_LAUNCH(pks_rotate_pack_kernel, dim3((nvals + 63) / 64, glwes), dim3(256), 0, st, out, (const uint64_t *)rows, lwe_in,
+            n_in, glwe_dim, N, num_lwes, lwe_per_glwe, nvals, s, words);
+}
+
 void launch_keyswitch_64_32(hipStream_t st, uint32_t *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
                             const uint64_t *in_idx, const uint32_t *ksk, uint32_t n_in, uint32_t n_out,
                             uint32_t base_log, uint32_t level, uint32_t num_samples) {

@@ -198,6 +198,21 @@ SIGNATURES = {
     "scratch_cuda_logical_scalar_shift_64_inplace_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _b, _u32]),
     "cuda_logical_scalar_shift_64_inplace_async": (None, [_S, _R, _u32, _v, _i8pp, _i8pp]),
     "cleanup_cuda_logical_scalar_shift_64_inplace": (None, [_S, _i8pp]),
+    # ciphertext compression
+    "hip_scratch_packing_keyswitch_lwe_list_to_glwe_64_async": (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _b]),
+    "hip_packing_keyswitch_lwe_list_to_glwe_64_async":
+        (None, [_S, _v, _v, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "hip_cleanup_packing_keyswitch_lwe_list_to_glwe_64": (None, [_S, _i8pp]),
+    "hip_scratch_integer_compress_radix_ciphertext_64_async":
+        (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _b]),
+    "hip_integer_compress_radix_ciphertext_64_async": (None, [_S, _v, _R, _i8pp, _v]),
+    "hip_cleanup_integer_compress_radix_ciphertext_64": (None, [_S, _i8pp]),
+    "hip_scratch_integer_decompress_radix_ciphertext_64_async":
+        (_u64, [_S, _i8pp, _BK, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_decompress_radix_ciphertext_64_async": (None, [_S, _R, _v, _u32, C.POINTER(C.c_uint32), _u32, _i8pp, _v]),
+    "hip_cleanup_integer_decompress_radix_ciphertext_64": (None, [_S, _i8pp]),
+    "hip_integer_extract_glwe_64_async": (None, [_S, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "hip_integer_compressed_size_words": (_u64, [_u32, _u32, _u32, _u32, _u32]),
     "hip_integer_scratch_batch": (None, [_u32]),
     "hip_integer_mult_pbs_count": (_u64, [_v]),
     "hip_integer_propagate_pbs_count": (_u64, [_u32]),

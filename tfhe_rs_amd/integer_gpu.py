@@ -431,3 +431,154 @@ class CudaUnsignedRadixCiphertext:
         return ffi.CudaRadixCiphertextFFI(self.d_blocks.ptr, deg.ctypes.data_as(C.POINTER(C.c_uint64)),
                                           noise.ctypes.data_as(C.POINTER(C.c_uint64)), self.total_blocks,
                                           self.total_blocks, self.lwe_dimension)
+
+
+# ---------------------------------------------------------------------------------------------- ciphertext compression
+# integer/gpu/list_compression/server_keys.rs (CudaCompressionKey, CudaDecompressionKey) and
+# integer/gpu/ciphertext/compressed_ciphertext_list.rs (CudaCompressedCiphertextList), over the hip_ entry points of
+# include/tfhe_hip_backend.h, "ciphertext compression".
+class CudaCompressionKey:
+    """server_keys.rs: the packing keyswitch key (big compute key -> compression GLWE key) and how a GLWE is stored."""
+
+    def __init__(self, packing_key_switching_key, lwe_per_glwe, storage_log_modulus, message_modulus, carry_modulus):
+        self.packing_key_switching_key = packing_key_switching_key
+        self.lwe_per_glwe, self.storage_log_modulus = int(lwe_per_glwe), int(storage_log_modulus)
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+        assert 1 <= self.lwe_per_glwe <= packing_key_switching_key.output_polynomial_size, \
+            "Cannot pack more than polynomial_size elements per glwe"
+
+    def compress_ciphertexts_into_list(self, ciphertexts, streams):
+        """`ciphertexts`: radix ciphertexts (one integer each, any widths) with empty carries.  Their blocks are laid
+        end to end, multiplied by message_modulus, packed lwe_per_glwe per GLWE, modulus switched and bit-packed."""
+        k = self.packing_key_switching_key
+        counts = []
+        for ct in ciphertexts:
+            assert ct.num_integers == 1, "one integer per list entry"
+            assert ct.lwe_dimension == k.input_key_lwe_dimension, \
+                "All ciphertexts do not have the same lwe size as the packing keyswitch key"
+            if int(ct.degrees.max(initial=0)) > self.message_modulus - 1:
+                raise ValueError("Ciphertexts must have empty carries to be compressed")
+            counts.append(ct.total_blocks)
+        total = sum(counts)
+        assert total >= 1, "nothing to compress"
+        w = k.input_key_lwe_dimension + 1
+        s, keep = CudaServerKey._streams(streams)
+        flat = CudaUnsignedRadixCiphertext(CudaVec(total * w, streams), 1, total, k.input_key_lwe_dimension)
+        at = 0
+        for ct, c in zip(ciphertexts, counts):
+            _lib().cuda_memcpy_async_gpu_to_gpu(flat.d_blocks.ptr + at * w * 8, ct.d_blocks.ptr, c * w * 8, streams.ptr[0],
+                                                streams.gpu_indexes[0])
+            flat.degrees[at:at + c] = ct.degrees
+            at += c
+        words = int(_lib().hip_integer_compressed_size_words(k.output_glwe_dimension, k.output_polynomial_size,
+                                                             self.lwe_per_glwe, self.storage_log_modulus, total))
+        packed = CudaVec(words, streams)
+        mem = C.c_void_p()
+        keys = (C.c_void_p * 1)(k.d_vec.ptr)
+        _lib().hip_scratch_integer_compress_radix_ciphertext_64_async(
+            s, C.byref(mem), k.input_key_lwe_dimension, k.output_glwe_dimension, k.output_polynomial_size,
+            k.decomp_base_log, k.decomp_level_count, total, self.message_modulus, self.carry_modulus, self.lwe_per_glwe,
+            self.storage_log_modulus, True)
+        _lib().hip_integer_compress_radix_ciphertext_64_async(s, packed.ptr, C.byref(flat._ffi()), keys, mem)
+        _lib().hip_cleanup_integer_compress_radix_ciphertext_64(s, C.byref(mem))
+        return CudaCompressedCiphertextList(packed, counts, k.output_glwe_dimension, k.output_polynomial_size,
+                                            self.lwe_per_glwe, self.storage_log_modulus, self.message_modulus,
+                                            self.carry_modulus)
+
+
+class CudaDecompressionKey:
+    """server_keys.rs: the bootstrap key from the (flattened) compression GLWE key to the compute GLWE key — a
+    CudaLweBootstrapKey or CudaLweMultiBitBootstrapKey whose input dimension is glwe_dimension * polynomial_size of the
+    compression GLWE."""
+
+    def __init__(self, blind_rotate_key, message_modulus, carry_modulus):
+        self.blind_rotate_key = blind_rotate_key
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+
+    def _bsk_params(self):
+        b = self.blind_rotate_key
+        g = getattr(b, "grouping_factor", 0)
+        return ffi.CudaLweBootstrapKeyParamsFFI(b.input_lwe_dimension, b.glwe_dimension, b.polynomial_size,
+                                                b.decomp_base_log, b.decomp_level_count, b.output_lwe_dimension,
+                                                PBS_TYPE_MULTI_BIT if g else PBS_TYPE_CLASSICAL, g)
+
+    def unpack_indexes(self, packed, indexes, streams):
+        """The blocks at `indexes` of the packed list (non-decreasing in GLWE index), decompressed: one integer of
+        len(indexes) clean blocks under the big compute key."""
+        b = self.blind_rotate_key
+        assert b.input_lwe_dimension == packed.glwe_dimension * packed.polynomial_size, \
+            "decompression key and compressed list do not have the same compression GLWE"
+        assert (packed.message_modulus, packed.carry_modulus) == (self.message_modulus, self.carry_modulus)
+        idx = np.ascontiguousarray(indexes, dtype=np.uint32)
+        s, keep = CudaServerKey._streams(streams)
+        out = CudaUnsignedRadixCiphertext(CudaVec(idx.size * (b.output_lwe_dimension + 1), streams), 1, idx.size,
+                                          b.output_lwe_dimension)
+        mem = C.c_void_p()
+        keys = (C.c_void_p * 1)(b.d_vec.ptr)
+        _lib().hip_scratch_integer_decompress_radix_ciphertext_64_async(
+            s, C.byref(mem), self._bsk_params(), packed.glwe_dimension, packed.polynomial_size, packed.lwe_per_glwe,
+            packed.storage_log_modulus, idx.size, self.message_modulus, self.carry_modulus, True,
+            1 if getattr(b, "ms_noise_reduction", False) else 0)
+        _lib().hip_integer_decompress_radix_ciphertext_64_async(
+            s, C.byref(out._ffi()), packed.d_packed.ptr, packed.total_blocks, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+            idx.size, keys, mem)
+        _lib().hip_cleanup_integer_decompress_radix_ciphertext_64(s, C.byref(mem))   # synchronises: idx may go
+        return out
+
+    def unpack(self, packed, start_block, end_block, streams):
+        """server_keys.rs unpack: blocks [start_block, end_block) of the list as one radix ciphertext."""
+        return self.unpack_indexes(packed, np.arange(start_block, end_block), streams)
+
+
+class CudaCompressedCiphertextList:
+    """The packed words on the device plus what unpacking needs: how many blocks every entry has, the compression GLWE
+    shape, lwe_per_glwe, storage_log_modulus and the moduli (CompressedCiphertextListMeta, compression.rs:121-127)."""
+
+    def __init__(self, d_packed, block_counts, glwe_dimension, polynomial_size, lwe_per_glwe, storage_log_modulus,
+                 message_modulus, carry_modulus):
+        self.d_packed = d_packed
+        self.block_counts = [int(c) for c in block_counts]
+        self.glwe_dimension, self.polynomial_size = int(glwe_dimension), int(polynomial_size)
+        self.lwe_per_glwe, self.storage_log_modulus = int(lwe_per_glwe), int(storage_log_modulus)
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+
+    @classmethod
+    def compress(cls, ciphertexts, compression_key, streams):
+        return compression_key.compress_ciphertexts_into_list(ciphertexts, streams)
+
+    @property
+    def total_blocks(self):
+        return sum(self.block_counts)
+
+    def __len__(self):
+        return len(self.block_counts)
+
+    def get(self, i, decompression_key, streams):
+        """Entry i as a radix ciphertext (compressed_ciphertext_list.rs get)."""
+        if not 0 <= i < len(self):
+            raise IndexError(f"Tried getting index {i} for CudaCompressedCiphertextList with {len(self)} elements")
+        start = sum(self.block_counts[:i])
+        return decompression_key.unpack(self, start, start + self.block_counts[i], streams)
+
+    def size_bytes(self):
+        return 8 * self.d_packed.len
+
+    def metadata(self):
+        return {"block_counts": list(self.block_counts), "glwe_dimension": self.glwe_dimension,
+                "polynomial_size": self.polynomial_size, "lwe_per_glwe": self.lwe_per_glwe,
+                "storage_log_modulus": self.storage_log_modulus, "message_modulus": self.message_modulus,
+                "carry_modulus": self.carry_modulus}
+
+    def to_host(self, streams):
+        """(packed u64 words, metadata dict)"""
+        return self.d_packed.copy_to_cpu(streams), self.metadata()
+
+    @classmethod
+    def from_host(cls, words, metadata, streams):
+        words = np.ascontiguousarray(words, dtype=U64)
+        m = metadata
+        want = int(_lib().hip_integer_compressed_size_words(m["glwe_dimension"], m["polynomial_size"], m["lwe_per_glwe"],
+                                                            m["storage_log_modulus"], sum(m["block_counts"])))
+        assert words.size == want, "packed words do not have the size the metadata describes"
+        return cls(CudaVec.from_cpu_async(words, streams), m["block_counts"], m["glwe_dimension"], m["polynomial_size"],
+                   m["lwe_per_glwe"], m["storage_log_modulus"], m["message_modulus"], m["carry_modulus"])
