@@ -678,6 +678,69 @@ uint64_t hip_integer_compressed_size_words(
     uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
     uint32_t total_blocks);
 
+/* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
+ * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's
+ * cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103 and cuda/include/fft/fft128.h), under hip_ names
+ * with the reference's parameter lists.  The reference-named *_128 / *_f128 symbols remain link stubs.
+ *
+ * Key: src is the standard-domain u128 key on the HOST in the reference's container order
+ * [input_lwe_dim][level][glwe_dim + 1][glwe_dim + 1][polynomial_size]; dest takes 32 * polynomial_size / 2 bytes per
+ * polynomial (four planes of doubles: re_hi, re_lo, im_hi, im_lo), i.e. as many bytes as the source.
+ * Bootstrap: lwe_array_in holds num_samples contiguous u64 LWEs of dimension lwe_dimension, lut_vector ONE u128 GLWE,
+ * lwe_array_out receives num_samples contiguous u128 LWEs of dimension glwe_dimension * polynomial_size.  One launch,
+ * one workgroup per input, no synchronisation between workgroups.  polynomial_size 256 .. 4096 (glwe_dimension up to 3
+ * below 2048, 2 at 2048, 1 at 4096), base_log <= 64, base_log * level_count <= 128.
+ * Panics: an unsupported size, an invalid decomposition, a scratch of another kind or other sizes, more samples than
+ * the scratch holds, a key that hip_convert_lwe_programmable_bootstrap_key_128_async converted for other sizes. */
+void hip_convert_lwe_programmable_bootstrap_key_128_async(
+    void *stream, uint32_t gpu_index, void *dest, void const *src, uint32_t input_lwe_dim, uint32_t glwe_dim,
+    uint32_t level_count, uint32_t polynomial_size);
+uint64_t hip_scratch_programmable_bootstrap_128_async(
+    void *stream, uint32_t gpu_index, int8_t **buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t level_count, uint32_t input_lwe_ciphertext_count, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_programmable_bootstrap_128_async(
+    void *stream, uint32_t gpu_index, void *lwe_array_out, void const *lut_vector, void const *lwe_array_in,
+    void const *bootstrapping_key, int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t base_log, uint32_t level_count, uint32_t num_samples);
+void hip_cleanup_programmable_bootstrap_128(void *stream, uint32_t gpu_index, int8_t **pbs_buffer);
+/* The negacyclic f128 transform of number_of_samples polynomials of N u128 coefficients: planes re0 (high doubles of the
+ * real parts), re1 (low), im0, im1 of N / 2 doubles per polynomial, in this library's transform order.
+ * "as torus": words read as signed, scaled by 2^-128; "as integer": unscaled; backward: normalised, reduced modulo 1. */
+void hip_fourier_transform_forward_as_torus_f128_async(
+    void *stream, uint32_t gpu_index, void *re0, void *re1, void *im0, void *im1, void const *standard, uint32_t const N,
+    const uint32_t number_of_samples);
+void hip_fourier_transform_forward_as_integer_f128_async(
+    void *stream, uint32_t gpu_index, void *re0, void *re1, void *im0, void *im1, void const *standard, uint32_t const N,
+    const uint32_t number_of_samples);
+void hip_fourier_transform_backward_as_torus_f128_async(
+    void *stream, uint32_t gpu_index, void *standard, void const *re0, void const *re1, void const *im0, void const *im1,
+    uint32_t const N, const uint32_t number_of_samples);
+/* Noise squashing of a radix ciphertext (integer.cuh:2776-2840): the ceil(blocks / 2) output blocks are u128 LWEs under
+ * the squashing key's output key; block i is  in[2i] + message_modulus * in[2i + 1]  (clean inputs), keyswitched with
+ * ksks[0] and bootstrapped with the 128-bit key bsks[0] and the identity table (delta = 2^127 / (message_modulus *
+ * carry_modulus)).  lwe_dimension: the small key's; glwe_dimension x polynomial_size: the squashing ring; input_*: the
+ * compute ring; num_radix_blocks: OUTPUT blocks; num_original_blocks: input blocks.  One GPU (entry 0 of `streams`).
+ * Panics: an output block count other than ceil(input / 2), a block with a carry, other lwe dimensions. */
+uint64_t hip_scratch_integer_apply_noise_squashing_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+    uint32_t input_glwe_dimension, uint32_t input_polynomial_size, uint32_t ks_level, uint32_t ks_base_log,
+    uint32_t pbs_level, uint32_t pbs_base_log, uint32_t num_radix_blocks, uint32_t num_original_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_apply_noise_squashing_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out, CudaRadixCiphertextFFI const *lwe_array_in,
+    int8_t *mem_ptr, void *const *ksks, void *const *bsks);
+void hip_cleanup_integer_apply_noise_squashing_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* test hooks of the 128-bit path: the host-built double-double tables (four doubles per entry: re_hi, re_lo, im_hi,
+ * im_lo; polynomial_size / 2 entries per table, indexed like hip_test_fft_tables_host's); the u128 signed decomposer
+ * (level_count digits per word, least significant first, as i128); the kernels' own complex f128 product of `count`
+ * points (each operand: four planes of count doubles) */
+void hip_test_fft128_tables_host(uint32_t polynomial_size, double *fwd, double *inv, double *untwist);
+void hip_test_decompose_128_async(void *stream, uint32_t gpu_index, void const *in, void *out, uint32_t count,
+                                  uint32_t base_log, uint32_t level_count);
+void hip_test_f128_cmul_async(void *stream, uint32_t gpu_index, void *out, void const *a, void const *b, uint32_t count);
+
 /* Select which f64 kernel serves cuda_programmable_bootstrap_64_async (all give identical bits):
  * 0 = automatic (N=2048,k=1: latency kernel up to 256 LWEs, throughput kernel beyond; N=1024,k<=2: its
  *     throughput kernel; generic otherwise),

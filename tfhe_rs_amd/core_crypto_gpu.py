@@ -13,6 +13,8 @@ the Rust module it mirrors:
   cuda_multi_bit_programmable_bootstrap_lwe_ciphertext gpu/algorithms/lwe_multi_bit_programmable_bootstrapping.rs:10-145
   cuda_keyswitch_lwe_ciphertext                        gpu/algorithms/lwe_keyswitch.rs:12-143
   cuda_extract_lwe_samples_from_glwe_ciphertext_list   gpu/algorithms/glwe_sample_extraction.rs:12
+  CudaLweBootstrapKey128 / cuda_programmable_bootstrap_128_lwe_ciphertext   the u128 bootstrap of noise squashing
+  cuda_fourier_transform_{forward_as_torus,forward_as_integer,backward_as_torus}_f128   gpu/ffi.rs, fft/fft128.h
 The Rust original is the reference's host language; no Rust toolchain exists in this image,
 so the mirror is Python (INTEGRATION.md shows the Rust binding a maintainer would add).
 numpy arrays are the "CPU containers".
@@ -68,37 +70,42 @@ class CudaStreams:
 
 
 class CudaVec:
-    """Device array of one dtype on the GPU of streams[stream_index] (vec.rs)."""
+    """Device array of one dtype on the GPU of streams[stream_index] (vec.rs).  elem_words=2: elements of 16 bytes
+    (u128), which cross the Python boundary as uint64 pairs (lo, hi) in a trailing dimension of 2 — the memory image of
+    unsigned __int128 on both sides."""
 
-    def __init__(self, length, streams, stream_index=0, dtype=U64):
+    def __init__(self, length, streams, stream_index=0, dtype=U64, elem_words=1):
         self.len = int(length)
         self.dtype = np.dtype(dtype)
+        self.elem_words = int(elem_words)
+        assert self.elem_words in (1, 2) and (self.elem_words == 1 or self.dtype == U64)
         self.gpu_index = streams.gpu_indexes[stream_index]
-        nbytes = max(self.len * self.dtype.itemsize, 8)
+        nbytes = max(self.len * self.dtype.itemsize * self.elem_words, 8)
         self.ptr = _lib().cuda_malloc(nbytes, self.gpu_index)
         _lib().cuda_memset_async(self.ptr, 0, nbytes, streams.ptr[stream_index], self.gpu_index)
 
     @classmethod
-    def from_cpu_async(cls, src, streams, stream_index=0):
+    def from_cpu_async(cls, src, streams, stream_index=0, elem_words=1):
         src = np.ascontiguousarray(src)
-        v = cls(src.size, streams, stream_index, src.dtype)
+        assert elem_words == 1 or src.shape[-1] == 2, "u128 arrays are uint64 arrays with a trailing dimension of 2"
+        v = cls(src.size // elem_words, streams, stream_index, src.dtype, elem_words)
         v.copy_from_cpu_async(src, streams, stream_index)
         return v
 
     def copy_from_cpu_async(self, src, streams, stream_index=0):
         src = np.ascontiguousarray(src, dtype=self.dtype)
-        assert src.size <= self.len, "CudaVec: source larger than the device vector"
+        assert src.size <= self.len * self.elem_words, "CudaVec: source larger than the device vector"
         _lib().cuda_memcpy_async_to_gpu(self.ptr, src.ctypes.data_as(C.c_void_p), src.nbytes,
                                         streams.ptr[stream_index], self.gpu_index)
         # the source is pageable host memory: keep it alive until the stream is drained
         streams.synchronize_one(stream_index)
 
     def copy_to_cpu(self, streams, stream_index=0):
-        out = np.empty(self.len, dtype=self.dtype)
+        out = np.empty(self.len * self.elem_words, dtype=self.dtype)
         _lib().cuda_memcpy_async_to_cpu(out.ctypes.data_as(C.c_void_p), self.ptr, out.nbytes,
                                         streams.ptr[stream_index], self.gpu_index)
         streams.synchronize_one(stream_index)
-        return out
+        return out.reshape(-1, 2) if self.elem_words == 2 else out
 
     def drop(self):
         if self.ptr:
@@ -119,19 +126,26 @@ class CudaLweCiphertextList:
         self.lwe_dimension = int(lwe_dimension)
 
     @classmethod
-    def new(cls, lwe_dimension, lwe_ciphertext_count, streams, dtype=U64):
-        """dtype=np.uint32: the 32-bit ciphertexts a u32 keyswitch key produces (KS32 pattern)."""
-        return cls(CudaVec((lwe_dimension + 1) * lwe_ciphertext_count, streams, dtype=dtype), lwe_ciphertext_count,
-                   lwe_dimension)
+    def new(cls, lwe_dimension, lwe_ciphertext_count, streams, dtype=U64, elem_words=1):
+        """dtype=np.uint32: the 32-bit ciphertexts a u32 keyswitch key produces (KS32 pattern); elem_words=2: u128."""
+        return cls(CudaVec((lwe_dimension + 1) * lwe_ciphertext_count, streams, dtype=dtype, elem_words=elem_words),
+                   lwe_ciphertext_count, lwe_dimension)
 
     @classmethod
     def from_lwe_ciphertext_list(cls, h_ct, streams):
+        """[count][lwe_size] u64 words, or [count][lwe_size][2] for u128 ciphertexts"""
         h_ct = np.ascontiguousarray(h_ct, dtype=U64)
+        if h_ct.ndim == 3:
+            assert h_ct.shape[2] == 2, "expected [count][lwe_size][2]"
+            return cls(CudaVec.from_cpu_async(h_ct.reshape(-1, 2), streams, elem_words=2), h_ct.shape[0], h_ct.shape[1] - 1)
         assert h_ct.ndim == 2, "expected [count][lwe_size]"
         return cls(CudaVec.from_cpu_async(h_ct.reshape(-1), streams), h_ct.shape[0], h_ct.shape[1] - 1)
 
     def to_lwe_ciphertext_list(self, streams):
-        return self.d_vec.copy_to_cpu(streams).reshape(self.lwe_ciphertext_count, self.lwe_dimension + 1)
+        flat = self.d_vec.copy_to_cpu(streams)
+        if self.d_vec.elem_words == 2:
+            return flat.reshape(self.lwe_ciphertext_count, self.lwe_dimension + 1, 2)
+        return flat.reshape(self.lwe_ciphertext_count, self.lwe_dimension + 1)
 
 
 class CudaGlweCiphertextList:
@@ -142,13 +156,18 @@ class CudaGlweCiphertextList:
         self.polynomial_size = int(polynomial_size)
 
     @classmethod
-    def from_glwe_ciphertext_list(cls, h_ct, glwe_dimension, polynomial_size, streams):
-        h_ct = np.ascontiguousarray(h_ct, dtype=U64).reshape(-1, (glwe_dimension + 1) * polynomial_size)
-        return cls(CudaVec.from_cpu_async(h_ct.reshape(-1), streams), h_ct.shape[0], glwe_dimension,
+    def from_glwe_ciphertext_list(cls, h_ct, glwe_dimension, polynomial_size, streams, elem_words=1):
+        """elem_words=2: u128 GLWEs, h_ct of shape [..., 2]"""
+        h_ct = np.ascontiguousarray(h_ct, dtype=U64).reshape(-1, (glwe_dimension + 1) * polynomial_size * elem_words)
+        flat = h_ct.reshape(-1, 2) if elem_words == 2 else h_ct.reshape(-1)
+        return cls(CudaVec.from_cpu_async(flat, streams, elem_words=elem_words), h_ct.shape[0], glwe_dimension,
                    polynomial_size)
 
     def to_glwe_ciphertext_list(self, streams):
-        return self.d_vec.copy_to_cpu(streams).reshape(self.glwe_ciphertext_count, -1)
+        flat = self.d_vec.copy_to_cpu(streams)
+        if self.d_vec.elem_words == 2:
+            return flat.reshape(self.glwe_ciphertext_count, -1, 2)
+        return flat.reshape(self.glwe_ciphertext_count, -1)
 
 
 class CudaLweBootstrapKey:
@@ -398,6 +417,100 @@ def cuda_multi_bit_programmable_bootstrap_lwe_ciphertext(input, output, accumula
         input_indexes.ptr, bsk.d_vec.ptr, buf, bsk.input_lwe_dimension, bsk.glwe_dimension, bsk.polynomial_size,
         bsk.grouping_factor, bsk.decomp_base_log, bsk.decomp_level_count, num_samples, num_many_lut, lut_stride)
     lib.cleanup_cuda_multi_bit_programmable_bootstrap_64(s, g, C.byref(buf))
+
+
+class CudaLweBootstrapKey128:
+    """gpu/entities/lwe_bootstrap_key.rs (the u128 key of noise squashing): the standard-domain key, [n][level][k + 1]
+    [k + 1][N] u128 words given as uint64 pairs, converted once per GPU of `streams` to the f128 Fourier domain."""
+
+    @classmethod
+    def from_lwe_bootstrap_key(cls, h_bsk, input_lwe_dimension, glwe_dimension, polynomial_size, decomp_base_log,
+                               decomp_level_count, streams, ms_noise_reduction=False):
+        self = cls()
+        self.input_lwe_dimension = int(input_lwe_dimension)
+        self.glwe_dimension = int(glwe_dimension)
+        self.polynomial_size = int(polynomial_size)
+        self.decomp_base_log = int(decomp_base_log)
+        self.decomp_level_count = int(decomp_level_count)
+        self.ms_noise_reduction = bool(ms_noise_reduction)
+        h_bsk = np.ascontiguousarray(h_bsk, dtype=U64)
+        elems = self.input_lwe_dimension * (glwe_dimension + 1) ** 2 * decomp_level_count * polynomial_size
+        assert h_bsk.size == 2 * elems and h_bsk.shape[-1] == 2, "bootstrap key container has the wrong size"
+        self.d_vecs = []
+        for i in range(len(streams)):
+            d = CudaVec(2 * elems, streams, i, np.float64)  # 32 * N / 2 bytes per polynomial
+            _lib().hip_convert_lwe_programmable_bootstrap_key_128_async(
+                streams.ptr[i], streams.gpu_indexes[i], d.ptr, h_bsk.ctypes.data_as(C.c_void_p),
+                self.input_lwe_dimension, glwe_dimension, decomp_level_count, polynomial_size)
+            self.d_vecs.append(d)
+        streams.synchronize()
+        self.d_vec = self.d_vecs[0]
+        return self
+
+    @property
+    def output_lwe_dimension(self):
+        return self.glwe_dimension * self.polynomial_size
+
+
+def cuda_programmable_bootstrap_128_lwe_ciphertext(input, output, accumulator, bsk, streams):
+    """gpu/algorithms/lwe_programmable_bootstrapping.rs (cuda_programmable_bootstrap_128_lwe_ciphertext): u64 inputs, one
+    u128 accumulator, u128 outputs (scratch -> launch -> cleanup on streams.ptr[0])."""
+    assert input.lwe_dimension == bsk.input_lwe_dimension, (
+        f"Mismatched input LweDimension. LweCiphertext input LweDimension {input.lwe_dimension}. "
+        f"BootstrapKey input LweDimension {bsk.input_lwe_dimension}.")
+    assert output.lwe_dimension == bsk.output_lwe_dimension, (
+        f"Mismatched output LweDimension. LweCiphertext output LweDimension {output.lwe_dimension}. "
+        f"BootstrapKey output LweDimension {bsk.output_lwe_dimension}.")
+    assert accumulator.glwe_dimension == bsk.glwe_dimension, "Mismatched GlweSize"
+    assert accumulator.polynomial_size == bsk.polynomial_size, "Mismatched PolynomialSize"
+    assert input.d_vec.elem_words == 1 and output.d_vec.elem_words == 2 and accumulator.d_vec.elem_words == 2, \
+        "the 128-bit bootstrap takes u64 inputs, a u128 accumulator and u128 outputs"
+    num_samples = input.lwe_ciphertext_count
+    assert output.lwe_ciphertext_count >= num_samples
+    lib = _lib()
+    buf = C.c_void_p()
+    s, g = streams.ptr[0], streams.gpu_indexes[0]
+    shape = (bsk.input_lwe_dimension, bsk.glwe_dimension, bsk.polynomial_size)
+    lib.hip_scratch_programmable_bootstrap_128_async(s, g, C.byref(buf), *shape, bsk.decomp_level_count, num_samples, True,
+                                                     1 if bsk.ms_noise_reduction else 0)
+    lib.hip_programmable_bootstrap_128_async(s, g, output.d_vec.ptr, accumulator.d_vec.ptr, input.d_vec.ptr, bsk.d_vec.ptr,
+                                             buf, *shape, bsk.decomp_base_log, bsk.decomp_level_count, num_samples)
+    lib.hip_cleanup_programmable_bootstrap_128(s, g, C.byref(buf))
+
+
+def _f128_planes(polynomial_size, number_of_samples, streams):
+    return [CudaVec(number_of_samples * polynomial_size // 2, streams, dtype=np.float64) for _ in range(4)]
+
+
+def cuda_fourier_transform_forward_as_torus_f128(standard, polynomial_size, number_of_samples, streams):
+    """gpu/ffi.rs (cuda_fourier_transform_forward_as_torus_f128_async): `standard` [samples][N][2] uint64 (u128 words);
+    returns the planes re0, re1, im0, im1 as four [samples][N / 2] float64 arrays."""
+    return _f128_forward(_lib().hip_fourier_transform_forward_as_torus_f128_async, standard, polynomial_size,
+                         number_of_samples, streams)
+
+
+def cuda_fourier_transform_forward_as_integer_f128(standard, polynomial_size, number_of_samples, streams):
+    return _f128_forward(_lib().hip_fourier_transform_forward_as_integer_f128_async, standard, polynomial_size,
+                         number_of_samples, streams)
+
+
+def _f128_forward(fn, standard, polynomial_size, number_of_samples, streams):
+    standard = np.ascontiguousarray(standard, dtype=U64)
+    assert standard.size == 2 * polynomial_size * number_of_samples
+    d_std = CudaVec.from_cpu_async(standard.reshape(-1, 2), streams, elem_words=2)
+    planes = _f128_planes(polynomial_size, number_of_samples, streams)
+    fn(streams.ptr[0], streams.gpu_indexes[0], *[p.ptr for p in planes], d_std.ptr, polynomial_size, number_of_samples)
+    return [p.copy_to_cpu(streams).reshape(number_of_samples, polynomial_size // 2) for p in planes]
+
+
+def cuda_fourier_transform_backward_as_torus_f128(re0, re1, im0, im1, polynomial_size, number_of_samples, streams):
+    """the inverse: four [samples][N / 2] float64 planes -> [samples][N][2] uint64 (u128 words)"""
+    planes = [CudaVec.from_cpu_async(np.ascontiguousarray(p, dtype=np.float64).reshape(-1), streams)
+              for p in (re0, re1, im0, im1)]
+    d_std = CudaVec(polynomial_size * number_of_samples, streams, elem_words=2)
+    _lib().hip_fourier_transform_backward_as_torus_f128_async(streams.ptr[0], streams.gpu_indexes[0], d_std.ptr,
+                                                              *[p.ptr for p in planes], polynomial_size, number_of_samples)
+    return d_std.copy_to_cpu(streams).reshape(number_of_samples, polynomial_size, 2)
 
 
 def cuda_keyswitch_lwe_ciphertext(ksk, input, output, input_indexes, output_indexes, uses_trivial_indices,

@@ -4,6 +4,7 @@
 #include "kernels.h"
 #include "arena.h"
 #include "profile.h"
+#include "pbs128.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -181,6 +182,7 @@ static const void *split_twin_of(int device, const void *split_key) {
 static void device_range_changes(int device, const void *p, size_t bytes) {
   ksm_invalidate_range(device, p, bytes);
   split_twin_forget_range(device, p, bytes);
+  key128_forget_range(device, p, bytes);
 }
 uint32_t cuda_is_available(void) { return hipSetDevice(0) == hipSuccess; }
 void *cuda_malloc(uint64_t size, uint32_t gpu_index) {
@@ -1198,6 +1200,159 @@ void cuda_backward_fft16x4x16_async(void *stream, uint32_t gpu_index, void const
 bool cuda_fft16x4x16_is_supported_async(uint32_t gpu_index) {
   set_device(gpu_index);
   return true;
+}
+
+// =========================================================================== 128-bit PBS (pbs128.h)
+// The reference's cuda_*_128 / *_f128 entry points under hip_ names, parameter lists unchanged
+// (cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103; cuda/include/fft/fft128.h).
+constexpr uint32_t kPbs128Magic = 0x50423238;  // "PB28"
+struct Pbs128Buffer {
+  uint32_t magic;
+  uint32_t lwe_dimension, glwe_dimension, polynomial_size, level_count, max_samples, ms_type;
+  bool gpu_memory_allocated;
+  Fft128Tables fft;
+  u128 *acc_scratch = nullptr;
+};
+void hip_convert_lwe_programmable_bootstrap_key_128_async(void *stream, uint32_t gpu_index, void *dest, void const *src,
+                                                          uint32_t input_lwe_dim, uint32_t glwe_dim, uint32_t level_count,
+                                                          uint32_t polynomial_size) {
+  set_device(gpu_index);
+  pbs128_check_poly(polynomial_size);
+  HX_PANIC_IF_FALSE(dest != nullptr && src != nullptr, "bootstrap key conversion: null pointer");
+  const size_t polys = (size_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1);
+  const size_t bytes = polys * polynomial_size * sizeof(u128);  // standard domain; the converted key takes as many
+  void *tmp = device_alloc_sync(bytes);
+  HX_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, S(stream)));
+  device_range_changes((int)gpu_index, dest, bytes);
+  launch_fft128_forward(S(stream), polynomial_size, (double *)dest, nullptr, nullptr, nullptr, (const u128 *)tmp, polys,
+                        get_fft128_tables(gpu_index, polynomial_size), 0, 1);
+  HX_CHECK(hipStreamSynchronize(S(stream)));  // the staging buffer must outlive the kernel
+  device_free_sync(tmp);
+  key128_record(Key128Record{(int)gpu_index, dest, bytes, input_lwe_dim, glwe_dim, level_count, polynomial_size});
+}
+uint64_t hip_scratch_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, int8_t **buffer,
+                                                      uint32_t lwe_dimension, uint32_t glwe_dimension,
+                                                      uint32_t polynomial_size, uint32_t level_count,
+                                                      uint32_t input_lwe_ciphertext_count, bool allocate_gpu_memory,
+                                                      enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  (void)stream;
+  set_device(gpu_index);
+  pbs128_check_poly(polynomial_size);
+  HX_PANIC_IF_FALSE(pbs128_supported(polynomial_size, glwe_dimension),
+                    "unsupported (polynomial_size=%u, glwe_dimension=%u) for the 128-bit PBS", polynomial_size, glwe_dimension);
+  HX_PANIC_IF_FALSE(level_count >= 1 && level_count <= 128, "invalid decomposition (level=%u)", level_count);
+  auto *b = new Pbs128Buffer();
+  b->magic = kPbs128Magic;
+  b->lwe_dimension = lwe_dimension;
+  b->glwe_dimension = glwe_dimension;
+  b->polynomial_size = polynomial_size;
+  b->level_count = level_count;
+  b->max_samples = input_lwe_ciphertext_count;
+  b->ms_type = (uint32_t)noise_reduction_type;
+  b->gpu_memory_allocated = allocate_gpu_memory;
+  // the accumulator stays on the chip wherever it fits next to the transform buffer; else one per sample in device memory
+  const uint64_t bytes = pbs128_needs_acc_scratch(polynomial_size, glwe_dimension)
+                             ? (uint64_t)input_lwe_ciphertext_count * (glwe_dimension + 1) * polynomial_size * sizeof(u128)
+                             : 0;
+  if (allocate_gpu_memory) {
+    b->fft = get_fft128_tables(gpu_index, polynomial_size);  // built here, so that the launch stays capture-safe
+    if (bytes) b->acc_scratch = (u128 *)scratch_alloc(bytes);
+  }
+  *buffer = reinterpret_cast<int8_t *>(b);
+  return bytes;
+}
+void hip_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void *lwe_array_out, void const *lut_vector,
+                                          void const *lwe_array_in, void const *bootstrapping_key, int8_t *buffer,
+                                          uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                          uint32_t base_log, uint32_t level_count, uint32_t num_samples) {
+  set_device(gpu_index);
+  auto *b = reinterpret_cast<Pbs128Buffer *>(buffer);
+  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kPbs128Magic,
+                    "PBS buffer was not created by hip_scratch_programmable_bootstrap_128_async");
+  HX_PANIC_IF_FALSE(b->gpu_memory_allocated, "PBS buffer was created with allocate_gpu_memory=false");
+  HX_PANIC_IF_FALSE(b->lwe_dimension == lwe_dimension && b->glwe_dimension == glwe_dimension &&
+                        b->polynomial_size == polynomial_size && b->level_count == level_count,
+                    "PBS buffer parameters do not match the call");
+  HX_PANIC_IF_FALSE(num_samples <= b->max_samples, "num_samples %u exceeds the scratch capacity %u", num_samples,
+                    b->max_samples);
+  HX_PANIC_IF_FALSE(base_log >= 1 && base_log <= 64 && (uint64_t)base_log * level_count <= 128,
+                    "invalid decomposition (base_log=%u, level=%u)", base_log, level_count);
+  Key128Record rec;
+  if (key128_find((int)gpu_index, bootstrapping_key, &rec))
+    HX_PANIC_IF_FALSE(rec.n == lwe_dimension && rec.glwe_dim == glwe_dimension && rec.level == level_count &&
+                          rec.N == polynomial_size,
+                      "the bootstrap key was converted for other sizes (n=%u, k=%u, level=%u, N=%u)", rec.n, rec.glwe_dim,
+                      rec.level, rec.N);
+  if (num_samples == 0) return;
+  HX_PANIC_IF_FALSE(lwe_array_out != nullptr && lut_vector != nullptr && lwe_array_in != nullptr && bootstrapping_key != nullptr,
+                    "128-bit PBS: null pointer");
+  Pbs128Args a;
+  a.lwe_out = (u128 *)lwe_array_out;
+  a.lut = (const u128 *)lut_vector;
+  a.lwe_in = (const uint64_t *)lwe_array_in;
+  a.bsk = (const double *)bootstrapping_key;
+  a.acc_scratch = b->acc_scratch;
+  a.n = lwe_dimension;
+  a.base_log = base_log;
+  a.level = level_count;
+  a.num_samples = num_samples;
+  a.ms_type = b->ms_type;
+  launch_pbs128(S(stream), polynomial_size, glwe_dimension, a, b->fft);
+}
+void hip_cleanup_programmable_bootstrap_128(void *stream, uint32_t gpu_index, int8_t **pbs_buffer) {
+  set_device(gpu_index);
+  auto *b = reinterpret_cast<Pbs128Buffer *>(*pbs_buffer);
+  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kPbs128Magic, "cleanup of a foreign 128-bit PBS buffer");
+  HX_CHECK(hipStreamSynchronize(S(stream)));
+  if (b->acc_scratch) scratch_free(b->acc_scratch);
+  b->magic = 0;
+  delete b;
+  *pbs_buffer = nullptr;
+}
+void hip_fourier_transform_forward_as_torus_f128_async(void *stream, uint32_t gpu_index, void *re0, void *re1, void *im0,
+                                                       void *im1, void const *standard, uint32_t const N,
+                                                       const uint32_t number_of_samples) {
+  set_device(gpu_index);
+  pbs128_check_poly(N);
+  launch_fft128_forward(S(stream), N, (double *)re0, (double *)re1, (double *)im0, (double *)im1, (const u128 *)standard,
+                        number_of_samples, get_fft128_tables(gpu_index, N), 0, 0);
+}
+void hip_fourier_transform_forward_as_integer_f128_async(void *stream, uint32_t gpu_index, void *re0, void *re1, void *im0,
+                                                         void *im1, void const *standard, uint32_t const N,
+                                                         const uint32_t number_of_samples) {
+  set_device(gpu_index);
+  pbs128_check_poly(N);
+  launch_fft128_forward(S(stream), N, (double *)re0, (double *)re1, (double *)im0, (double *)im1, (const u128 *)standard,
+                        number_of_samples, get_fft128_tables(gpu_index, N), 1, 0);
+}
+void hip_fourier_transform_backward_as_torus_f128_async(void *stream, uint32_t gpu_index, void *standard, void const *re0,
+                                                        void const *re1, void const *im0, void const *im1, uint32_t const N,
+                                                        const uint32_t number_of_samples) {
+  set_device(gpu_index);
+  pbs128_check_poly(N);
+  launch_fft128_backward(S(stream), N, (u128 *)standard, (const double *)re0, (const double *)re1, (const double *)im0,
+                         (const double *)im1, number_of_samples, get_fft128_tables(gpu_index, N));
+}
+// test hooks of the 128-bit path: the host tables (4 doubles per entry: re_hi, re_lo, im_hi, im_lo; N / 2 entries each),
+// the u128 decomposer (level digits per word, least significant first, as i128) and the kernels' complex f128 product
+void hip_test_fft128_tables_host(uint32_t polynomial_size, double *fwd, double *inv, double *untwist) {
+  pbs128_check_poly(polynomial_size);
+  fill_fft128_tables_host(polynomial_size, fwd, inv, untwist);
+}
+void hip_test_decompose_128_async(void *stream, uint32_t gpu_index, void const *in, void *out, uint32_t count,
+                                  uint32_t base_log, uint32_t level_count) {
+  set_device(gpu_index);
+  HX_PANIC_IF_FALSE(base_log >= 1 && base_log <= 64 && (uint64_t)base_log * level_count <= 128,
+                    "invalid decomposition (base_log=%u, level=%u)", base_log, level_count);
+  if (count == 0) return;
+  HX_LAUNCH(test_decompose128_kernel, dim3((count + 127) / 128), dim3(128), 0, S(stream), (const u128 *)in, (i128 *)out, count,
+            base_log, level_count);
+}
+void hip_test_f128_cmul_async(void *stream, uint32_t gpu_index, void *out, void const *a, void const *b, uint32_t count) {
+  set_device(gpu_index);
+  if (count == 0) return;
+  HX_LAUNCH(test_f128_cmul_kernel, dim3((count + 127) / 128), dim3(128), 0, S(stream), (double *)out, (const double *)a,
+            (const double *)b, count);
 }
 
 void hip_test_arith_async(void *stream, uint32_t gpu_index, uint32_t op, void const *in, void *out, uint32_t count,

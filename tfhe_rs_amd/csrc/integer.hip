@@ -1625,6 +1625,22 @@ static void generate_rescaling_lut(const Params &p, uint64_t *acc) {
   std::rotate(body, body + half, body + p.N);
 }
 
+// Noise squashing of a radix ciphertext (integer.cuh:2776-2840): pairs of clean blocks packed, keyswitched and
+// bootstrapped over the 128-bit torus with the identity table
+struct NoiseSquashMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x4E535131;  // "NSQ1"
+  uint32_t big_n = 0, small_n = 0, k = 0, N = 0, ks_base_log = 0, ks_level = 0, pbs_base_log = 0, pbs_level = 0;
+  uint32_t msg = 0, carry = 0, cap_in = 0, cap_out = 0, gpu = 0;
+  uint64_t *d_packed = nullptr, *d_after_ks = nullptr, *d_trivial = nullptr, *d_lo = nullptr, *d_hi = nullptr;
+  unsigned __int128 *d_lut = nullptr;
+  int8_t *pbs_buf = nullptr;
+  void release(const CudaStreamsFFI &s) {
+    if (pbs_buf) hip_cleanup_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
+    for (void *d : {(void *)d_packed, (void *)d_after_ks, (void *)d_trivial, (void *)d_lo, (void *)d_hi, (void *)d_lut})
+      if (d) scratch_free(d);
+  }
+};
+
 }  // namespace radix
 }  // namespace tfhe_hip
 
@@ -2777,6 +2793,88 @@ void hip_integer_extract_glwe_64_async(CudaStreamsFFI streams, void *glwe_out, v
   const uint32_t words = packed_words_per_glwe(glwe_dimension, polynomial_size, lwe_per_glwe, storage_log_modulus);
   launch_unpack_glwe(S0(streams), (uint64_t *)glwe_out, (const uint64_t *)packed_in + (size_t)glwe_index * words,
                      glwe_dimension, polynomial_size, bodies, storage_log_modulus);
+}
+
+// ---- noise squashing (integer.cuh:2776-2840; tfhe/src/integer/gpu/noise_squashing).  lwe_dimension: the small key's;
+// glwe_dimension x polynomial_size: the squashing key's output ring; input_*: the compute set's ring (the big key the
+// blocks are under).  num_radix_blocks: blocks of the OUTPUT (ceil(num_original_blocks / 2)).  One GPU.
+uint64_t hip_scratch_integer_apply_noise_squashing_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+    uint32_t input_glwe_dimension, uint32_t input_polynomial_size, uint32_t ks_level, uint32_t ks_base_log,
+    uint32_t pbs_level, uint32_t pbs_base_log, uint32_t num_radix_blocks, uint32_t num_original_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  HX_PANIC_IF_FALSE(num_radix_blocks == (num_original_blocks + 1) / 2,
+                    "apply_noise_squashing: num output radix blocks (%u) should be half ceil the number input radix blocks (%u)",
+                    num_radix_blocks, num_original_blocks);
+  HX_PANIC_IF_FALSE(message_modulus >= 2 && carry_modulus >= message_modulus,
+                    "apply_noise_squashing: two blocks are packed in one, so carry_modulus (=%u) must be at least "
+                    "message_modulus (=%u)", carry_modulus, message_modulus);
+  HX_PANIC_IF_FALSE(polynomial_size >= 2 * message_modulus * carry_modulus, "apply_noise_squashing: polynomial_size %u too small",
+                    polynomial_size);
+  return scratch_create<NoiseSquashMem>(streams, mem_ptr, allocate_gpu_memory, "apply_noise_squashing", [&](NoiseSquashMem &m) {
+    const hipStream_t st = S0(streams);
+    m.big_n = input_glwe_dimension * input_polynomial_size, m.small_n = lwe_dimension;
+    m.k = glwe_dimension, m.N = polynomial_size;
+    m.ks_base_log = ks_base_log, m.ks_level = ks_level, m.pbs_base_log = pbs_base_log, m.pbs_level = pbs_level;
+    m.msg = message_modulus, m.carry = carry_modulus;
+    m.cap_in = std::max(1u, num_original_blocks), m.cap_out = std::max(1u, num_radix_blocks);
+    m.gpu = G0(streams);
+    radix_alloc((void **)&m.d_packed, (size_t)m.cap_out * (m.big_n + 1) * sizeof(uint64_t));
+    radix_alloc((void **)&m.d_after_ks, (size_t)m.cap_out * (m.small_n + 1) * sizeof(uint64_t));
+    std::vector<uint64_t> triv(m.cap_out), lo(m.cap_out), hi(m.cap_out);
+    for (uint32_t i = 0; i < m.cap_out; ++i) triv[i] = i, lo[i] = 2 * i, hi[i] = 2 * i + 1;
+    m.d_trivial = dev_upload(st, triv);
+    m.d_lo = dev_upload(st, lo);
+    m.d_hi = dev_upload(st, hi);
+    // the identity on message_modulus * carry_modulus values, encoded on 128 bits: delta = 2^127 / (msg * carry)
+    const uint32_t sup = m.msg * m.carry, box = m.N / sup, half = box / 2;
+    const unsigned __int128 delta = ((unsigned __int128)1 << 127) / sup;
+    std::vector<unsigned __int128> lut((size_t)(m.k + 1) * m.N, 0);
+    unsigned __int128 *body = lut.data() + (size_t)m.k * m.N;
+    for (uint32_t i = 0; i < sup; ++i)
+      for (uint32_t j = i * box; j < (i + 1) * box; ++j) body[j] = (unsigned __int128)i * delta;
+    for (uint32_t i = 0; i < half; ++i) body[i] = (unsigned __int128)0 - body[i];
+    std::rotate(body, body + half, body + m.N);
+    m.d_lut = dev_upload(st, lut);
+    t_bytes += hip_scratch_programmable_bootstrap_128_async(st, m.gpu, &m.pbs_buf, m.small_n, m.k, m.N, m.pbs_level, m.cap_out,
+                                                            !t_dry, noise_reduction_type);
+  });
+}
+
+void hip_integer_apply_noise_squashing_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out,
+                                                CudaRadixCiphertextFFI const *lwe_array_in, int8_t *mem_ptr,
+                                                void *const *ksks, void *const *bsks) {
+  first_gpu(streams);
+  auto *m = scratch_use<NoiseSquashMem>(mem_ptr, "apply_noise_squashing");
+  HX_PANIC_IF_FALSE(lwe_array_out && lwe_array_out->ptr && lwe_array_in && lwe_array_in->ptr && ksks && ksks[0] && bsks && bsks[0],
+                    "apply_noise_squashing: null pointer");
+  const uint32_t n_in = lwe_array_in->num_radix_blocks, n_out = lwe_array_out->num_radix_blocks;
+  HX_PANIC_IF_FALSE(n_out == (n_in + 1) / 2,
+                    "apply_noise_squashing: num output radix blocks (%u) should be half ceil the number input radix blocks (%u)",
+                    n_out, n_in);
+  HX_PANIC_IF_FALSE(n_in <= m->cap_in && n_out <= m->cap_out, "apply_noise_squashing: %u blocks exceed the scratch capacity %u",
+                    n_in, m->cap_in);
+  HX_PANIC_IF_FALSE(lwe_array_in->lwe_dimension == m->big_n && lwe_array_out->lwe_dimension == m->k * m->N,
+                    "apply_noise_squashing: lwe dimensions (%u in, %u out) differ from the scratch's (%u, %u)",
+                    lwe_array_in->lwe_dimension, lwe_array_out->lwe_dimension, m->big_n, m->k * m->N);
+  check_clean({lwe_array_in}, n_in, m->msg, "apply_noise_squashing", "ciphertexts must have empty carries to be squashed");
+  if (n_out == 0) return;
+  const hipStream_t st = S0(streams);
+  const uint64_t *in = (const uint64_t *)lwe_array_in->ptr;
+  const uint32_t words = m->big_n + 1, pairs = n_in / 2;
+  // block 2i + message_modulus * block 2i + 1; an odd last block goes through alone
+  axpy(st, m->d_packed, nullptr, in, m->d_hi, m->msg, in, m->d_lo, words, pairs);
+  if (n_in & 1) axpy(st, m->d_packed + (size_t)pairs * words, nullptr, in + (size_t)(n_in - 1) * words, nullptr, 1, nullptr, nullptr, words, 1);
+  launch_keyswitch(st, m->d_after_ks, m->d_trivial, m->d_packed, m->d_trivial, (const uint64_t *)ksks[0], m->big_n, m->small_n,
+                   m->ks_base_log, m->ks_level, n_out);
+  hip_programmable_bootstrap_128_async(st, m->gpu, lwe_array_out->ptr, m->d_lut, m->d_after_ks, bsks[0], m->pbs_buf, m->small_n,
+                                       m->k, m->N, m->pbs_base_log, m->pbs_level, n_out);
+  set_block_info(lwe_array_out, 0, n_out, (uint64_t)m->msg * m->msg - 1, 1);
+}
+
+void hip_cleanup_integer_apply_noise_squashing_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<NoiseSquashMem>(streams, mem_ptr_void, "cleanup apply_noise_squashing");
 }
 
 }  // extern "C"

@@ -216,6 +216,21 @@ SIGNATURES = {
     "hip_integer_scratch_batch": (None, [_u32]),
     "hip_integer_mult_pbs_count": (_u64, [_v]),
     "hip_integer_propagate_pbs_count": (_u64, [_u32]),
+    # 128-bit PBS and noise squashing
+    "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
+    "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_programmable_bootstrap_128_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "hip_cleanup_programmable_bootstrap_128": (None, [_v, _u32, _i8pp]),
+    "hip_fourier_transform_forward_as_torus_f128_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _u32, _u32]),
+    "hip_fourier_transform_forward_as_integer_f128_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _u32, _u32]),
+    "hip_fourier_transform_backward_as_torus_f128_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _u32, _u32]),
+    "hip_scratch_integer_apply_noise_squashing_64_async":
+        (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_apply_noise_squashing_64_async": (None, [_S, _R, _R, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_apply_noise_squashing_64": (None, [_S, _i8pp]),
+    "hip_test_fft128_tables_host": (None, [_u32, _v, _v, _v]),
+    "hip_test_decompose_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32]),
+    "hip_test_f128_cmul_async": (None, [_v, _u32, _v, _v, _v, _u32]),
 }
 
 

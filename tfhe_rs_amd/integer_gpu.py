@@ -582,3 +582,66 @@ class CudaCompressedCiphertextList:
         assert words.size == want, "packed words do not have the size the metadata describes"
         return cls(CudaVec.from_cpu_async(words, streams), m["block_counts"], m["glwe_dimension"], m["polynomial_size"],
                    m["lwe_per_glwe"], m["storage_log_modulus"], m["message_modulus"], m["carry_modulus"])
+
+
+# ---------------------------------------------------------------------------------------------- noise squashing
+# integer/gpu/noise_squashing/keys.rs (CudaNoiseSquashingKey) and integer/gpu/ciphertext/squashed_noise.rs
+# (CudaSquashedNoiseRadixCiphertext), over the hip_ entry points of include/tfhe_hip_backend.h, "128-bit PBS and noise
+# squashing".
+class CudaSquashedNoiseRadixCiphertext:
+    """ceil(blocks / 2) u128 LWE blocks under the squashing key's output key, each holding lo + message_modulus * hi of a
+    pair of input blocks; [block][lwe_size][2] uint64 on the host."""
+
+    def __init__(self, d_blocks: CudaVec, num_blocks, lwe_dimension, original_block_count):
+        self.d_blocks = d_blocks
+        self.num_blocks, self.lwe_dimension = int(num_blocks), int(lwe_dimension)
+        self.original_block_count = int(original_block_count)
+        self._info = np.ones(self.num_blocks, dtype=U64), np.ones(self.num_blocks, dtype=U64)
+
+    def to_blocks(self, streams):
+        return self.d_blocks.copy_to_cpu(streams).reshape(self.num_blocks, self.lwe_dimension + 1, 2)
+
+    def _ffi(self):
+        deg, noise = self._info
+        return ffi.CudaRadixCiphertextFFI(self.d_blocks.ptr, deg.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          noise.ctypes.data_as(C.POINTER(C.c_uint64)), self.num_blocks, self.num_blocks,
+                                          self.lwe_dimension)
+
+
+class CudaNoiseSquashingKey:
+    """keys.rs: the u128 bootstrap key (a CudaLweBootstrapKey128 from the compute set's small key to the squashing GLWE
+    key) and the moduli of the blocks it squashes."""
+
+    def __init__(self, bootstrapping_key, message_modulus, carry_modulus):
+        self.bootstrapping_key = bootstrapping_key
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+
+    def squash_radix_ciphertext_noise(self, src_server_key, ciphertext, streams):
+        """One integer with empty carries -> its squashed form: pack block pairs, keyswitch with the server key's
+        keyswitch key, bootstrap over the 128-bit torus with the identity table.  `ciphertext` is left unchanged."""
+        b, k = self.bootstrapping_key, src_server_key.key_switching_key
+        assert ciphertext.num_integers == 1, "one integer per call"
+        assert k.output_key_lwe_dimension == b.input_lwe_dimension, "keyswitch and squashing keys do not chain"
+        assert ciphertext.lwe_dimension == k.input_key_lwe_dimension, "Mismatched input LweDimension"
+        if int(ciphertext.degrees.max(initial=0)) > self.message_modulus - 1:
+            raise ValueError("Ciphertexts must have empty carries to be squashed")
+        n_in = ciphertext.total_blocks
+        n_out = (n_in + 1) // 2
+        out = CudaSquashedNoiseRadixCiphertext(CudaVec(n_out * (b.output_lwe_dimension + 1), streams, elem_words=2), n_out,
+                                               b.output_lwe_dimension, n_in)
+        s, keep = CudaServerKey._streams(streams)
+        mem = C.c_void_p()
+        ksks, bsks = (C.c_void_p * 1)(k.d_vec.ptr), (C.c_void_p * 1)(b.d_vec.ptr)
+        big = src_server_key.bootstrapping_key
+        lib = _lib()
+        lib.hip_scratch_integer_apply_noise_squashing_64_async(
+            s, C.byref(mem), b.input_lwe_dimension, b.glwe_dimension, b.polynomial_size, big.glwe_dimension,
+            big.polynomial_size, k.decomp_level_count, k.decomp_base_log, b.decomp_level_count, b.decomp_base_log, n_out,
+            n_in, self.message_modulus, self.carry_modulus, True, 1 if b.ms_noise_reduction else 0)
+        lib.hip_integer_apply_noise_squashing_64_async(s, C.byref(out._ffi()), C.byref(ciphertext._ffi()), mem, ksks, bsks)
+        lib.hip_cleanup_integer_apply_noise_squashing_64(s, C.byref(mem))
+        return out
+
+
+def squash_radix_ciphertext_noise(noise_squashing_key, src_server_key, ciphertext, streams):
+    return noise_squashing_key.squash_radix_ciphertext_noise(src_server_key, ciphertext, streams)
