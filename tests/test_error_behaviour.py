@@ -96,6 +96,39 @@ ABORTS = {
         p = C.c_void_p(C.addressof(junk))
         lib.cleanup_cuda_programmable_bootstrap_64(S, G, C.byref(p))
         """, "PBS buffer"),
+    "classic launch on a size-only scratch": ("""
+        buf = C.c_void_p()
+        lib.scratch_cuda_programmable_bootstrap_64_async(S, G, C.byref(buf), 10, 1, 256, 1, 4, False, 0)
+        v = gpu.CudaVec(4 * 600, st)
+        lib.cuda_programmable_bootstrap_64_async(S, G, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, buf,
+                                                 10, 1, 256, 4, 1, 4, 1, 0)
+        """, "created with allocate_gpu_memory=false"),
+    "multi-bit launch on a classic scratch": ("""
+        buf = C.c_void_p()
+        lib.scratch_cuda_programmable_bootstrap_64_async(S, G, C.byref(buf), 8, 1, 256, 1, 4, True, 0)
+        v = gpu.CudaVec(4 * 600, st)
+        lib.cuda_multi_bit_programmable_bootstrap_64_async(S, G, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, buf,
+                                                           8, 1, 256, 2, 4, 1, 4, 1, 0)
+        """, "multi-bit PBS buffer was not created by its scratch function"),
+    "multi-bit launch does not match its scratch": ("""
+        buf = C.c_void_p()
+        lib.scratch_cuda_multi_bit_programmable_bootstrap_64_async(S, G, C.byref(buf), 1, 256, 1, 4, True)
+        v = gpu.CudaVec(4 * 600, st)
+        lib.cuda_multi_bit_programmable_bootstrap_64_async(S, G, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, v.ptr, buf,
+                                                           8, 1, 512, 2, 4, 1, 4, 1, 0)
+        """, "multi-bit PBS buffer parameters do not match"),
+    "128-bit cleanup of a classic scratch": ("""
+        buf = C.c_void_p()
+        lib.scratch_cuda_programmable_bootstrap_64_async(S, G, C.byref(buf), 10, 1, 256, 1, 4, True, 0)
+        lib.hip_cleanup_programmable_bootstrap_128(S, G, C.byref(buf))
+        """, "foreign 128-bit PBS buffer"),
+    "second cleanup of the same variable": ("""
+        buf = C.c_void_p()
+        lib.scratch_cuda_programmable_bootstrap_64_async(S, G, C.byref(buf), 10, 1, 256, 1, 4, True, 0)
+        lib.cleanup_cuda_programmable_bootstrap_64(S, G, C.byref(buf))
+        assert not buf.value, buf.value             # the first cleanup nulled the caller's pointer
+        lib.cleanup_cuda_programmable_bootstrap_64(S, G, C.byref(buf))
+        """, "PBS buffer"),
     "launch on a size-only radix scratch": ("""
         s = ffi.CudaStreamsFFI((C.c_void_p * 1)(S), (C.c_uint32 * 1)(0), 1)
         mem = C.c_void_p()
@@ -214,6 +247,10 @@ RADIX_ABORTS = {
         assert not mem.value, mem.value             # the first cleanup nulled the caller's pointer
         lib.cleanup_cuda_cmux_64(s, C.byref(mem))
         """, "cleanup cmux: foreign scratch pointer"),
+    "classic cleanup of a live radix scratch (the kinds are told apart, not merely 'not zero')": ("""
+        lib.scratch_cuda_cmux_64_async(s, C.byref(mem), BSK, KSK, 8, 4, 4, True, 0)
+        lib.cleanup_cuda_programmable_bootstrap_64(S, G, C.byref(mem))
+        """, "PBS buffer"),
     "radix scratch creation through a null mem_ptr": ("""
         lib.scratch_cuda_propagate_single_carry_64_inplace_async(s, None, BSK, KSK, 8, 4, 4, 0, True, 0)
         """, "propagate_single_carry: null pointer"),
@@ -227,6 +264,30 @@ def test_misuse_prints_and_aborts(name):
     r = run(snippet)
     assert r.returncode == -signal.SIGABRT, (r.returncode, r.stderr[-400:])
     assert needle in r.stderr, r.stderr[-400:]
+
+
+def test_core_scratch_functions_return_the_same_bytes_sized_or_allocated():
+    """What the three core scratch functions and the keyswitch-PBS one return, with and without allocate_gpu_memory
+    (recorded from the library before the core scratches moved onto the shared scratch protocol)."""
+    r = run("""
+        def sized(create, cleanup, *args, ms=()):
+            got = []
+            for allocate in (True, False):
+                buf = C.c_void_p()
+                got.append(int(create(S, G, C.byref(buf), *args, allocate, *ms)))
+                cleanup(S, G, C.byref(buf))
+                assert not buf.value
+            return got
+        classic = (lib.scratch_cuda_programmable_bootstrap_64_async, lib.cleanup_cuda_programmable_bootstrap_64)
+        kspbs = (lib.hip_scratch_keyswitch_programmable_bootstrap_64_async, lib.cleanup_cuda_programmable_bootstrap_64)
+        multi = (lib.scratch_cuda_multi_bit_programmable_bootstrap_64_async, lib.cleanup_cuda_multi_bit_programmable_bootstrap_64)
+        wide = (lib.hip_scratch_programmable_bootstrap_128_async, lib.hip_cleanup_programmable_bootstrap_128)
+        print("SIZES", sized(*classic, 10, 1, 256, 1, 4, ms=(0,)), sized(*classic, 10, 1, 8192, 1, 4, ms=(0,)),
+              sized(*kspbs, 10, 1, 256, 1, 4, ms=(0,)), sized(*multi, 1, 256, 1, 4),
+              sized(*wide, 10, 1, 256, 1, 2, ms=(0,)), sized(*wide, 10, 1, 4096, 1, 2, ms=(0,)))
+        """)
+    assert r.returncode == 0, r.stderr[-400:]
+    assert "SIZES [0, 0] [524288, 524288] [384, 384] [33587200, 33587200] [0, 0] [262144, 262144]" in r.stdout, r.stdout
 
 
 def test_host_mirror_asserts_like_the_rust_wrappers():

@@ -5,6 +5,8 @@
 #include "arena.h"
 #include "profile.h"
 #include "pbs128.h"
+#include "ranges.h"
+#include "scratch.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -23,20 +25,18 @@ std::atomic<uint32_t> g_fft_kernel_choice{0};
 std::atomic<uint32_t> g_last_pbs_kernel{0};
 std::atomic<uint32_t> g_last_pbs_inst[7];  // L, B, G, mode, LWEs per workgroup, N, K1 (note_pbs_instantiation)
 
-constexpr uint32_t kPbsMagic = 0x50425331;   // "PBS1"
-constexpr uint32_t kMbMagic = 0x4d425031;    // "MBP1"
-
 // Host-side descriptor behind the opaque `int8_t *buffer` of the scratch/cleanup triple
 // (the reference's pbs_buffer<Torus, CLASSICAL>, cuda/include/pbs/pbs_utilities.h:100-260).
 // The whole CMUX loop runs on-chip, so the classic PBS needs no global scratch — except for the rings of
 // 8192 and 16384 coefficients, whose accumulator is a per-sample device buffer (acc_scratch).
-struct PbsBuffer {
-  uint32_t magic;
-  uint32_t lwe_dimension, glwe_dimension, polynomial_size, level_count, max_samples;
-  uint32_t ms_type;
-  bool gpu_memory_allocated;
-  FftTables fft;
-  NttTables ntt;
+// The three scratches of this file follow the protocol of scratch.h; their scratch functions return bytes by formulas of
+// their own (the tables and the multi-bit pace words are left out on purpose) and never touch the radix layer's count.
+struct PbsBuffer : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x50425331;  // "PBS1"
+  uint32_t lwe_dimension = 0, glwe_dimension = 0, polynomial_size = 0, level_count = 0, max_samples = 0;
+  uint32_t ms_type = 0;
+  FftTables fft{};
+  NttTables ntt{};
   uint64_t *acc_scratch = nullptr;
   uint64_t *split_acc = nullptr;  // exact engine, split-key form: (k+1) N accumulator words per sample in device memory
   uint32_t *split_flag = nullptr; // ... and its round-off flag (PbsArgs::roundoff_flag), allocated with split_acc
@@ -55,19 +55,37 @@ struct PbsBuffer {
   } emitted;
   uint64_t *ks_out = nullptr;  // hip_keyswitch_programmable_bootstrap_64_async: the keyswitched LWEs (small key)
   uint64_t *trivial = nullptr; // 0, 1, ..., max_samples - 1 (indexes of that list)
+  void release() {
+    if (split_flag && split_unrecovered) {
+      // a launch of the split-key exact engine ran without the NTT-domain twin of its key: its round-off flag is checked here
+      // even if nobody polled it — a host that never asks must not keep untrustworthy "exact" outputs
+      uint32_t v = 0;
+      HX_CHECK(hipMemcpy(&v, split_flag, sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HX_PANIC_IF_FALSE(v == 0, "split-key exact engine: an f64 limb product was further than 1/4 from an integer in a launch on "
+                                "this scratch whose key has no NTT-domain twin — its outputs are not the exact ones");
+    }
+    for (void *d : {(void *)acc_scratch, (void *)split_acc, (void *)split_flag, (void *)split_bad})
+      if (d) scratch_free(d);
+    for (void *r : emit_retired) scratch_free(r);
+    for (void *d : {(void *)emit_a, (void *)ks_out, (void *)trivial})
+      if (d) scratch_free(d);
+  }
 };
-struct MultiBitBuffer {
-  uint32_t magic;
-  uint32_t glwe_dimension, polynomial_size, level_count, max_samples;
-  bool gpu_memory_allocated;
-  FftTables fft;
-  uint32_t chunk;
-  uint64_t *acc;   // latency path: the accumulators crossing passes
+struct MultiBitBuffer : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x4d425031;  // "MBP1"
+  uint32_t glwe_dimension = 0, polynomial_size = 0, level_count = 0, max_samples = 0;
+  FftTables fft{};
+  uint32_t chunk = 1;
+  uint64_t *acc = nullptr;   // latency path: the accumulators crossing passes
   uint32_t *pace = nullptr;  // throughput kernel: per-XCD progress counters (PbsArgs::pace)
   // latency path (small batches): the keybundles of a pass, lat_bytes / (batch * kb_per_sample) groups at a time
   cplx *kb_lat = nullptr;
   uint32_t lat_samples = 0;
   uint64_t lat_bytes = 0, kb_per_sample = 0;
+  void release() {
+    for (void *d : {(void *)acc, (void *)kb_lat, (void *)pace})
+      if (d) scratch_free(d);
+  }
 };
 
 // max_n: 16384 for the classic and the multi-bit f64 PBS with k = 1 (the reference's kernels support rings up to
@@ -106,6 +124,42 @@ PbsArgs make_args(void *lwe_array_out, void const *lwe_output_indexes, void cons
   a.ms_type = ms_type;
   return a;
 }
+
+// ---- what the library derived from a range of device memory (ranges.h; the keyswitch cache keeps its own table)
+// The split-key exact engine's way out of a raised round-off flag: the NTT-domain form of the same key (the integer
+// Goldilocks kernel's operand), made next to the split form by hip_convert_lwe_programmable_bootstrap_key_ntt64_split_async
+// and kept by the library for as long as the split key's device memory is neither dropped nor overwritten
+RangeRegistry<void *> g_split_twins;
+// What hip_convert_lwe_programmable_bootstrap_key_128_async wrote where: a bootstrap whose key pointer is a converted
+// key of other sizes is refused.
+struct Key128Sizes {
+  uint32_t n, glwe_dim, level, N;
+};
+RangeRegistry<Key128Sizes> g_key128;
+// device memory [p, p + bytes) is about to be freed or written: what the library derived from it goes
+void device_range_changes(int device, const void *p, size_t bytes) {
+  ksm_invalidate_range(device, p, bytes);
+  for (void *twin : g_split_twins.take_overlapping(device, p, bytes)) device_free_sync(twin);  // synchronises the device: no launch still reads it
+  g_key128.take_overlapping(device, p, bytes);
+}
+
+// Key conversions: `bytes` of the standard-domain key `src` are staged on the device, `transform(staged)` launches on
+// `stream` whatever writes the dest_bytes of the converted key at `dest`.  `who` names the conversion in a refusal.
+template <class Transform>
+void convert_staged_key(void *stream, uint32_t gpu_index, void *dest, size_t dest_bytes, void const *src, size_t bytes,
+                        const char *who, Transform &&transform) {
+  HX_PANIC_IF_FALSE(dest != nullptr && src != nullptr, "%s: null pointer", who);
+  device_range_changes((int)gpu_index, dest, dest_bytes);
+  void *tmp = device_alloc_sync(bytes);
+  HX_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, S(stream)));
+  transform(tmp);
+  // the staging buffer must outlive the kernels: release it once the stream reaches here
+  HX_CHECK(hipStreamSynchronize(S(stream)));
+  device_free_sync(tmp);
+}
+size_t bsk_polys(uint32_t input_lwe_dim, uint32_t glwe_dim, uint32_t level_count) {
+  return (size_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1);
+}
 }  // namespace
 
 namespace tfhe_hip {
@@ -142,47 +196,6 @@ void cuda_destroy_stream(void *stream, uint32_t gpu_index) {
 void cuda_synchronize_stream(void *stream, uint32_t gpu_index) {
   set_device(gpu_index);
   HX_CHECK(hipStreamSynchronize(S(stream)));
-}
-// ---- the split-key exact engine's way out of a raised round-off flag: the NTT-domain form of the same key (the integer
-// Goldilocks kernel's operand), made next to the split form by hip_convert_lwe_programmable_bootstrap_key_ntt64_split_async
-// and kept by the library for as long as the split key's device memory is neither dropped nor overwritten
-struct SplitTwin {
-  int device;
-  const void *split_key;
-  size_t split_bytes;
-  void *ntt_key;
-};
-static std::mutex g_twin_mutex;
-static std::vector<SplitTwin> g_split_twins;
-static void split_twin_forget_range(int device, const void *p, size_t bytes) {
-  if (p == nullptr) return;
-  std::vector<void *> dead;
-  {
-    std::lock_guard<std::mutex> lock(g_twin_mutex);
-    const char *lo = (const char *)p, *hi = lo + (bytes ? bytes : 1);
-    for (size_t i = 0; i < g_split_twins.size();) {
-      const char *klo = (const char *)g_split_twins[i].split_key, *khi = klo + g_split_twins[i].split_bytes;
-      if (g_split_twins[i].device == device && klo < hi && lo < khi) {
-        dead.push_back(g_split_twins[i].ntt_key);
-        g_split_twins.erase(g_split_twins.begin() + i);
-      } else {
-        ++i;
-      }
-    }
-  }
-  for (void *d : dead) device_free_sync(d);  // synchronises the device: no launch still reads it
-}
-static const void *split_twin_of(int device, const void *split_key) {
-  std::lock_guard<std::mutex> lock(g_twin_mutex);
-  for (const SplitTwin &t : g_split_twins)
-    if (t.device == device && t.split_key == split_key) return t.ntt_key;
-  return nullptr;
-}
-// device memory [p, p + bytes) is about to be freed or written: what the library derived from it goes
-static void device_range_changes(int device, const void *p, size_t bytes) {
-  ksm_invalidate_range(device, p, bytes);
-  split_twin_forget_range(device, p, bytes);
-  key128_forget_range(device, p, bytes);
 }
 uint32_t cuda_is_available(void) { return hipSetDevice(0) == hipSuccess; }
 void *cuda_malloc(uint64_t size, uint32_t gpu_index) {
@@ -310,8 +323,8 @@ void cuda_drop(void *ptr, uint32_t gpu_index) {
     HX_CHECK(hipDeviceSynchronize());  // cudaFree synchronises; the memory is back in the pool for every stream
     return;
   }
-  if (ptr != nullptr && ksm_cache_entries() != 0) {
-    // a keyswitch key inside this allocation takes its cached matrix-core layout with it
+  if (ptr != nullptr && (ksm_cache_entries() != 0 || !g_split_twins.empty() || !g_key128.empty())) {
+    // a key inside this allocation takes what the library derived from it (device_range_changes) along
     void *base = ptr;
     size_t bytes = 1;
     if (hipMemGetAddressRange(&base, &bytes, ptr) != hipSuccess) base = ptr, bytes = 1;
@@ -326,22 +339,16 @@ static void convert_bsk_common(bool ntt, void *stream, uint32_t gpu_index, void 
                                uint32_t polynomial_size) {
   set_device(gpu_index);
   check_pow2_poly(polynomial_size, ntt ? 4096 : 16384);
-  HX_PANIC_IF_FALSE(dest != nullptr && src != nullptr, "bootstrap key conversion: null pointer");
-  const size_t polys = (size_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1);
+  const size_t polys = bsk_polys(input_lwe_dim, glwe_dim, level_count);
   const size_t bytes = polys * polynomial_size * sizeof(uint64_t);
-  // stage the standard-domain key on the device, transform polynomial by polynomial
-  void *tmp = device_alloc_sync(bytes);
-  HX_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, S(stream)));
-  if (ntt) {
-    const NttTables tb = get_ntt_tables(gpu_index, S(stream), polynomial_size);
-    launch_bsk_to_ntt(S(stream), polynomial_size, (const uint64_t *)tmp, dest, polys, tb);
-  } else {
-    const FftTables tb = get_fft_tables(gpu_index, S(stream), polynomial_size);
-    launch_bsk_to_fourier(S(stream), polynomial_size, glwe_dim, (const uint64_t *)tmp, dest, polys, tb);
-  }
-  // the staging buffer must outlive the kernel: release it once the stream reaches here
-  HX_CHECK(hipStreamSynchronize(S(stream)));
-  device_free_sync(tmp);
+  convert_staged_key(stream, gpu_index, dest, bytes, src, bytes, "bootstrap key conversion", [&](const void *staged) {
+    if (ntt)
+      launch_bsk_to_ntt(S(stream), polynomial_size, (const uint64_t *)staged, dest, polys,
+                        get_ntt_tables(gpu_index, S(stream), polynomial_size));
+    else
+      launch_bsk_to_fourier(S(stream), polynomial_size, glwe_dim, (const uint64_t *)staged, dest, polys,
+                            get_fft_tables(gpu_index, S(stream), polynomial_size));
+  });
 }
 
 void cuda_convert_lwe_programmable_bootstrap_key_64_async(void *stream, uint32_t gpu_index, void *dest,
@@ -368,14 +375,12 @@ uint64_t scratch_cuda_programmable_bootstrap_64_async(void *stream, uint32_t gpu
   HX_PANIC_IF_FALSE(polynomial_size <= 4096 || glwe_dimension == 1,
                     "polynomial_size %u is supported with glwe_dimension 1 only", polynomial_size);
   auto *b = new PbsBuffer();
-  b->magic = kPbsMagic;
   b->lwe_dimension = lwe_dimension;
   b->glwe_dimension = glwe_dimension;
   b->polynomial_size = polynomial_size;
   b->level_count = level_count;
   b->max_samples = input_lwe_ciphertext_count;
   b->ms_type = (uint32_t)noise_reduction_type;
-  b->gpu_memory_allocated = allocate_gpu_memory;
   if (allocate_gpu_memory) {
     // constant tables are built here (not in the launch) so the launch stays capture-safe
     b->fft = get_fft_tables(gpu_index, S(stream), polynomial_size);
@@ -389,7 +394,7 @@ uint64_t scratch_cuda_programmable_bootstrap_64_async(void *stream, uint32_t gpu
                                                  : (uint64_t)input_lwe_ciphertext_count * (glwe_dimension + 1) *
                                                        polynomial_size * sizeof(uint64_t);
   if (allocate_gpu_memory && bytes) b->acc_scratch = (uint64_t *)scratch_alloc(bytes);
-  *buffer = reinterpret_cast<int8_t *>(b);
+  scratch_hand_out(b, allocate_gpu_memory, buffer);
   return bytes;
 }
 
@@ -405,7 +410,7 @@ uint64_t hip_scratch_keyswitch_programmable_bootstrap_64_async(void *stream, uin
   const uint64_t bytes = scratch_cuda_programmable_bootstrap_64_async(
       stream, gpu_index, buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count,
       input_lwe_ciphertext_count, allocate_gpu_memory, noise_reduction_type);
-  auto *b = reinterpret_cast<PbsBuffer *>(*buffer);
+  auto *b = scratch_cast<PbsBuffer>(*buffer, "PBS buffer");
   const uint64_t ks_bytes = (uint64_t)input_lwe_ciphertext_count * (lwe_dimension + 1) * sizeof(uint64_t);
   const uint64_t idx_bytes = (uint64_t)input_lwe_ciphertext_count * sizeof(uint64_t);
   if (allocate_gpu_memory && ks_bytes) {
@@ -418,14 +423,30 @@ uint64_t hip_scratch_keyswitch_programmable_bootstrap_64_async(void *stream, uin
 
 static PbsBuffer *checked_buffer(int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
                                  uint32_t polynomial_size, uint32_t level_count, uint32_t num_samples) {
-  auto *b = reinterpret_cast<PbsBuffer *>(buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kPbsMagic, "PBS buffer was not created by scratch_cuda_programmable_bootstrap_64_async");
-  HX_PANIC_IF_FALSE(b->gpu_memory_allocated, "PBS buffer was created with allocate_gpu_memory=false");
+  auto *b = scratch_use<PbsBuffer>(buffer, "PBS buffer", " was not created by scratch_cuda_programmable_bootstrap_64_async");
   HX_PANIC_IF_FALSE(b->lwe_dimension == lwe_dimension && b->glwe_dimension == glwe_dimension &&
                         b->polynomial_size == polynomial_size && b->level_count == level_count,
                     "PBS buffer parameters do not match the call");
   HX_PANIC_IF_FALSE(num_samples <= b->max_samples, "num_samples %u exceeds the scratch capacity %u", num_samples,
                     b->max_samples);
+  return b;
+}
+// What the launch entry points of the classic family start with: device, scratch, decomposition (and num_many_lut where
+// `check_many_lut`), arguments.  nullptr: nothing to launch (num_samples == 0)
+static PbsBuffer *classic_prologue(PbsArgs *a, bool check_many_lut, uint32_t gpu_index, void *lwe_array_out,
+                                   void const *lwe_output_indexes, void const *lut_vector, void const *lut_vector_indexes,
+                                   void const *lwe_array_in, void const *lwe_input_indexes, void const *bootstrapping_key,
+                                   int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                   uint32_t base_log, uint32_t level_count, uint32_t num_samples, uint32_t num_many_lut,
+                                   uint32_t lut_stride) {
+  set_device(gpu_index);
+  PbsBuffer *b = checked_buffer(buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count, num_samples);
+  HX_PANIC_IF_FALSE(base_log >= 1 && base_log * level_count < 64, "invalid decomposition (base_log=%u, level=%u)",
+                    base_log, level_count);
+  if (check_many_lut) HX_PANIC_IF_FALSE(num_many_lut >= 1, "num_many_lut must be >= 1");
+  if (num_samples == 0) return nullptr;
+  *a = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in, lwe_input_indexes,
+                 bootstrapping_key, lwe_dimension, base_log, level_count, num_samples, num_many_lut, lut_stride, b->ms_type);
   return b;
 }
 
@@ -468,15 +489,11 @@ void cuda_programmable_bootstrap_64_async(void *stream, uint32_t gpu_index, void
                                           int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
                                           uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
                                           uint32_t num_samples, uint32_t num_many_lut, uint32_t lut_stride) {
-  set_device(gpu_index);
-  PbsBuffer *b = checked_buffer(buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count, num_samples);
-  HX_PANIC_IF_FALSE(base_log >= 1 && base_log * level_count < 64, "invalid decomposition (base_log=%u, level=%u)",
-                    base_log, level_count);
-  HX_PANIC_IF_FALSE(num_many_lut >= 1, "num_many_lut must be >= 1");
-  if (num_samples == 0) return;
-  PbsArgs a = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in,
-                        lwe_input_indexes, bootstrapping_key, lwe_dimension, base_log, level_count, num_samples,
-                        num_many_lut, lut_stride, b->ms_type);
+  PbsArgs a;
+  PbsBuffer *b = classic_prologue(&a, true, gpu_index, lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes,
+                                  lwe_array_in, lwe_input_indexes, bootstrapping_key, buffer, lwe_dimension, glwe_dimension,
+                                  polynomial_size, base_log, level_count, num_samples, num_many_lut, lut_stride);
+  if (b == nullptr) return;
   b->emitted.valid = false;  // whatever a chained call left describes an array this call may overwrite
   launch_classic_pbs(S(stream), a, b, glwe_dimension, polynomial_size);
 }
@@ -532,11 +549,15 @@ void hip_keyswitch_programmable_bootstrap_chain_64_async(void *stream, uint32_t 
                                                          uint32_t ks_level, uint32_t base_log, uint32_t level_count,
                                                          uint32_t num_samples, uint32_t num_many_lut,
                                                          uint32_t lut_stride, uint32_t flags) {
-  set_device(gpu_index);
-  PbsBuffer *b = checked_buffer(buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count, num_samples);
-  HX_PANIC_IF_FALSE(b->ks_out != nullptr || num_samples == 0,
+  PbsArgs a;
+  PbsBuffer *b = classic_prologue(&a, true, gpu_index, lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes,
+                                  lwe_array_in, lwe_input_indexes, bootstrapping_key, buffer, lwe_dimension, glwe_dimension,
+                                  polynomial_size, base_log, level_count, num_samples, num_many_lut, lut_stride);
+  if (b == nullptr) return;
+  HX_PANIC_IF_FALSE(b->ks_out != nullptr,
                     "PBS buffer has no keyswitch scratch: create it with hip_scratch_keyswitch_programmable_bootstrap_64_async");
-  if (num_samples == 0) return;
+  a.lwe_in = b->ks_out;  // the bootstrap reads the keyswitched list trivially
+  a.in_idx = b->trivial;
   const uint32_t n_big = glwe_dimension * polynomial_size;
   uint32_t level_pad = 0, steps = 0;
   const bool emittable = keyswitch_digits_emittable(n_big, ks_base_log, ks_level, &level_pad, &steps);
@@ -550,12 +571,6 @@ void hip_keyswitch_programmable_bootstrap_chain_64_async(void *stream, uint32_t 
                    ks_level, num_samples, use_ready ? &ready : nullptr);
   b->emitted.valid = false;  // the operands described the INPUT of this call; its output replaces them below or not
   // ---- bootstrap, with the emission when the throughput kernel takes the launch
-  HX_PANIC_IF_FALSE(base_log >= 1 && base_log * level_count < 64, "invalid decomposition (base_log=%u, level=%u)",
-                    base_log, level_count);
-  HX_PANIC_IF_FALSE(num_many_lut >= 1, "num_many_lut must be >= 1");
-  PbsArgs a = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, b->ks_out, b->trivial,
-                        bootstrapping_key, lwe_dimension, base_log, level_count, num_samples, num_many_lut, lut_stride,
-                        b->ms_type);
   // The operands only pay off where the NEXT keyswitch takes the GEMM path (keyswitch_mfma consumes them from
   // g_keyswitch_gemm_min LWEs on): below that, the flag changes nothing.
   if ((flags & HIP_KSPBS_EMIT_DIGITS) && emittable && num_many_lut == 1 && polynomial_size == 2048 && glwe_dimension == 1 &&
@@ -597,14 +612,11 @@ void hip_programmable_bootstrap_ntt64_async(void *stream, uint32_t gpu_index, vo
                                             int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
                                             uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
                                             uint32_t num_samples, uint32_t num_many_lut, uint32_t lut_stride) {
-  set_device(gpu_index);
-  PbsBuffer *b = checked_buffer(buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count, num_samples);
-  HX_PANIC_IF_FALSE(base_log >= 1 && base_log * level_count < 64, "invalid decomposition (base_log=%u, level=%u)",
-                    base_log, level_count);
-  if (num_samples == 0) return;
-  const PbsArgs a = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in,
-                              lwe_input_indexes, bootstrapping_key, lwe_dimension, base_log, level_count,
-                              num_samples, num_many_lut, lut_stride, b->ms_type);
+  PbsArgs a;
+  PbsBuffer *b = classic_prologue(&a, false, gpu_index, lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes,
+                                  lwe_array_in, lwe_input_indexes, bootstrapping_key, buffer, lwe_dimension, glwe_dimension,
+                                  polynomial_size, base_log, level_count, num_samples, num_many_lut, lut_stride);
+  if (b == nullptr) return;
   launch_pbs_ntt_generic(S(stream), polynomial_size, glwe_dimension, a, b->ntt);
   g_last_pbs_kernel.store(3);
 }
@@ -621,25 +633,21 @@ void hip_convert_lwe_programmable_bootstrap_key_ntt64_split_async(void *stream, 
                                                                   uint32_t glwe_dim, uint32_t level_count,
                                                                   uint32_t polynomial_size) {
   set_device(gpu_index);
-  HX_PANIC_IF_FALSE(dest != nullptr && src != nullptr, "bootstrap key conversion: null pointer");
   HX_PANIC_IF_FALSE(polynomial_size == 2048 && glwe_dim == 1 && level_count == 1,
                     "split-key exact engine: parameter set not supported (N = 2048, k = 1, one level)");
-  const size_t polys = (size_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1);
+  const size_t polys = bsk_polys(input_lwe_dim, glwe_dim, level_count);
   const size_t bytes = polys * polynomial_size * sizeof(uint64_t);
-  void *tmp = device_alloc_sync(bytes);
-  HX_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, S(stream)));
-  device_range_changes((int)gpu_index, dest, bytes * NTT_SPLIT_LIMBS);
-  launch_bsk_to_split(S(stream), polynomial_size, (const uint64_t *)tmp, dest, polys,
-                      get_fft_tables(gpu_index, S(stream), polynomial_size));
-  // the key's NTT-domain twin (as many bytes as the standard key): what the integer kernel recomputes a flagged
-  // ciphertext with (hip_programmable_bootstrap_ntt64_split_async)
-  void *twin = device_alloc_sync(bytes);
-  launch_bsk_to_ntt(S(stream), polynomial_size, (const uint64_t *)tmp, twin, polys,
-                    get_ntt_tables(gpu_index, S(stream), polynomial_size));
-  HX_CHECK(hipStreamSynchronize(S(stream)));  // the staging buffer must outlive the kernels
-  device_free_sync(tmp);
-  std::lock_guard<std::mutex> lock(g_twin_mutex);
-  g_split_twins.push_back(SplitTwin{(int)gpu_index, dest, bytes * NTT_SPLIT_LIMBS, twin});
+  void *twin = nullptr;
+  convert_staged_key(stream, gpu_index, dest, bytes * NTT_SPLIT_LIMBS, src, bytes, "bootstrap key conversion", [&](const void *staged) {
+    launch_bsk_to_split(S(stream), polynomial_size, (const uint64_t *)staged, dest, polys,
+                        get_fft_tables(gpu_index, S(stream), polynomial_size));
+    // the key's NTT-domain twin (as many bytes as the standard key): what the integer kernel recomputes a flagged
+    // ciphertext with (hip_programmable_bootstrap_ntt64_split_async)
+    twin = device_alloc_sync(bytes);
+    launch_bsk_to_ntt(S(stream), polynomial_size, (const uint64_t *)staged, twin, polys,
+                      get_ntt_tables(gpu_index, S(stream), polynomial_size));
+  });
+  g_split_twins.add((int)gpu_index, dest, bytes * NTT_SPLIT_LIMBS, twin);
 }
 void hip_programmable_bootstrap_ntt64_split_async(void *stream, uint32_t gpu_index, void *lwe_array_out,
                                                   void const *lwe_output_indexes, void const *lut_vector,
@@ -648,12 +656,15 @@ void hip_programmable_bootstrap_ntt64_split_async(void *stream, uint32_t gpu_ind
                                                   int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
                                                   uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
                                                   uint32_t num_samples, uint32_t num_many_lut, uint32_t lut_stride) {
-  set_device(gpu_index);
-  PbsBuffer *b = checked_buffer(buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count, num_samples);
+  // (what the engine supports is a valid decomposition: the prologue's own check never fires behind this one)
   HX_PANIC_IF_FALSE(pbs_ntt_split_supported(polynomial_size, glwe_dimension, level_count, base_log),
                     "split-key exact engine: parameter set not supported (N=%u, k=%u, level=%u, base_log=%u)",
                     polynomial_size, glwe_dimension, level_count, base_log);
-  if (num_samples == 0) return;
+  PbsArgs a;
+  PbsBuffer *b = classic_prologue(&a, false, gpu_index, lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes,
+                                  lwe_array_in, lwe_input_indexes, bootstrapping_key, buffer, lwe_dimension, glwe_dimension,
+                                  polynomial_size, base_log, level_count, num_samples, num_many_lut, lut_stride);
+  if (b == nullptr) return;
   if (b->split_acc == nullptr) {
     // first use of this engine with this scratch: the accumulators' home (an allocation — not under stream capture;
     // a capture must be preceded by one plain launch, like the keyswitch's first use of a key)
@@ -665,9 +676,6 @@ void hip_programmable_bootstrap_ntt64_split_async(void *stream, uint32_t gpu_ind
     HX_CHECK(hipMemsetAsync(b->split_flag, 0, (64 + 8 * 32) * sizeof(uint32_t), S(stream)));
     b->split_bad = (uint32_t *)scratch_alloc((size_t)b->max_samples * sizeof(uint32_t));
   }
-  PbsArgs a = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in,
-                        lwe_input_indexes, bootstrapping_key, lwe_dimension, base_log, level_count, num_samples,
-                        num_many_lut, lut_stride, b->ms_type);
   a.acc_scratch = b->split_acc;
   a.roundoff_flag = b->split_flag;
   a.pace = b->split_flag + 64;
@@ -676,7 +684,8 @@ void hip_programmable_bootstrap_ntt64_split_async(void *stream, uint32_t gpu_ind
   // on the same stream, with the key's NTT-domain twin: per sample a flag word, the second launch's workgroups return at
   // once where it is 0 (a few microseconds for the launch when nothing was flagged).  Both compute ntt64_bnf_pbs.rs:208-280,
   // so the outputs are the exact ones whatever the data; the status call counts the recomputed ciphertexts.
-  const void *twin = split_twin_of((int)gpu_index, bootstrapping_key);
+  void *twin = nullptr;
+  g_split_twins.find((int)gpu_index, bootstrapping_key, &twin);
   if (twin != nullptr) {
     HX_CHECK(hipMemsetAsync(b->split_bad, 0, (size_t)num_samples * sizeof(uint32_t), S(stream)));
     a.bad_samples = b->split_bad;
@@ -706,8 +715,7 @@ void hip_programmable_bootstrap_ntt64_split_async(void *stream, uint32_t gpu_ind
 // key had no NTT-domain twin (a split key the caller copied instead of converting): those outputs cannot be trusted.
 uint32_t hip_programmable_bootstrap_ntt64_split_roundoff_status(void *stream, uint32_t gpu_index, int8_t *buffer) {
   set_device(gpu_index);
-  PbsBuffer *b = reinterpret_cast<PbsBuffer *>(buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kPbsMagic, "roundoff_status: foreign scratch pointer");
+  PbsBuffer *b = scratch_cast<PbsBuffer>(buffer, "roundoff_status");
   if (b->split_flag == nullptr) return 0;
   uint32_t v[2] = {0, 0};
   HX_CHECK(hipMemcpyAsync(v, b->split_flag, sizeof(v), hipMemcpyDeviceToHost, S(stream)));
@@ -727,15 +735,12 @@ void hip_convert_lwe_programmable_bootstrap_key_ref64_async(void *stream, uint32
                                                             uint32_t polynomial_size) {
   set_device(gpu_index);
   check_pow2_poly(polynomial_size, 2048);
-  HX_PANIC_IF_FALSE(dest != nullptr && src != nullptr, "bootstrap key conversion: null pointer");
-  const size_t polys = (size_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1);
+  const size_t polys = bsk_polys(input_lwe_dim, glwe_dim, level_count);
   const size_t bytes = polys * polynomial_size * sizeof(uint64_t);
-  void *tmp = device_alloc_sync(bytes);
-  HX_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, S(stream)));
-  launch_bsk_to_ref64(S(stream), polynomial_size, (const uint64_t *)tmp, dest, polys,
-                      get_ref_tables(gpu_index, S(stream), polynomial_size));
-  HX_CHECK(hipStreamSynchronize(S(stream)));
-  device_free_sync(tmp);
+  convert_staged_key(stream, gpu_index, dest, bytes, src, bytes, "bootstrap key conversion", [&](const void *staged) {
+    launch_bsk_to_ref64(S(stream), polynomial_size, (const uint64_t *)staged, dest, polys,
+                        get_ref_tables(gpu_index, S(stream), polynomial_size));
+  });
 }
 void hip_programmable_bootstrap_ref64_async(void *stream, uint32_t gpu_index, void *lwe_array_out,
                                             void const *lwe_output_indexes, void const *lut_vector,
@@ -744,14 +749,11 @@ void hip_programmable_bootstrap_ref64_async(void *stream, uint32_t gpu_index, vo
                                             int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
                                             uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
                                             uint32_t num_samples, uint32_t num_many_lut, uint32_t lut_stride) {
-  set_device(gpu_index);
-  PbsBuffer *b = checked_buffer(buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count, num_samples);
-  HX_PANIC_IF_FALSE(base_log >= 1 && base_log * level_count < 64, "invalid decomposition (base_log=%u, level=%u)",
-                    base_log, level_count);
-  if (num_samples == 0) return;
-  const PbsArgs a = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in,
-                              lwe_input_indexes, bootstrapping_key, lwe_dimension, base_log, level_count,
-                              num_samples, num_many_lut, lut_stride, b->ms_type);
+  PbsArgs a;
+  PbsBuffer *b = classic_prologue(&a, false, gpu_index, lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes,
+                                  lwe_array_in, lwe_input_indexes, bootstrapping_key, buffer, lwe_dimension, glwe_dimension,
+                                  polynomial_size, base_log, level_count, num_samples, num_many_lut, lut_stride);
+  if (b == nullptr) return;
   launch_pbs_ref64(S(stream), polynomial_size, glwe_dimension, a, get_ref_tables(gpu_index, S(stream), polynomial_size));
   g_last_pbs_kernel.store(11);
 }
@@ -762,7 +764,8 @@ void hip_convert_lwe_programmable_bootstrap_key_exact64_async(void *stream, uint
                                                               uint32_t polynomial_size) {
   // the exact engine consumes the key in the standard domain: plain upload
   set_device(gpu_index);
-  const size_t bytes = (size_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1) * polynomial_size * 8;
+  const size_t bytes = bsk_polys(input_lwe_dim, glwe_dim, level_count) * polynomial_size * sizeof(uint64_t);
+  device_range_changes((int)gpu_index, dest, bytes);
   HX_CHECK(hipMemcpyAsync(dest, src, bytes, hipMemcpyHostToDevice, S(stream)));
 }
 
@@ -773,42 +776,17 @@ void hip_programmable_bootstrap_exact64_async(void *stream, uint32_t gpu_index, 
                                               int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension,
                                               uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
                                               uint32_t num_samples, uint32_t num_many_lut, uint32_t lut_stride) {
-  set_device(gpu_index);
-  PbsBuffer *b = checked_buffer(buffer, lwe_dimension, glwe_dimension, polynomial_size, level_count, num_samples);
-  HX_PANIC_IF_FALSE(base_log >= 1 && base_log * level_count < 64, "invalid decomposition (base_log=%u, level=%u)",
-                    base_log, level_count);
-  if (num_samples == 0) return;
-  const PbsArgs a = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in,
-                              lwe_input_indexes, bootstrapping_key, lwe_dimension, base_log, level_count,
-                              num_samples, num_many_lut, lut_stride, b->ms_type);
+  PbsArgs a;
+  PbsBuffer *b = classic_prologue(&a, false, gpu_index, lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes,
+                                  lwe_array_in, lwe_input_indexes, bootstrapping_key, buffer, lwe_dimension, glwe_dimension,
+                                  polynomial_size, base_log, level_count, num_samples, num_many_lut, lut_stride);
+  if (b == nullptr) return;
   launch_pbs_exact_generic(S(stream), polynomial_size, glwe_dimension, a);
   g_last_pbs_kernel.store(5);
 }
 
 void cleanup_cuda_programmable_bootstrap_64(void *stream, uint32_t gpu_index, int8_t **pbs_buffer) {
-  set_device(gpu_index);
-  auto *b = reinterpret_cast<PbsBuffer *>(*pbs_buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kPbsMagic, "cleanup of a foreign PBS buffer");
-  HX_CHECK(hipStreamSynchronize(S(stream)));  // cleanup_* synchronises (pbs_utilities.h:261-271)
-  if (b->split_flag && b->split_unrecovered) {
-    // a launch of the split-key exact engine ran without the NTT-domain twin of its key: its round-off flag is checked here
-    // even if nobody polled it — a host that never asks must not keep untrustworthy "exact" outputs
-    uint32_t v = 0;
-    HX_CHECK(hipMemcpy(&v, b->split_flag, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HX_PANIC_IF_FALSE(v == 0, "split-key exact engine: an f64 limb product was further than 1/4 from an integer in a launch on "
-                              "this scratch whose key has no NTT-domain twin — its outputs are not the exact ones");
-  }
-  if (b->acc_scratch) scratch_free(b->acc_scratch);
-  if (b->split_acc) scratch_free(b->split_acc);
-  if (b->split_flag) scratch_free(b->split_flag);
-  if (b->split_bad) scratch_free(b->split_bad);
-  for (void *r : b->emit_retired) scratch_free(r);
-  if (b->emit_a) scratch_free(b->emit_a);
-  if (b->ks_out) scratch_free(b->ks_out);
-  if (b->trivial) scratch_free(b->trivial);
-  b->magic = 0;
-  delete b;
-  *pbs_buffer = nullptr;
+  scratch_destroy<PbsBuffer>(gpu_index, S(stream), pbs_buffer, "cleanup of a foreign PBS buffer", "");
 }
 
 // =========================================================================== multi-bit PBS
@@ -828,18 +806,15 @@ void cuda_convert_lwe_multi_bit_programmable_bootstrap_key_64_async(void *stream
   // the keybundle of every group is a pointwise combine (multibit.hip).
   set_device(gpu_index);
   check_pow2_poly(polynomial_size, glwe_dim == 1 ? 16384 : glwe_dim == 2 ? 2048 : 1024);
-  HX_PANIC_IF_FALSE(dest != nullptr && src != nullptr, "multi-bit bootstrap key conversion: null pointer");
   HX_PANIC_IF_FALSE(grouping_factor >= 1 && input_lwe_dim % grouping_factor == 0,
                     "input_lwe_dim %u not a multiple of grouping_factor %u", input_lwe_dim, grouping_factor);
   const size_t polys = (size_t)(input_lwe_dim / grouping_factor) * ((size_t)1 << grouping_factor) * level_count *
                        (glwe_dim + 1) * (glwe_dim + 1);
   const size_t bytes = polys * polynomial_size * sizeof(uint64_t);
-  void *tmp = device_alloc_sync(bytes);
-  HX_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, S(stream)));
-  const FftTables tb = get_fft_tables(gpu_index, S(stream), polynomial_size);
-  launch_bsk_to_fourier(S(stream), polynomial_size, glwe_dim, (const uint64_t *)tmp, dest, polys, tb);
-  HX_CHECK(hipStreamSynchronize(S(stream)));  // the staging buffer must outlive the kernel
-  device_free_sync(tmp);
+  convert_staged_key(stream, gpu_index, dest, bytes, src, bytes, "multi-bit bootstrap key conversion", [&](const void *staged) {
+    launch_bsk_to_fourier(S(stream), polynomial_size, glwe_dim, (const uint64_t *)staged, dest, polys,
+                          get_fft_tables(gpu_index, S(stream), polynomial_size));
+  });
 }
 
 uint64_t scratch_cuda_multi_bit_programmable_bootstrap_64_async(void *stream, uint32_t gpu_index,
@@ -850,13 +825,10 @@ uint64_t scratch_cuda_multi_bit_programmable_bootstrap_64_async(void *stream, ui
   set_device(gpu_index);
   check_pow2_poly(polynomial_size, glwe_dimension == 1 ? 16384 : glwe_dimension == 2 ? 2048 : 1024);
   auto *b = new MultiBitBuffer();
-  b->magic = kMbMagic;
   b->glwe_dimension = glwe_dimension;
   b->polynomial_size = polynomial_size;
   b->level_count = level_count;
   b->max_samples = input_lwe_ciphertext_count;
-  b->gpu_memory_allocated = allocate_gpu_memory;
-  b->acc = nullptr;
   const size_t k1 = glwe_dimension + 1;
   const size_t kb_per_sample = (size_t)level_count * k1 * k1 * (polynomial_size / 2) * sizeof(cplx);
   const size_t acc_per_sample = 2 * k1 * polynomial_size * sizeof(uint64_t);
@@ -881,8 +853,19 @@ uint64_t scratch_cuda_multi_bit_programmable_bootstrap_64_async(void *stream, ui
     if (lat_bytes) b->kb_lat = (cplx *)scratch_alloc(lat_bytes);
   }
   b->lat_bytes = lat_bytes;
-  *pbs_buffer = reinterpret_cast<int8_t *>(b);
+  scratch_hand_out(b, allocate_gpu_memory, pbs_buffer);
   return bytes + lat_bytes;
+}
+
+static MultiBitBuffer *checked_multi_bit(int8_t *buffer, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                         uint32_t grouping_factor, uint32_t level_count, uint32_t num_samples) {
+  auto *b = scratch_use<MultiBitBuffer>(buffer, "multi-bit PBS buffer", " was not created by its scratch function");
+  HX_PANIC_IF_FALSE(b->glwe_dimension == glwe_dimension && b->polynomial_size == polynomial_size &&
+                        b->level_count == level_count && num_samples <= b->max_samples,
+                    "multi-bit PBS buffer parameters do not match the call");
+  HX_PANIC_IF_FALSE(grouping_factor >= 1 && grouping_factor <= 4 && lwe_dimension % grouping_factor == 0,
+                    "unsupported grouping_factor %u for lwe_dimension %u", grouping_factor, lwe_dimension);
+  return b;
 }
 
 void cuda_multi_bit_programmable_bootstrap_64_async(void *stream, uint32_t gpu_index, void *lwe_array_out,
@@ -894,14 +877,8 @@ void cuda_multi_bit_programmable_bootstrap_64_async(void *stream, uint32_t gpu_i
                                                     uint32_t base_log, uint32_t level_count, uint32_t num_samples,
                                                     uint32_t num_many_lut, uint32_t lut_stride) {
   set_device(gpu_index);
-  auto *b = reinterpret_cast<MultiBitBuffer *>(buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kMbMagic, "multi-bit PBS buffer was not created by its scratch function");
-  HX_PANIC_IF_FALSE(b->gpu_memory_allocated, "multi-bit PBS buffer was created with allocate_gpu_memory=false");
-  HX_PANIC_IF_FALSE(b->glwe_dimension == glwe_dimension && b->polynomial_size == polynomial_size &&
-                        b->level_count == level_count && num_samples <= b->max_samples,
-                    "multi-bit PBS buffer parameters do not match the call");
-  HX_PANIC_IF_FALSE(grouping_factor >= 1 && grouping_factor <= 4 && lwe_dimension % grouping_factor == 0,
-                    "unsupported grouping_factor %u for lwe_dimension %u", grouping_factor, lwe_dimension);
+  MultiBitBuffer *b = checked_multi_bit(buffer, lwe_dimension, glwe_dimension, polynomial_size, grouping_factor, level_count,
+                                        num_samples);
   if (num_samples == 0) return;
   MultiBitArgs m;
   m.pbs = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in,
@@ -938,16 +915,7 @@ void cuda_multi_bit_programmable_bootstrap_64_async(void *stream, uint32_t gpu_i
 }
 
 void cleanup_cuda_multi_bit_programmable_bootstrap_64(void *stream, uint32_t gpu_index, int8_t **pbs_buffer) {
-  set_device(gpu_index);
-  auto *b = reinterpret_cast<MultiBitBuffer *>(*pbs_buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kMbMagic, "cleanup of a foreign multi-bit PBS buffer");
-  HX_CHECK(hipStreamSynchronize(S(stream)));
-  if (b->acc) scratch_free(b->acc);
-  if (b->kb_lat) scratch_free(b->kb_lat);
-  if (b->pace) scratch_free(b->pace);
-  b->magic = 0;
-  delete b;
-  *pbs_buffer = nullptr;
+  scratch_destroy<MultiBitBuffer>(gpu_index, S(stream), pbs_buffer, "cleanup of a foreign multi-bit PBS buffer", "");
 }
 
 // The reference's noise tests run the blind rotation on an input that the multi-bit switch has ALREADY been applied to
@@ -978,14 +946,8 @@ void cuda_multi_bit_programmable_bootstrap_noise_tests_64_async(
   HX_PANIC_IF_FALSE(base_log <= 64, "(multi-bit PBS): base log (%u) should be <= 64", base_log);
   HX_PANIC_IF_FALSE(polynomial_size == 2048, "(multi-bit PBS noise tests): only polynomial size 2048 is supported, got %u.",
                     polynomial_size);
-  auto *b = reinterpret_cast<MultiBitBuffer *>(buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kMbMagic, "multi-bit PBS buffer was not created by its scratch function");
-  HX_PANIC_IF_FALSE(b->gpu_memory_allocated, "multi-bit PBS buffer was created with allocate_gpu_memory=false");
-  HX_PANIC_IF_FALSE(b->glwe_dimension == glwe_dimension && b->polynomial_size == polynomial_size &&
-                        b->level_count == level_count && num_samples <= b->max_samples,
-                    "multi-bit PBS buffer parameters do not match the call");
-  HX_PANIC_IF_FALSE(grouping_factor >= 1 && grouping_factor <= 4 && lwe_dimension % grouping_factor == 0,
-                    "unsupported grouping_factor %u for lwe_dimension %u", grouping_factor, lwe_dimension);
+  MultiBitBuffer *b = checked_multi_bit(buffer, lwe_dimension, glwe_dimension, polynomial_size, grouping_factor, level_count,
+                                        num_samples);
   MultiBitArgs m;
   m.pbs = make_args(lwe_array_out, lwe_output_indexes, lut_vector, lut_vector_indexes, lwe_array_in, lwe_input_indexes,
                     bootstrapping_key, lwe_dimension, base_log, level_count, num_samples, num_many_lut, lut_stride, 0);
@@ -1205,30 +1167,27 @@ bool cuda_fft16x4x16_is_supported_async(uint32_t gpu_index) {
 // =========================================================================== 128-bit PBS (pbs128.h)
 // The reference's cuda_*_128 / *_f128 entry points under hip_ names, parameter lists unchanged
 // (cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103; cuda/include/fft/fft128.h).
-constexpr uint32_t kPbs128Magic = 0x50423238;  // "PB28"
-struct Pbs128Buffer {
-  uint32_t magic;
-  uint32_t lwe_dimension, glwe_dimension, polynomial_size, level_count, max_samples, ms_type;
-  bool gpu_memory_allocated;
-  Fft128Tables fft;
+struct Pbs128Buffer : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x50423238;  // "PB28"
+  uint32_t lwe_dimension = 0, glwe_dimension = 0, polynomial_size = 0, level_count = 0, max_samples = 0, ms_type = 0;
+  Fft128Tables fft{};
   u128 *acc_scratch = nullptr;
+  void release() {
+    if (acc_scratch) scratch_free(acc_scratch);
+  }
 };
 void hip_convert_lwe_programmable_bootstrap_key_128_async(void *stream, uint32_t gpu_index, void *dest, void const *src,
                                                           uint32_t input_lwe_dim, uint32_t glwe_dim, uint32_t level_count,
                                                           uint32_t polynomial_size) {
   set_device(gpu_index);
   pbs128_check_poly(polynomial_size);
-  HX_PANIC_IF_FALSE(dest != nullptr && src != nullptr, "bootstrap key conversion: null pointer");
-  const size_t polys = (size_t)input_lwe_dim * level_count * (glwe_dim + 1) * (glwe_dim + 1);
+  const size_t polys = bsk_polys(input_lwe_dim, glwe_dim, level_count);
   const size_t bytes = polys * polynomial_size * sizeof(u128);  // standard domain; the converted key takes as many
-  void *tmp = device_alloc_sync(bytes);
-  HX_CHECK(hipMemcpyAsync(tmp, src, bytes, hipMemcpyHostToDevice, S(stream)));
-  device_range_changes((int)gpu_index, dest, bytes);
-  launch_fft128_forward(S(stream), polynomial_size, (double *)dest, nullptr, nullptr, nullptr, (const u128 *)tmp, polys,
-                        get_fft128_tables(gpu_index, polynomial_size), 0, 1);
-  HX_CHECK(hipStreamSynchronize(S(stream)));  // the staging buffer must outlive the kernel
-  device_free_sync(tmp);
-  key128_record(Key128Record{(int)gpu_index, dest, bytes, input_lwe_dim, glwe_dim, level_count, polynomial_size});
+  convert_staged_key(stream, gpu_index, dest, bytes, src, bytes, "bootstrap key conversion", [&](const void *staged) {
+    launch_fft128_forward(S(stream), polynomial_size, (double *)dest, nullptr, nullptr, nullptr, (const u128 *)staged, polys,
+                          get_fft128_tables(gpu_index, polynomial_size), 0, 1);
+  });
+  g_key128.add((int)gpu_index, dest, bytes, Key128Sizes{input_lwe_dim, glwe_dim, level_count, polynomial_size});
 }
 uint64_t hip_scratch_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, int8_t **buffer,
                                                       uint32_t lwe_dimension, uint32_t glwe_dimension,
@@ -1242,14 +1201,12 @@ uint64_t hip_scratch_programmable_bootstrap_128_async(void *stream, uint32_t gpu
                     "unsupported (polynomial_size=%u, glwe_dimension=%u) for the 128-bit PBS", polynomial_size, glwe_dimension);
   HX_PANIC_IF_FALSE(level_count >= 1 && level_count <= 128, "invalid decomposition (level=%u)", level_count);
   auto *b = new Pbs128Buffer();
-  b->magic = kPbs128Magic;
   b->lwe_dimension = lwe_dimension;
   b->glwe_dimension = glwe_dimension;
   b->polynomial_size = polynomial_size;
   b->level_count = level_count;
   b->max_samples = input_lwe_ciphertext_count;
   b->ms_type = (uint32_t)noise_reduction_type;
-  b->gpu_memory_allocated = allocate_gpu_memory;
   // the accumulator stays on the chip wherever it fits next to the transform buffer; else one per sample in device memory
   const uint64_t bytes = pbs128_needs_acc_scratch(polynomial_size, glwe_dimension)
                              ? (uint64_t)input_lwe_ciphertext_count * (glwe_dimension + 1) * polynomial_size * sizeof(u128)
@@ -1258,7 +1215,7 @@ uint64_t hip_scratch_programmable_bootstrap_128_async(void *stream, uint32_t gpu
     b->fft = get_fft128_tables(gpu_index, polynomial_size);  // built here, so that the launch stays capture-safe
     if (bytes) b->acc_scratch = (u128 *)scratch_alloc(bytes);
   }
-  *buffer = reinterpret_cast<int8_t *>(b);
+  scratch_hand_out(b, allocate_gpu_memory, buffer);
   return bytes;
 }
 void hip_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void *lwe_array_out, void const *lut_vector,
@@ -1266,10 +1223,7 @@ void hip_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void
                                           uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
                                           uint32_t base_log, uint32_t level_count, uint32_t num_samples) {
   set_device(gpu_index);
-  auto *b = reinterpret_cast<Pbs128Buffer *>(buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kPbs128Magic,
-                    "PBS buffer was not created by hip_scratch_programmable_bootstrap_128_async");
-  HX_PANIC_IF_FALSE(b->gpu_memory_allocated, "PBS buffer was created with allocate_gpu_memory=false");
+  auto *b = scratch_use<Pbs128Buffer>(buffer, "PBS buffer", " was not created by hip_scratch_programmable_bootstrap_128_async");
   HX_PANIC_IF_FALSE(b->lwe_dimension == lwe_dimension && b->glwe_dimension == glwe_dimension &&
                         b->polynomial_size == polynomial_size && b->level_count == level_count,
                     "PBS buffer parameters do not match the call");
@@ -1277,8 +1231,8 @@ void hip_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void
                     b->max_samples);
   HX_PANIC_IF_FALSE(base_log >= 1 && base_log <= 64 && (uint64_t)base_log * level_count <= 128,
                     "invalid decomposition (base_log=%u, level=%u)", base_log, level_count);
-  Key128Record rec;
-  if (key128_find((int)gpu_index, bootstrapping_key, &rec))
+  Key128Sizes rec;
+  if (g_key128.find((int)gpu_index, bootstrapping_key, &rec))
     HX_PANIC_IF_FALSE(rec.n == lwe_dimension && rec.glwe_dim == glwe_dimension && rec.level == level_count &&
                           rec.N == polynomial_size,
                       "the bootstrap key was converted for other sizes (n=%u, k=%u, level=%u, N=%u)", rec.n, rec.glwe_dim,
@@ -1300,14 +1254,7 @@ void hip_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void
   launch_pbs128(S(stream), polynomial_size, glwe_dimension, a, b->fft);
 }
 void hip_cleanup_programmable_bootstrap_128(void *stream, uint32_t gpu_index, int8_t **pbs_buffer) {
-  set_device(gpu_index);
-  auto *b = reinterpret_cast<Pbs128Buffer *>(*pbs_buffer);
-  HX_PANIC_IF_FALSE(b != nullptr && b->magic == kPbs128Magic, "cleanup of a foreign 128-bit PBS buffer");
-  HX_CHECK(hipStreamSynchronize(S(stream)));
-  if (b->acc_scratch) scratch_free(b->acc_scratch);
-  b->magic = 0;
-  delete b;
-  *pbs_buffer = nullptr;
+  scratch_destroy<Pbs128Buffer>(gpu_index, S(stream), pbs_buffer, "cleanup of a foreign 128-bit PBS buffer", "");
 }
 void hip_fourier_transform_forward_as_torus_f128_async(void *stream, uint32_t gpu_index, void *re0, void *re1, void *im0,
                                                        void *im1, void const *standard, uint32_t const N,

@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "arena.h"
 #include "profile.h"
+#include "scratch.h"
 #include "../../include/tfhe_hip_backend.h"
 
 #include <algorithm>
@@ -473,20 +474,11 @@ static uint32_t G0(const CudaStreamsFFI &s) { return s.gpu_indexes ? s.gpu_index
 // uploads act on the thread's CURRENT device, which a host alternating between GPUs may have left elsewhere
 static void first_gpu(const CudaStreamsFFI &s) { HX_CHECK(hipSetDevice((int)G0(s))); }
 
-// ------------------------------------------------------------------ scratch protocol
-// Every object handed out through `int8_t **mem_ptr` starts with this header; a struct M of the layer derives from it,
-// names its kMagic, fills itself in a callable given to scratch_create and frees what it declares in
-// release(const CudaStreamsFFI &).  Only the header of the object that was handed out is stamped and checked: a
-// scratch that is a member of another one keeps its release() and nothing else of the protocol.
-struct ScratchHeader {
-  uint32_t magic = 0;      // M::kMagic while the object is alive (offset 0: scratch_magic tells BoolMulMem from MulMem)
-  bool size_only = false;  // created with allocate_gpu_memory = false: sized, nothing allocated
-};
-static uint32_t scratch_magic(const int8_t *mem_ptr) {
-  return mem_ptr ? reinterpret_cast<const ScratchHeader *>(mem_ptr)->magic : 0;
-}
-
-// create: the only place that sets the thread's dry-run state; `fill` allocates through radix_alloc / dev_upload.
+// ------------------------------------------------------------------ scratch protocol (scratch.h) on a stream set
+// A struct M of the layer fills itself in a callable given to scratch_create and frees what it declares in
+// release(const CudaStreamsFFI &).
+// create: the only place that sets the thread's dry-run state; `fill` allocates through radix_alloc / dev_upload.  (The core
+// scratch functions a fill calls neither read nor reset that state.)
 // Known and kept, a fix changes returned values: a size query counts the index uploads, a real creation does not
 // (dev_upload), so the two modes return different numbers; the reference returns one size_tracker in both.
 template <class M, class Fill>
@@ -497,36 +489,15 @@ static uint64_t scratch_create(const CudaStreamsFFI &s, int8_t **mem_ptr, bool a
   t_dry = !allocate_gpu_memory;
   t_bytes = 0;
   M *m = new M();
-  m->magic = M::kMagic;
   fill(*m);
-  m->size_only = t_dry;
   t_dry = false;
-  *mem_ptr = reinterpret_cast<int8_t *>(static_cast<ScratchHeader *>(m));
+  scratch_hand_out(m, allocate_gpu_memory, mem_ptr);
   return t_bytes;
-}
-template <class M>
-static M *scratch_cast(int8_t *mem_ptr, const char *who) {
-  auto *h = reinterpret_cast<ScratchHeader *>(mem_ptr);
-  HX_PANIC_IF_FALSE(h && h->magic == M::kMagic, "%s: foreign scratch pointer", who);
-  return static_cast<M *>(h);
-}
-// use: the scratch a launch was handed, refused if it is of another kind or was only sized
-template <class M>
-static M *scratch_use(int8_t *mem_ptr, const char *who) {
-  M *m = scratch_cast<M>(mem_ptr, who);
-  HX_PANIC_IF_FALSE(!m->size_only, "%s: scratch was created with allocate_gpu_memory=false", who);
-  return m;
 }
 // destroy (`who` = "cleanup <operation>"): the first stream is idle before anything is freed
 template <class M>
 static void scratch_destroy(const CudaStreamsFFI &s, int8_t **mem_ptr, const char *who) {
-  first_gpu(s);
-  M *m = scratch_cast<M>(*mem_ptr, who);
-  HX_CHECK(hipStreamSynchronize(S0(s)));
-  m->release(s);
-  m->magic = 0;
-  delete m;
-  *mem_ptr = nullptr;
+  tfhe_hip::scratch_destroy<M>(G0(s), S0(s), mem_ptr, who, kForeignScratch, s);
 }
 
 // ------------------------------------------------------------------ apply a univariate LUT

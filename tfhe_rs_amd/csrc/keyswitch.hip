@@ -12,6 +12,7 @@
 // elements are staged in LDS and broadcast-read.
 #include "kernels.h"
 #include "arena.h"
+#include "ranges.h"
 #include <mutex>
 #include <vector>
 
@@ -788,11 +789,9 @@ void ksm_invalidate_range(int device, const void *p, size_t bytes) {
   std::vector<KsmEntry> dead;
   {
     std::lock_guard<std::mutex> lock(g_ksm_mutex);
-    const char *lo = (const char *)p, *hi = lo + (bytes ? bytes : 1);
     for (size_t i = 0; i < g_ksm_cache.size();) {
       KsmEntry &e = g_ksm_cache[i];
-      const char *klo = (const char *)e.ksk, *khi = klo + e.ksk_bytes;
-      if (e.device == device && klo < hi && lo < khi) {
+      if (range_overlaps(e.device, e.ksk, e.ksk_bytes, device, p, bytes)) {
         dead.push_back(e);
         g_ksm_cache.erase(g_ksm_cache.begin() + i);
       } else {

@@ -676,39 +676,4 @@ __global__ void test_f128_cmul_kernel(double *out, const double *x, const double
   out[3 * count + i] = r.im.lo;
 }
 
-// ------------------------------------------------------------------------------------------------ converted keys
-// What hip_convert_lwe_programmable_bootstrap_key_128_async wrote where: a bootstrap whose key pointer is a converted
-// key of other sizes is refused.  An entry goes when its memory is dropped or overwritten.
-struct Key128Record {
-  int device;
-  const void *key;
-  size_t bytes;
-  uint32_t n, glwe_dim, level, N;
-};
-inline std::mutex g_key128_mu;
-inline std::vector<Key128Record> g_key128;
-inline void key128_forget_range(int device, const void *p, size_t bytes) {
-  if (p == nullptr) return;
-  std::lock_guard<std::mutex> lk(g_key128_mu);
-  const char *lo = (const char *)p, *hi = lo + (bytes ? bytes : 1);
-  for (size_t i = 0; i < g_key128.size();) {
-    const char *klo = (const char *)g_key128[i].key, *khi = klo + g_key128[i].bytes;
-    if (g_key128[i].device == device && klo < hi && lo < khi) g_key128.erase(g_key128.begin() + i);
-    else ++i;
-  }
-}
-inline void key128_record(const Key128Record &r) {
-  std::lock_guard<std::mutex> lk(g_key128_mu);
-  g_key128.push_back(r);
-}
-inline bool key128_find(int device, const void *key, Key128Record *out) {
-  std::lock_guard<std::mutex> lk(g_key128_mu);
-  for (const Key128Record &r : g_key128)
-    if (r.device == device && r.key == key) {
-      *out = r;
-      return true;
-    }
-  return false;
-}
-
 }  // namespace tfhe_hip
