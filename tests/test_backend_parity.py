@@ -1187,6 +1187,52 @@ def test_keyswitch_64_32_matrix_core_path(kind, p):
     assert np.array_equal(got[0], ref)
 
 
+# (base_log, level) per key width: level_pad 1, 2, 16 and — (3, 11) — the 64-bit decomposition at pad 16
+_KS_EVERY_PADDING = [(bits, ks) for bits, rows in ((64, [(6, 1), (5, 2), (2, 9), (3, 11)]), (32, [(6, 1), (5, 2), (2, 9), (2, 16)]))
+                     for ks in rows]
+
+
+@pytest.mark.parametrize("kind", BACKENDS)
+@pytest.mark.parametrize("bits,ks", _KS_EVERY_PADDING, ids=lambda v: "u%d" % v if isinstance(v, int) else "ks_%dx%d" % v)
+def test_keyswitch_matrix_core_path_at_every_level_padding(kind, bits, ks):
+    """The other parity tests reach 4 and 8 levels per mask word only.  Here 1, 2 and 16 (9, 11 and 16 levels padded or
+    not), 64- and 32-bit keys, n_in = 2048, n_out = 12: 7 LWEs (four waves split K, key parts over the grid's y), 70 / 71 (a wave
+    per tile, key parts over z) and 131 with choice 3 (digit pass + GEMM) against the oracle, bit for bit, and against
+    the scalar kernels where they accept the level count (<= 8).  The path taken is asserted; nothing is decrypted:
+    these decompositions are not noise-sized."""
+    p = dataclasses.replace(TOY_2048, name="toy_k1_N2048_ks%dx%d" % ks, ks_base_log=ks[0], ks_level=ks[1])
+    c = ctx(kind, TOY_2048, "fft64")          # the secret keys and the streams; the keyswitch key is this row's own
+    st = c.streams
+    lib = use_backend(kind)
+    cts = encrypt_big(p, c.keys, [m % p.plaintext_modulus for m in range(131)], seed=61)
+    if bits == 64:
+        ksk = orc.gen_ksk(0x6b73 + ks[1], c.keys.glwe_sk, c.keys.lwe_sk, ks[0], ks[1], p.lwe_noise)
+        ref = orc.keyswitch_batch(cts, ksk, p.big_n, p.n, ks[0], ks[1])
+    else:
+        ksk = _ks32_key(p, c.keys, 60 + ks[1])
+        ref = np.stack([orc.keyswitch_64_32(ct, ksk, p.big_n, p.n, ks[0], ks[1]) for ct in cts])
+    d_ksk = gpu.CudaLweKeyswitchKey.from_lwe_keyswitch_key(ksk, p.big_n, p.n, ks[0], ks[1], st)
+    assert d_ksk.scalar_bits == bits
+
+    def run(count, choice):
+        d_in = gpu.CudaLweCiphertextList.from_lwe_ciphertext_list(cts[:count], st)
+        d_out = gpu.CudaLweCiphertextList.new(p.n, count, st, dtype=ref.dtype)
+        idx = gpu.CudaVec.from_cpu_async(np.arange(count, dtype=np.uint64), st)
+        lib.hip_backend_set_keyswitch_kernel(choice)
+        gpu.cuda_keyswitch_lwe_ciphertext(d_ksk, d_in, d_out, idx, idx, True, st)
+        return d_out.to_lwe_ciphertext_list(st), lib.hip_backend_last_keyswitch_path()
+
+    try:
+        for count, choice, path in ((7, 0, 1), (70 if bits == 64 else 71, 0, 1), (131, 3, 2)):
+            out, took = run(count, choice)
+            assert took == path, (count, took)
+            assert np.array_equal(out, ref[:count]), count
+            if ks[1] <= 8:   # above that the scalar kernels refuse by design
+                assert np.array_equal(run(count, 1)[0], ref[:count]), count
+    finally:
+        lib.hip_backend_set_keyswitch_kernel(0)
+
+
 # ------------------------------------------------------------------ empty and boundary-size batches
 @pytest.mark.parametrize("kind", BACKENDS)
 def test_empty_batches_are_noops(kind):

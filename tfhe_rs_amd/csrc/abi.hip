@@ -572,9 +572,9 @@ void hip_keyswitch_programmable_bootstrap_chain_64_async(void *stream, uint32_t 
   b->emitted.valid = false;  // the operands described the INPUT of this call; its output replaces them below or not
   // ---- bootstrap, with the emission when the throughput kernel takes the launch
   // The operands only pay off where the NEXT keyswitch takes the GEMM path (keyswitch_mfma consumes them from
-  // g_keyswitch_gemm_min LWEs on): below that, the flag changes nothing.
+  // the batch size of keyswitch_batch_takes_gemm on): below that, the flag changes nothing.
   if ((flags & HIP_KSPBS_EMIT_DIGITS) && emittable && num_many_lut == 1 && polynomial_size == 2048 && glwe_dimension == 1 &&
-      num_samples >= g_keyswitch_gemm_min.load()) {
+      keyswitch_batch_takes_gemm(num_samples)) {
     const size_t a_bytes = (size_t)((b->max_samples + 31) / 32) * steps * 1024;
     const size_t need = a_bytes + (size_t)((b->max_samples + 31) / 32) * 32 * sizeof(int32_t);
     if (b->emit_bytes < need && !stream_is_capturing(S(stream))) {
@@ -1088,11 +1088,7 @@ void hip_backend_allocator_stats(uint32_t gpu_index, uint64_t *out7) {
 }
 uint64_t hip_backend_redzone_checks(uint32_t gpu_index) { return arena_redzone_checks((int)gpu_index); }
 uint64_t hip_backend_profile_ranges(void) { return profile_range_count(); }
-void hip_backend_set_keyswitch_kernel(uint32_t which) {
-  g_keyswitch_use_mfma.store(which != 1);
-  g_keyswitch_split_digits.store(which != 2);
-  g_keyswitch_gemm_min.store(which == 3 ? 129u : 769u);
-}
+void hip_backend_set_keyswitch_kernel(uint32_t which) { keyswitch_select_kernel(which); }
 void hip_backend_set_ntt_kernel(uint32_t which) { g_ntt_kernel_serial = (which == 1); }
 void hip_backend_set_multibit_latency_groups(uint32_t groups) { g_multibit_latency_groups.store(groups); }
 uint32_t hip_backend_last_pbs_kernel(void) { return g_last_pbs_kernel.load(); }
@@ -1100,8 +1096,8 @@ void hip_backend_last_pbs_instantiation(uint32_t *out8) {
   out8[0] = g_last_pbs_kernel.load();
   get_pbs_instantiation(out8 + 1);
 }
-uint32_t hip_backend_last_keyswitch_path(void) { return g_last_keyswitch_path.load(); }
-void hip_backend_set_keyswitch_kparts(uint32_t parts) { g_keyswitch_kparts.store(parts ? parts : 1); }
+uint32_t hip_backend_last_keyswitch_path(void) { return keyswitch_last_path(); }
+void hip_backend_set_keyswitch_kparts(uint32_t parts) { keyswitch_set_kparts(parts); }
 const char *hip_backend_version(void) {
 #if defined(TFHE_HIPEMU)
   return "tfhe-hip-backend 0.1 (HOST EMULATION - test build, not a product)";

@@ -25,6 +25,7 @@ void scratch_free(void *p);  // whichever device's arena the block belongs to
 // hipMalloc / hipFree (a free that synchronises the device) — arena blocks too in red-zone mode (TFHE_HIP_ARENA_REDZONE=1)
 void *device_alloc_sync(size_t bytes);
 void device_free_sync(void *p);
+bool stream_is_capturing(hipStream_t st);  // the stream is recording a graph (nothing may allocate)
 uint64_t arena_redzone_checks(int device);  // canary checks made so far (0 when the mode is off)
 
 }  // namespace tfhe_hip

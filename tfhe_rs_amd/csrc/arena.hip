@@ -30,7 +30,6 @@
 // the test suites, never for throughput.  The library's other device allocations (cuda_malloc, key staging, keyswitch
 // planes and scratches) go through the arena too in this mode (device_alloc_sync).
 #include "arena.h"
-#include "kernels.h"
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -235,6 +234,17 @@ size_t trim_locked(DeviceArena &a) {
 }
 
 }  // namespace
+
+bool stream_is_capturing(hipStream_t st) {
+#if defined(TFHE_HIPEMU)
+  (void)st;
+  return false;
+#else
+  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &status) != hipSuccess) return false;
+  return status != hipStreamCaptureStatusNone;
+#endif
+}
 
 void *arena_alloc(int device, size_t bytes, hipStream_t stream, bool scratch) {
   HX_PANIC_IF_FALSE(device >= 0 && device < 16, "cuda_malloc_async: device index %d", device);

@@ -63,12 +63,12 @@ void launch_packing_keyswitch(hipStream_t st, uint64_t *out, uint64_t *rows, con
 // cache of the matrix-core key layout (keyswitch.hip): drop what overlaps device memory about to be freed / written
 void ksm_invalidate_range(int device, const void *p, size_t bytes);
 size_t ksm_cache_entries();
-extern std::atomic<bool> g_keyswitch_use_mfma;
-extern std::atomic<bool> g_keyswitch_split_digits;
-extern std::atomic<uint32_t> g_last_keyswitch_path;
-extern std::atomic<uint32_t> g_keyswitch_kparts;
-extern std::atomic<uint32_t> g_keyswitch_gemm_min;
-bool stream_is_capturing(hipStream_t st);  // keyswitch.hip: the stream is recording a graph (nothing may allocate)
+// kernel selection (keyswitch.hip), behind the hip_backend_* test hooks of the same names: which = 0 automatic, 1 scalar
+// kernels, 2 the one-launch matrix-core kernel at every batch size, 3 digit pass + GEMM from 129 LWEs on
+void keyswitch_select_kernel(uint32_t which);
+uint32_t keyswitch_last_path();  // 0 scalar kernels, 1 one-launch matrix-core kernel, 2 digit pass + GEMM, 3 GEMM on emitted digits
+void keyswitch_set_kparts(uint32_t parts);
+bool keyswitch_batch_takes_gemm(uint32_t num_samples);  // a batch of this size takes the GEMM path (emitted digits pay off)
 void ksd_release_stream(int device, hipStream_t st);  // the large-batch keyswitch's per-stream scratch
 extern bool g_ntt_kernel_serial;
 

@@ -3,10 +3,19 @@
 // Semantics: cc/algorithms/lwe_keyswitch.rs:137-227 — out = (0,…,0,b_in); for every input
 // mask element i and level (l first): out -= digit_{i,level} * KSK[i][level][:].
 // Replaces backends/tfhe-cuda-backend/cuda/src/crypto/keyswitch.cuh:200-560 (per-LWE kernel
-// and the u64 "GEMM" variant).  Integer sums mod 2^64 are order-independent, so the tiling
+// and the u64 "GEMM" variant).  Integer sums mod 2^64 are order-independent, so every tiling
 // below is bit-exact by construction.
 //
-// Shape (HBM/L2-bound streaming of the 60 MB key): a workgroup owns TB samples x 256 output
+// Four paths, chosen per launch (keyswitch_mfma; hip_backend_last_keyswitch_path reports which one a launch took):
+//   0  the scalar kernels (keyswitch_small_base_kernel, keyswitch_kernel, keyswitch_64_32_kernel): any decomposition of
+//      up to KS_MAXL levels — where the matrix-core paths decline the shape (ksm_shape) or are switched off;
+//   1  ks_mfma_kernel: one launch on the int8 matrix cores, the digits rebuilt for every column tile — small and medium
+//      batches;
+//   2  ks_digits_kernel + ks_gemm_kernel: the digits once, then an LDS-staged int8 GEMM — from KSD_MIN_SAMPLES LWEs on;
+//   3  ks_gemm_kernel alone, on digits that the bootstrap in front of the keyswitch emitted (KsDigits).
+// The packing keyswitch of the compression path (launch_packing_keyswitch) is launch_keyswitch plus an epilogue kernel.
+//
+// Shape of the scalar kernels (HBM/L2-bound streaming of the 60 MB key): a workgroup owns TB samples x 256 output
 // columns; KSK rows are read once per workgroup with 8-byte coalesced loads (lane = column)
 // and reused across the TB samples held in registers; the signed digits of a chunk of IC mask
 // elements are staged in LDS and broadcast-read.
@@ -14,6 +23,7 @@
 #include "arena.h"
 #include "ranges.h"
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace tfhe_hip {
@@ -22,14 +32,41 @@ constexpr int KS_TPB = 256;  // output columns per workgroup
 constexpr int KS_TB = 16;    // samples per workgroup
 constexpr int KS_IC = 32;    // mask elements decomposed per LDS stage
 constexpr int KS_MAXL = 8;   // max levels staged (level_count <= 8 for every shortint set)
-// kernel selection (hip_backend_set_keyswitch_kernel: 0 = automatic, 1 = scalar kernels, 2 = the one-launch matrix-core
-// kernel at every batch size, 3 = digit pass + GEMM from 129 LWEs on; tests and measurements)
-std::atomic<bool> g_keyswitch_use_mfma{true};       // false: scalar kernels only
-std::atomic<bool> g_keyswitch_split_digits{true};   // false: never the digit pass + GEMM
-std::atomic<uint32_t> g_last_keyswitch_path{0};     // which path the last launch took: 0 scalar kernels, 1 one-launch
-                                                    // matrix-core kernel, 2 digit pass + GEMM, 3 GEMM on emitted digits
-std::atomic<uint32_t> g_keyswitch_kparts{8};        // workgroups per column tile of the one-launch kernel at small
-                                                    // batches (hip_backend_set_keyswitch_kparts)
+
+// stage digits: one (sample, mask element) pair per thread iteration.  dig: [KS_IC][level][KS_TB], a digit d stored as
+// enc(d); the mask elements i0 .. i0 + ic - 1 of the samples s0 .. s0 + ns - 1, every other pair of the stage enc(0)
+template <typename StoreT, typename Enc>
+HX_DEV void ks_stage_digits(StoreT *dig, const uint64_t *lwe_in, const uint64_t *in_idx, uint32_t n_in, uint32_t i0,
+                            uint32_t ic, uint32_t s0, uint32_t ns, uint32_t base_log, uint32_t level, Enc enc) {
+  for (uint32_t w = threadIdx.x; w < (uint32_t)(KS_IC * KS_TB); w += KS_TPB) {
+    const uint32_t ii = w / KS_TB, s = w - ii * KS_TB;
+    uint64_t st = 0;
+    const bool valid = ii < ic && s < ns;
+    if (valid) {
+      const uint64_t x = lwe_in[(size_t)in_idx[s0 + s] * (n_in + 1) + i0 + ii];
+      st = decomp_init_state(x, base_log, level);
+    }
+    for (uint32_t lv = 0; lv < level; ++lv) {
+      const int64_t d = valid ? decompose_one_level(base_log, st) : 0;
+      dig[(ii * level + lv) * KS_TB + s] = enc(d);
+    }
+  }
+}
+
+// what the output's last column receives of the input body: the body itself, or — 32-bit output — the closest
+// representable on 32 bits, one level (decomposer.rs:25-50), shifted down to the output width
+template <typename OutT>
+HX_DEV uint64_t ks_body(const uint64_t *lwe_in, const uint64_t *in_idx, uint32_t n_in, uint32_t sample) {
+  const uint64_t b = lwe_in[(size_t)in_idx[sample] * (n_in + 1) + n_in];
+  return sizeof(OutT) == 8 ? b : ((b >> 31) + 1) >> 1;
+}
+// column `col` of output `sample` of a scalar kernel: v, plus the body in the last column
+template <typename OutT>
+HX_DEV void ks_store(OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in, const uint64_t *in_idx, uint32_t n_in,
+                     uint32_t n_out, uint32_t col, uint32_t sample, OutT v) {
+  if (col == n_out) v += (OutT)ks_body<OutT>(lwe_in, in_idx, n_in, sample);
+  lwe_out[(size_t)out_idx[sample] * (n_out + 1) + col] = v;
+}
 
 // DigitT: int32_t when base_log <= 31 (every shortint set), int64_t for wider bases
 template <typename DigitT>
@@ -51,20 +88,7 @@ __global__ void __launch_bounds__(KS_TPB) keyswitch_kernel(uint64_t *lwe_out, co
 
   for (uint32_t i0 = 0; i0 < n_in; i0 += KS_IC) {
     const uint32_t ic = (n_in - i0 < (uint32_t)KS_IC) ? n_in - i0 : KS_IC;
-    // stage digits: one (sample, mask element) pair per thread iteration
-    for (uint32_t w = tid; w < (uint32_t)(KS_IC * KS_TB); w += KS_TPB) {
-      const uint32_t ii = w / KS_TB, s = w - ii * KS_TB;
-      uint64_t st = 0;
-      const bool valid = ii < ic && s < ns;
-      if (valid) {
-        const uint64_t x = lwe_in[(size_t)in_idx[s0 + s] * (n_in + 1) + i0 + ii];
-        st = decomp_init_state(x, base_log, level);
-      }
-      for (uint32_t lv = 0; lv < level; ++lv) {
-        const int64_t d = valid ? decompose_one_level(base_log, st) : 0;
-        dig[(ii * level + lv) * KS_TB + s] = (DigitT)d;
-      }
-    }
+    ks_stage_digits(dig, lwe_in, in_idx, n_in, i0, ic, s0, ns, base_log, level, [](int64_t d) { return (DigitT)d; });
     __syncthreads();
     if (active) {
       for (uint32_t ii = 0; ii < ic; ++ii)
@@ -77,13 +101,8 @@ __global__ void __launch_bounds__(KS_TPB) keyswitch_kernel(uint64_t *lwe_out, co
     }
     __syncthreads();
   }
-  if (active) {
-    for (uint32_t s = 0; s < ns; ++s) {
-      uint64_t v = accv[s];
-      if (col == n_out) v += lwe_in[(size_t)in_idx[s0 + s] * (n_in + 1) + n_in];
-      lwe_out[(size_t)out_idx[s0 + s] * (n_out + 1) + col] = v;
-    }
-  }
+  if (active)
+    for (uint32_t s = 0; s < ns; ++s) ks_store(lwe_out, out_idx, lwe_in, in_idx, n_in, n_out, col, s0 + s, accv[s]);
 }
 
 // Small bases (base_log + 33 + log2(n_in * level) <= 64, true for every shortint set: base_log 2..5):
@@ -113,22 +132,11 @@ __global__ void __launch_bounds__(KS_TPB) keyswitch_small_base_kernel(uint64_t *
 
   for (uint32_t i0 = 0; i0 < n_in; i0 += KS_IC) {
     const uint32_t ic = (n_in - i0 < (uint32_t)KS_IC) ? n_in - i0 : KS_IC;
-    for (uint32_t w = tid; w < (uint32_t)(KS_IC * KS_TB); w += KS_TPB) {
-      const uint32_t ii = w / KS_TB, s = w - ii * KS_TB;
-      uint64_t st = 0;
-      const bool valid = ii < ic && s < ns;
-      if (valid) {
-        const uint64_t x = lwe_in[(size_t)in_idx[s0 + s] * (n_in + 1) + i0 + ii];
-        st = decomp_init_state(x, base_log, level);
-      }
-      for (uint32_t lv = 0; lv < level; ++lv) {
-        // padding rows/samples get d' = B/2 (d = 0): they cancel against the column-sum term only if the
-        // key row is also skipped, so padded mask elements are never multiplied (loop bound ic below) and
-        // padded samples are never stored
-        const int64_t d = valid ? decompose_one_level(base_log, st) : 0;
-        dig[(ii * level + lv) * KS_TB + s] = (uint32_t)((int32_t)d + (int32_t)half_b);
-      }
-    }
+    // padding rows/samples get d' = B/2 (d = 0): they cancel against the column-sum term only if the
+    // key row is also skipped, so padded mask elements are never multiplied (loop bound ic below) and
+    // padded samples are never stored
+    ks_stage_digits(dig, lwe_in, in_idx, n_in, i0, ic, s0, ns, base_log, level,
+                    [half_b](int64_t d) { return (uint32_t)((int32_t)d + (int32_t)half_b); });
     __syncthreads();
     if (active) {
       for (uint32_t ii = 0; ii < ic; ++ii)
@@ -148,11 +156,8 @@ __global__ void __launch_bounds__(KS_TPB) keyswitch_small_base_kernel(uint64_t *
   }
   if (active) {
     const uint64_t corr = (uint64_t)half_b * wsum;
-    for (uint32_t s = 0; s < ns; ++s) {
-      uint64_t v = corr - (acc_lo[s] + (acc_hi[s] << 32));
-      if (col == n_out) v += lwe_in[(size_t)in_idx[s0 + s] * (n_in + 1) + n_in];
-      lwe_out[(size_t)out_idx[s0 + s] * (n_out + 1) + col] = v;
-    }
+    for (uint32_t s = 0; s < ns; ++s)
+      ks_store(lwe_out, out_idx, lwe_in, in_idx, n_in, n_out, col, s0 + s, corr - (acc_lo[s] + (acc_hi[s] << 32)));
   }
 }
 
@@ -180,19 +185,7 @@ __global__ void __launch_bounds__(KS_TPB) keyswitch_64_32_kernel(uint32_t *lwe_o
 
   for (uint32_t i0 = 0; i0 < n_in; i0 += KS_IC) {
     const uint32_t ic = (n_in - i0 < (uint32_t)KS_IC) ? n_in - i0 : KS_IC;
-    for (uint32_t w = tid; w < (uint32_t)(KS_IC * KS_TB); w += KS_TPB) {
-      const uint32_t ii = w / KS_TB, s = w - ii * KS_TB;
-      uint64_t st = 0;
-      const bool valid = ii < ic && s < ns;
-      if (valid) {
-        const uint64_t x = lwe_in[(size_t)in_idx[s0 + s] * (n_in + 1) + i0 + ii];
-        st = decomp_init_state(x, base_log, level);
-      }
-      for (uint32_t lv = 0; lv < level; ++lv) {
-        const int64_t d = valid ? decompose_one_level(base_log, st) : 0;
-        dig[(ii * level + lv) * KS_TB + s] = (uint32_t)(uint64_t)d;
-      }
-    }
+    ks_stage_digits(dig, lwe_in, in_idx, n_in, i0, ic, s0, ns, base_log, level, [](int64_t d) { return (uint32_t)(uint64_t)d; });
     __syncthreads();
     if (active) {
       for (uint32_t ii = 0; ii < ic; ++ii)
@@ -205,17 +198,8 @@ __global__ void __launch_bounds__(KS_TPB) keyswitch_64_32_kernel(uint32_t *lwe_o
     }
     __syncthreads();
   }
-  if (active) {
-    for (uint32_t s = 0; s < ns; ++s) {
-      uint32_t v = accv[s];
-      if (col == n_out) {
-        const uint64_t b = lwe_in[(size_t)in_idx[s0 + s] * (n_in + 1) + n_in];
-        // closest representable on 32 bits, one level (decomposer.rs:25-50), shifted down to the output width
-        v += (uint32_t)(((b >> 31) + 1) >> 1);
-      }
-      lwe_out[(size_t)out_idx[s0 + s] * (n_out + 1) + col] = v;
-    }
-  }
+  if (active)
+    for (uint32_t s = 0; s < ns; ++s) ks_store(lwe_out, out_idx, lwe_in, in_idx, n_in, n_out, col, s0 + s, accv[s]);
 }
 
 // ------------------------------------------------------------------ keyswitch on the int8 matrix cores
@@ -226,8 +210,8 @@ __global__ void __launch_bounds__(KS_TPB) keyswitch_64_32_kernel(uint32_t *lwe_o
 // and sum_k d'*b'_p is exactly what v_mfma_i32_32x32x32_i8 computes (|.| <= B * 128 * K < 2^31).  All integer,
 // so the result equals the scalar kernels' bit for bit.
 //   * ksk_planes_kernel: key -> [k block of 16][column tile][plane][column][16 bytes]  (+ column sums), so that a
-//     lane's B operand is one 16-byte load and a wave's loads are contiguous; redone at every call (60 MB in,
-//     60 MB out, ~40 us) because the C ABI hands the key over as a plain device array.
+//     lane's B operand is one 16-byte load and a wave's loads are contiguous; run once per key (60 MB in, 60 MB out,
+//     ~40 us), its output cached for as long as the key's device memory stands (ksm_planes below).
 //   * ks_mfma_kernel: a wave owns 32 samples x 32 columns x 8 planes (8 accumulators of 16 VGPRs); per step of
 //     32 k it decomposes 16/level mask words of its row into the A operand (no LDS: a lane's 16 consecutive k
 //     ARE the digits of consecutive mask words) and issues 8 MFMAs.
@@ -281,13 +265,91 @@ template <typename KeyT>
 __global__ void __launch_bounds__(64) ksk_fingerprint_kernel(uint64_t *fp, const KeyT *ksk, size_t words) {
   fp[threadIdx.x] = (uint64_t)ksk[ksm_fp_index((int)threadIdx.x, words)];
 }
+// first thing in both matrix-core kernels (the fingerprint is stored behind the column sums)
+template <typename KeyT>
+HX_DEV void ksm_check_fingerprint(const uint64_t *colsum, uint32_t col_tiles, const KeyT *ksk_raw, size_t ksk_words) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < KSM_FP) {  // the planes must still be this key's
+    const uint64_t *fp = colsum + (size_t)col_tiles * KSM_CT;
+    if ((uint64_t)ksk_raw[ksm_fp_index((int)threadIdx.x, ksk_words)] != fp[threadIdx.x]) __builtin_trap();
+  }
+}
 
+// A operand of one lane and step: k = st*32 + h*16 + j  <->  mask word (k / LEVEL), level index (k % LEVEL), level l first —
+// the shifted digits of the lane's 16 / LEVEL mask words xc, their sum added to my_sa
 // PADDED: `level` < LEVEL real levels per mask word, the rest zero digits against zero key rows
+template <int LEVEL, bool PADDED>
+HX_DEV hx_i8x16 ksm_build_a(const uint64_t (&xc)[16 / LEVEL], uint32_t base_log, uint32_t level, bool narrow,
+                            uint32_t half_b, int32_t &my_sa) {
+  constexpr int WORDS = 16 / LEVEL;
+  uint32_t bytes[16];
+  HX_UNROLL
+  for (int q = 0; q < WORDS; ++q) {
+    const uint32_t real = PADDED ? level : (uint32_t)LEVEL;
+    if (narrow) {  // wave-uniform: the decomposition on 32-bit registers (arith.h)
+      int32_t state = decomp_init_state32((uint32_t)(xc[q] >> 32), base_log, real);
+      HX_UNROLL
+      for (int lv = 0; lv < LEVEL; ++lv) {
+        // padded levels: digit 0 against a zero key row (its two shift corrections cancel)
+        const int32_t d = ((!PADDED || (uint32_t)lv < level) ? decompose_one_level32(base_log, state) : 0) + (int32_t)half_b;
+        bytes[q * LEVEL + lv] = (uint32_t)d;
+        my_sa += d;
+      }
+    } else {
+      uint64_t state = decomp_init_state(xc[q], base_log, real);
+      HX_UNROLL
+      for (int lv = 0; lv < LEVEL; ++lv) {
+        const int32_t d = ((!PADDED || (uint32_t)lv < level) ? (int32_t)decompose_one_level(base_log, state) : 0) + (int32_t)half_b;
+        bytes[q * LEVEL + lv] = (uint32_t)d;
+        my_sa += d;
+      }
+    }
+  }
+  hx_i8x16 av;
+  HX_UNROLL
+  for (int q = 0; q < 4; ++q)
+    av.w[q] = (int32_t)(bytes[4 * q] | (bytes[4 * q + 1] << 8) | (bytes[4 * q + 2] << 16) | (bytes[4 * q + 3] << 24));
+  return av;
+}
+
+// What a lane of either matrix-core kernel stores.  It holds column ct*32 + (lane & 31) of the rows orow(r) of sample tile
+// `stile` in acc[plane].v[r]; sum_a(orow, sample) is the row's sum of shifted digits.  Of `kparts` workgroups that share
+// the K dimension, part 0 adds the shift correction and the body; more than one part: into the zeroed output, with atomics
+template <typename OutT, typename SumA>
+HX_DEV void ksm_epilogue(const hx_i32x16 (&acc)[sizeof(OutT)], SumA sum_a, uint32_t kpart, uint32_t kparts, int lane,
+                         OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in, const uint64_t *in_idx,
+                         const uint64_t *colsum, uint32_t n_in, uint32_t n_out, uint32_t base_log, uint32_t num_samples,
+                         uint32_t ct, uint32_t stile) {
+  constexpr int PLANES = (int)sizeof(OutT);
+  const uint32_t col = ct * KSM_CT + (lane & 31);
+  if (col > n_out) return;
+  const uint32_t half_b = 1u << (base_log - 1);
+  const uint64_t corr = (uint64_t)half_b * colsum[col];
+  HX_UNROLL
+  for (int r = 0; r < 16; ++r) {
+    const int orow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const uint32_t so = stile * 32 + orow;
+    if (so >= num_samples) continue;
+    const int64_t sum = sum_a(orow, so);
+    uint64_t v = 0;
+    HX_UNROLL
+    for (int p = 0; p < PLANES; ++p) v += (uint64_t)((int64_t)acc[p].v[r] + 128 * sum) << (8 * p);
+    uint64_t o = (kpart == 0 ? corr : 0) - v;  // the part's share: wrapping sums, any order
+    // 32-bit output: the body rounded to the closest multiple of 2^32, as keyswitch_64_32_kernel does
+    if (col == n_out && kpart == 0) o += ks_body<OutT>(lwe_in, in_idx, n_in, so);
+    OutT *dst = &lwe_out[(size_t)out_idx[so] * (n_out + 1) + col];
+    if (kparts > 1) {
+      if constexpr (sizeof(OutT) == 8) atomicAdd((unsigned long long *)dst, (unsigned long long)o);
+      else atomicAdd((unsigned int *)dst, (unsigned int)o);
+    } else {
+      *dst = (OutT)o;
+    }
+  }
+}
+
 // OutT = uint32_t: the 64->32 keyswitch (4 planes, arithmetic mod 2^32, body rounded to 32 bits)
 // KSPLIT = 4 (batches of at most 32 LWEs: one tile of samples per workgroup): the four waves of a workgroup take a
 // quarter of the K dimension each for the SAME tile and add their integer accumulators through LDS — the key is
 // streamed four times faster for the latency-bound rounds of the radix layer (7 to 32 blocks)
-#define PLANES_OF(T) ((int)sizeof(T))
 template <int LEVEL, bool PADDED, typename OutT, int KSPLIT = 1>
 __global__ void __launch_bounds__(256) ks_mfma_kernel(OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
                                                       const uint64_t *in_idx, const int8_t *planes,
@@ -296,12 +358,9 @@ __global__ void __launch_bounds__(256) ks_mfma_kernel(OutT *lwe_out, const uint6
                                                       uint32_t level,  // level <= LEVEL (the padded count)
                                                       const OutT *ksk_raw, size_t ksk_words) {
   constexpr int PLANES = (int)sizeof(OutT);
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < KSM_FP) {  // the planes must still be this key's
-    const uint64_t *fp = colsum + (size_t)col_tiles * KSM_CT;
-    if ((uint64_t)ksk_raw[ksm_fp_index((int)threadIdx.x, ksk_words)] != fp[threadIdx.x]) __builtin_trap();
-  }
+  ksm_check_fingerprint(colsum, col_tiles, ksk_raw, ksk_words);
   __shared__ int32_t sa[4][2][32];  // per wave: sum of the shifted digits of every row, per k half
-  __shared__ int32_t red[KSPLIT > 1 ? 2 : 1][KSPLIT > 1 ? PLANES_OF(OutT) : 1][KSPLIT > 1 ? 16 : 1][64];
+  __shared__ int32_t red[KSPLIT > 1 ? 2 : 1][KSPLIT > 1 ? PLANES : 1][KSPLIT > 1 ? 16 : 1][64];
   // KSPLIT = 4 with a 64-bit key: 64 KiB of static LDS for the two-round reduction — gfx950 only (160 KiB per CU; this
   // library is built for that target alone, Makefile ARCH), two workgroups per CU
   static_assert(sizeof(red) + sizeof(sa) <= 160 * 1024 / 2, "split-K reduction buffers: more than half of a gfx950 CU's LDS");
@@ -335,9 +394,6 @@ __global__ void __launch_bounds__(256) ks_mfma_kernel(OutT *lwe_out, const uint6
     HX_UNROLL
     for (int q = 0; q < WORDS; ++q) xn[q] = x[(st_lo * 32 + h * 16) / LEVEL + q];
     for (uint32_t st = st_lo; st < st_hi; ++st) {
-      // A operand: k = st*32 + h*16 + j  <->  mask word (k / LEVEL), level index (k % LEVEL), level l first
-      hx_i8x16 av;
-      uint32_t bytes[16];
       uint64_t xc[WORDS];
       HX_UNROLL
       for (int q = 0; q < WORDS; ++q) xc[q] = xn[q];
@@ -357,33 +413,7 @@ __global__ void __launch_bounds__(256) ks_mfma_kernel(OutT *lwe_out, const uint6
         bv[p].w[2] = src[2];
         bv[p].w[3] = src[3];
       }
-      HX_UNROLL
-      for (int q = 0; q < WORDS; ++q) {
-        const uint32_t real = PADDED ? level : (uint32_t)LEVEL;
-        if (narrow) {  // wave-uniform: the decomposition on 32-bit registers (arith.h)
-          int32_t state = decomp_init_state32((uint32_t)(xc[q] >> 32), base_log, real);
-          HX_UNROLL
-          for (int lv = 0; lv < LEVEL; ++lv) {
-            // padded levels: digit 0 against a zero key row (its two shift corrections cancel)
-            const int32_t d = ((!PADDED || (uint32_t)lv < level) ? decompose_one_level32(base_log, state) : 0) +
-                              (int32_t)half_b;
-            bytes[q * LEVEL + lv] = (uint32_t)d;
-            my_sa += d;
-          }
-        } else {
-          uint64_t state = decomp_init_state(xc[q], base_log, real);
-          HX_UNROLL
-          for (int lv = 0; lv < LEVEL; ++lv) {
-            const int32_t d = ((!PADDED || (uint32_t)lv < level) ? (int32_t)decompose_one_level(base_log, state) : 0) +
-                              (int32_t)half_b;
-            bytes[q * LEVEL + lv] = (uint32_t)d;
-            my_sa += d;
-          }
-        }
-      }
-      HX_UNROLL
-      for (int q = 0; q < 4; ++q)
-        av.w[q] = (int32_t)(bytes[4 * q] | (bytes[4 * q + 1] << 8) | (bytes[4 * q + 2] << 16) | (bytes[4 * q + 3] << 24));
+      const hx_i8x16 av = ksm_build_a<LEVEL, PADDED>(xc, base_log, level, narrow, half_b, my_sa);
       HX_UNROLL
       for (int p = 0; p < PLANES; ++p) acc[p] = hx_mfma_i32_32x32x32_i8(av, bv[p], acc[p]);
     }
@@ -413,36 +443,16 @@ __global__ void __launch_bounds__(256) ks_mfma_kernel(OutT *lwe_out, const uint6
     __syncthreads();
   }
   if (!live) return;
-  const uint32_t col = ct * KSM_CT + (lane & 31);
-  if (col > n_out) return;
-  const uint64_t corr = (uint64_t)half_b * colsum[col];
-  HX_UNROLL
-  for (int r = 0; r < 16; ++r) {
-    const int orow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    const uint32_t so = stile * 32 + orow;
-    if (so >= num_samples) continue;
-    int64_t sum_a = (int64_t)sa[wave][0][orow] + sa[wave][1][orow];
+  const auto sum_a = [&](int orow, uint32_t) {  // over the k halves and, KSPLIT, over the waves that shared K
+    int64_t t = (int64_t)sa[wave][0][orow] + sa[wave][1][orow];
     if constexpr (KSPLIT > 1) {
       HX_UNROLL
-      for (int ww = 1; ww < KSPLIT; ++ww) sum_a += (int64_t)sa[ww][0][orow] + sa[ww][1][orow];
+      for (int ww = 1; ww < KSPLIT; ++ww) t += (int64_t)sa[ww][0][orow] + sa[ww][1][orow];
     }
-    uint64_t v = 0;
-    HX_UNROLL
-    for (int p = 0; p < PLANES; ++p) v += (uint64_t)((int64_t)acc[p].v[r] + 128 * sum_a) << (8 * p);
-    uint64_t o = (kpart == 0 ? corr : 0) - v;  // the part's share: wrapping sums, any order
-    if (col == n_out && kpart == 0) {
-      const uint64_t b = lwe_in[(size_t)in_idx[so] * (n_in + 1) + n_in];
-      // 32-bit output: the body rounded to the closest multiple of 2^32, as keyswitch_64_32_kernel does
-      o += sizeof(OutT) == 8 ? b : ((b >> 31) + 1) >> 1;
-    }
-    OutT *dst = &lwe_out[(size_t)out_idx[so] * (n_out + 1) + col];
-    if (kparts > 1) {
-      if constexpr (sizeof(OutT) == 8) atomicAdd((unsigned long long *)dst, (unsigned long long)o);
-      else atomicAdd((unsigned int *)dst, (unsigned int)o);
-    } else {
-      *dst = (OutT)o;
-    }
-  }
+    return t;
+  };
+  ksm_epilogue(acc, sum_a, kpart, kparts, lane, lwe_out, out_idx, lwe_in, in_idx, colsum, n_in, n_out, base_log, num_samples,
+               ct, stile);
 }
 
 // zeroes the output ciphertexts of a keyswitch whose K dimension is split over workgroups (ks_mfma_kernel, KSPLIT)
@@ -470,40 +480,6 @@ __global__ void ks_zero_outputs_kernel(OutT *lwe_out, const uint64_t *out_idx, u
 // column tile).  Measured at the 2_2 sizes (tools/measure_all.py kscross), one launch / digit pass + GEMM: 256 LWEs 0.063 /
 // 0.148 ms, 512: 0.114 / 0.152, 1024: 0.214 / 0.162, 4096: 0.82 / 0.38
 constexpr uint32_t KSD_MIN_SAMPLES = 769;
-std::atomic<uint32_t> g_keyswitch_gemm_min{KSD_MIN_SAMPLES};  // hip_backend_set_keyswitch_kernel(3): 129 (tests)
-
-template <int LEVEL, bool PADDED>
-HX_DEV hx_i8x16 ksm_build_a(const uint64_t (&xc)[16 / LEVEL], uint32_t base_log, uint32_t level, bool narrow,
-                            uint32_t half_b, int32_t &my_sa) {
-  constexpr int WORDS = 16 / LEVEL;
-  uint32_t bytes[16];
-  HX_UNROLL
-  for (int q = 0; q < WORDS; ++q) {
-    const uint32_t real = PADDED ? level : (uint32_t)LEVEL;
-    if (narrow) {  // wave-uniform: the decomposition on 32-bit registers (arith.h)
-      int32_t state = decomp_init_state32((uint32_t)(xc[q] >> 32), base_log, real);
-      HX_UNROLL
-      for (int lv = 0; lv < LEVEL; ++lv) {
-        const int32_t d = ((!PADDED || (uint32_t)lv < level) ? decompose_one_level32(base_log, state) : 0) + (int32_t)half_b;
-        bytes[q * LEVEL + lv] = (uint32_t)d;
-        my_sa += d;
-      }
-    } else {
-      uint64_t state = decomp_init_state(xc[q], base_log, real);
-      HX_UNROLL
-      for (int lv = 0; lv < LEVEL; ++lv) {
-        const int32_t d = ((!PADDED || (uint32_t)lv < level) ? (int32_t)decompose_one_level(base_log, state) : 0) + (int32_t)half_b;
-        bytes[q * LEVEL + lv] = (uint32_t)d;
-        my_sa += d;
-      }
-    }
-  }
-  hx_i8x16 av;
-  HX_UNROLL
-  for (int q = 0; q < 4; ++q)
-    av.w[q] = (int32_t)(bytes[4 * q] | (bytes[4 * q + 1] << 8) | (bytes[4 * q + 2] << 16) | (bytes[4 * q + 3] << 24));
-  return av;
-}
 
 // grid: (tiles of 32 samples, KSD_SPLIT): workgroup (t, y) takes the steps y*4 + w, y*4 + w + 4*KSD_SPLIT, ... of tile
 // t (w = its wave) and adds its share of the digit sums to suma (zeroed by the launcher; integer sums, any order)
@@ -543,21 +519,6 @@ __global__ void __launch_bounds__(256) ks_digits_kernel(int8_t *aplanes, int32_t
   }
 }
 
-template <typename OutT, int SPB>
-__global__ void ks_gemm_kernel(OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in, const uint64_t *in_idx,
-                               const int8_t *planes, const uint64_t *colsum, const int8_t *aplanes, const int32_t *suma,
-                               uint32_t n_in, uint32_t n_out, uint32_t base_log, uint32_t num_samples, uint32_t col_tiles,
-                               uint32_t steps, const OutT *ksk_raw, size_t ksk_words);
-// the widest supported step count per barrier that divides `steps`.  Steps of 32 k between two workgroup barriers, by key
-// word size: measured per 4096 LWEs on one box, u64 keys 0.373 / 0.307 / 0.325 ms with 1 / 2 / 4 (4 fills the 64 KB of
-// static LDS), u32 keys 0.279 / 0.216 / 0.203 ms
-template <typename OutT, typename... Args>
-static void launch_ks_gemm(dim3 grid, hipStream_t st, uint32_t steps, Args... args) {
-  constexpr int WANT = sizeof(OutT) == 8 ? 2 : 4;
-  if (WANT >= 4 && steps % 4 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 4>), grid, dim3(256), 0, st, args...);
-  else if (WANT >= 2 && steps % 2 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 2>), grid, dim3(256), 0, st, args...);
-  else HX_LAUNCH((ks_gemm_kernel<OutT, 1>), grid, dim3(256), 0, st, args...);
-}
 // SPB = steps of 32 k per workgroup barrier: with 2 the barrier, the drain of the global -> LDS loads in front of it and
 // the LDS round trip behind it are paid once per 16 matrix instructions instead of once per 8 (32 KB of LDS for u64 keys)
 // The register budget is cut for 2 waves per SIMD (256 registers; the u64 forms spill 40-61 in their epilogue): one wave
@@ -573,10 +534,7 @@ __global__ void __launch_bounds__(256, 2) ks_gemm_kernel(OutT *lwe_out, const ui
   constexpr int HALF_BYTES = PLANES * KSM_CT * 16;  // one k half of a step: [plane][column][16 bytes]
   constexpr int CHUNKS = 2 * HALF_BYTES / 16 / 256; // 16-byte chunks of B per thread and step (2 for u64 keys, 1 for u32)
   __shared__ alignas(16) int8_t bs[2][SPB][2][HALF_BYTES];
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < KSM_FP) {  // the planes must still be this key's
-    const uint64_t *fp = colsum + (size_t)col_tiles * KSM_CT;
-    if ((uint64_t)ksk_raw[ksm_fp_index((int)threadIdx.x, ksk_words)] != fp[threadIdx.x]) __builtin_trap();
-  }
+  ksm_check_fingerprint(colsum, col_tiles, ksk_raw, ksk_words);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = lane & 31, h = lane >> 5;
   const uint32_t ct = blockIdx.x, stile = blockIdx.y * 4 + wave;
@@ -648,26 +606,18 @@ __global__ void __launch_bounds__(256, 2) ks_gemm_kernel(OutT *lwe_out, const ui
   // pointer loads of all 16 output rows are hoisted above the loop and held (or spilled) across it
   int lane_e = lane;
   HX_OPAQUE(lane_e);
-  const uint32_t col = ct * KSM_CT + (lane_e & 31);
-  if (col > n_out) return;
-  const uint32_t half_b = 1u << (base_log - 1);
-  const uint64_t corr = (uint64_t)half_b * colsum[col];
-  HX_UNROLL
-  for (int r = 0; r < 16; ++r) {
-    const int orow = (r & 3) + 8 * (r >> 2) + 4 * (lane_e >> 5);
-    const uint32_t so = stile * 32 + orow;
-    if (so >= num_samples) continue;
-    const int64_t sum_a = (int64_t)suma[so];
-    uint64_t v = 0;
-    HX_UNROLL
-    for (int p = 0; p < PLANES; ++p) v += (uint64_t)((int64_t)acc[p].v[r] + 128 * sum_a) << (8 * p);
-    uint64_t o = corr - v;
-    if (col == n_out) {
-      const uint64_t b = lwe_in[(size_t)in_idx[so] * (n_in + 1) + n_in];
-      o += sizeof(OutT) == 8 ? b : ((b >> 31) + 1) >> 1;
-    }
-    lwe_out[(size_t)out_idx[so] * (n_out + 1) + col] = (OutT)o;
-  }
+  ksm_epilogue(acc, [suma](int, uint32_t so) { return (int64_t)suma[so]; }, 0u, 1u, lane_e, lwe_out, out_idx, lwe_in, in_idx,
+               colsum, n_in, n_out, base_log, num_samples, ct, stile);
+}
+// the widest supported step count per barrier that divides `steps`.  Steps of 32 k between two workgroup barriers, by key
+// word size: measured per 4096 LWEs on one box, u64 keys 0.373 / 0.307 / 0.325 ms with 1 / 2 / 4 (4 fills the 64 KB of
+// static LDS), u32 keys 0.279 / 0.216 / 0.203 ms
+template <typename OutT, typename... Args>
+static void launch_ks_gemm(dim3 grid, hipStream_t st, uint32_t steps, Args... args) {
+  constexpr int WANT = sizeof(OutT) == 8 ? 2 : 4;
+  if (WANT >= 4 && steps % 4 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 4>), grid, dim3(256), 0, st, args...);
+  else if (WANT >= 2 && steps % 2 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 2>), grid, dim3(256), 0, st, args...);
+  else HX_LAUNCH((ks_gemm_kernel<OutT, 1>), grid, dim3(256), 0, st, args...);
 }
 
 // A operands + digit sums of the large-batch path: buffers per (device, stream) — the keyswitch entry points of the
@@ -772,17 +722,6 @@ static void ksm_release(const KsmEntry &e) {
   HX_CHECK(hipSetDevice(cur));
 }
 
-bool stream_is_capturing(hipStream_t st) {
-#if defined(TFHE_HIPEMU)
-  (void)st;
-  return false;
-#else
-  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &status) != hipSuccess) return false;
-  return status != hipStreamCaptureStatusNone;
-#endif
-}
-
 // device memory [p, p + bytes) of `device` is about to be freed or written
 void ksm_invalidate_range(int device, const void *p, size_t bytes) {
   if (p == nullptr) return;
@@ -806,41 +745,82 @@ size_t ksm_cache_entries() {
   return g_ksm_cache.size();
 }
 
+// ------------------------------------------------------------------ kernel selection
+// hip_backend_set_keyswitch_kernel: 0 = automatic, 1 = scalar kernels, 2 = the one-launch matrix-core kernel at every batch
+// size, 3 = digit pass + GEMM from 129 LWEs on; tests and measurements
+static std::atomic<bool> g_use_mfma{true};                 // false: scalar kernels only
+static std::atomic<bool> g_split_digits{true};             // false: never the digit pass + GEMM
+static std::atomic<uint32_t> g_gemm_min{KSD_MIN_SAMPLES};  // the digit pass + GEMM from this many LWEs on
+static std::atomic<uint32_t> g_last_path{0};               // which path the last launch took: 0 scalar kernels, 1 one-launch
+                                                           // matrix-core kernel, 2 digit pass + GEMM, 3 GEMM on emitted digits
+static std::atomic<uint32_t> g_kparts{8};                  // workgroups per column tile of the one-launch kernel at small
+                                                           // batches (hip_backend_set_keyswitch_kparts)
+void keyswitch_select_kernel(uint32_t which) {
+  g_use_mfma.store(which != 1);
+  g_split_digits.store(which != 2);
+  g_gemm_min.store(which == 3 ? 129u : KSD_MIN_SAMPLES);
+}
+uint32_t keyswitch_last_path() { return g_last_path.load(); }
+void keyswitch_set_kparts(uint32_t parts) { g_kparts.store(parts ? parts : 1); }
+bool keyswitch_batch_takes_gemm(uint32_t num_samples) { return num_samples >= g_gemm_min.load() && g_split_digits.load(); }
+
+// ------------------------------------------------------------------ launching the matrix-core paths
+// one keyswitch call, as the entry points receive it
 template <typename OutT>
-static bool keyswitch_mfma(hipStream_t st, OutT *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
-                           const uint64_t *in_idx, const OutT *ksk, uint32_t n_in, uint32_t n_out,
-                           uint32_t base_log, uint32_t level, uint32_t num_samples, const KsDigits *ready = nullptr) {
-  uint32_t level_pad = 1;  // levels per mask word in the K dimension: the next power of two
-  while (level_pad < level) level_pad <<= 1;
-  const uint32_t K = n_in * level_pad;
+struct KsCall {
+  hipStream_t st;
+  OutT *lwe_out;
+  const uint64_t *out_idx, *lwe_in, *in_idx;
+  const OutT *ksk;
+  uint32_t n_in, n_out, base_log, level, num_samples;
+  size_t key_words() const { return (size_t)n_in * level * (n_out + 1); }
+};
+
+// The shape rule of the matrix-core paths, and what follows from the shape
+struct KsmShape {
+  uint32_t level_pad;  // levels per mask word in the K dimension: the next power of two
+  uint32_t K, steps;   // K = n_in * level_pad, in steps of 32
+  uint32_t col_tiles;
+  size_t plane_bytes;  // the key's byte planes; the column sums and the fingerprint follow them
+  bool ok;             // the matrix-core paths take this shape
+};
+static KsmShape ksm_shape(uint32_t n_in, uint32_t n_out, uint32_t base_log, uint32_t level, size_t key_bytes) {
+  KsmShape s{};
+  s.level_pad = 1;
+  while (s.level_pad < level) s.level_pad <<= 1;
+  s.K = n_in * s.level_pad;
+  s.steps = s.K / 32;
   uint32_t log_k = 0;
-  while (((uint64_t)1 << log_k) < K) ++log_k;
+  while (((uint64_t)1 << log_k) < s.K) ++log_k;
+  s.col_tiles = (n_out + 1 + KSM_CT - 1) / KSM_CT;
+  s.plane_bytes = (size_t)(s.K / 16) * s.col_tiles * key_bytes * KSM_CT * 16;
   // any batch size: a lone ciphertext occupies one row of one 32-row tile, and the launch still streams the key
   // through col_tiles workgroups (0.17 ms at the 2_2 sizes; the scalar kernels need 2.8 ms below 64 LWEs, 4 workgroups)
-  if (level_pad > 16 || K % 32 != 0 || base_log > 6 || base_log + 7 + log_k > 31) return false;
-  const uint32_t ncols = n_out + 1, col_tiles = (ncols + KSM_CT - 1) / KSM_CT;
-  const size_t plane_bytes = (size_t)(K / 16) * col_tiles * sizeof(OutT) * KSM_CT * 16;
-  const size_t need = plane_bytes + ((size_t)col_tiles * KSM_CT + KSM_FP) * sizeof(uint64_t);  // planes, column sums, fingerprint
-  const size_t ksk_words = (size_t)n_in * level * ncols;
-  int device = 0;
-  HX_CHECK(hipGetDevice(&device));
-  int8_t *planes = nullptr;
-  uint64_t *colsum = nullptr;
+  s.ok = s.level_pad <= 16 && s.K % 32 == 0 && base_log <= 6 && base_log + 7 + log_k <= 31;
+  return s;
+}
+
+// The cached planes of the call's key: found, or built on the call's stream (the least recently used key goes when the
+// cache is full), and ordered in front of this stream's work.  Null: not to be had under stream capture.
+template <typename OutT>
+static const int8_t *ksm_planes(const KsCall<OutT> &c, const KsmShape &sh, int device, bool capturing) {
+  const hipStream_t st = c.st;
+  const size_t need = sh.plane_bytes + ((size_t)sh.col_tiles * KSM_CT + KSM_FP) * sizeof(uint64_t);  // planes, column sums, fingerprint
+  const int8_t *planes = nullptr;
   // Under stream capture the cache is read-only: building an entry allocates and frees (neither may be captured) and
   // would record `ready` inside the capture, where later launches of other streams could not wait for it.  A key
   // that is not warm yet takes the scalar kernel for the captured launch (same bits).
-  const bool capturing = stream_is_capturing(st);
   std::vector<KsmEntry> evicted;
   {
     std::lock_guard<std::mutex> lock(g_ksm_mutex);
     KsmEntry *hit = nullptr;
     for (KsmEntry &e : g_ksm_cache)
-      if (e.device == device && e.ksk == (const void *)ksk && e.n_in == n_in && e.n_out == n_out && e.level == level &&
+      if (e.device == device && e.ksk == (const void *)c.ksk && e.n_in == c.n_in && e.n_out == c.n_out && e.level == c.level &&
           e.key_size == sizeof(OutT)) {
         hit = &e;
         break;
       }
-    if (hit == nullptr && capturing) return false;
+    if (hit == nullptr && capturing) return nullptr;
     if (hit == nullptr) {
       if (g_ksm_cache.size() >= kKsmMaxEntries) {  // least recently used key goes (released after the lock)
         size_t lru = 0;
@@ -851,18 +831,18 @@ static bool keyswitch_mfma(hipStream_t st, OutT *lwe_out, const uint64_t *out_id
       }
       KsmEntry e{};
       e.device = device;
-      e.ksk = ksk;
-      e.ksk_bytes = (size_t)n_in * level * ncols * sizeof(OutT);
-      e.n_in = n_in, e.n_out = n_out, e.level = level, e.level_pad = level_pad, e.key_size = sizeof(OutT);
-      e.plane_bytes = plane_bytes;
+      e.ksk = c.ksk;
+      e.ksk_bytes = c.key_words() * sizeof(OutT);
+      e.n_in = c.n_in, e.n_out = c.n_out, e.level = c.level, e.level_pad = sh.level_pad, e.key_size = sizeof(OutT);
+      e.plane_bytes = sh.plane_bytes;
       e.planes = device_alloc_sync(need);
       HX_CHECK(hipEventCreate(&e.ready));
-      uint64_t *cs = (uint64_t *)((char *)e.planes + plane_bytes);
-      HX_CHECK(hipMemsetAsync(cs, 0, (size_t)col_tiles * KSM_CT * sizeof(uint64_t), st));
-      HX_LAUNCH((ksk_planes_kernel<OutT>), dim3((col_tiles * KSM_CT + 255) / 256, K / 16), dim3(256), 0, st,
-                (int8_t *)e.planes, cs, ksk, K, ncols, col_tiles, level, level_pad);
-      HX_LAUNCH((ksk_fingerprint_kernel<OutT>), dim3(1), dim3(KSM_FP), 0, st, cs + (size_t)col_tiles * KSM_CT, ksk,
-                ksk_words);
+      uint64_t *cs = (uint64_t *)((char *)e.planes + sh.plane_bytes);
+      HX_CHECK(hipMemsetAsync(cs, 0, (size_t)sh.col_tiles * KSM_CT * sizeof(uint64_t), st));
+      HX_LAUNCH((ksk_planes_kernel<OutT>), dim3((sh.col_tiles * KSM_CT + 255) / 256, sh.K / 16), dim3(256), 0, st,
+                (int8_t *)e.planes, cs, c.ksk, sh.K, c.n_out + 1, sh.col_tiles, c.level, sh.level_pad);
+      HX_LAUNCH((ksk_fingerprint_kernel<OutT>), dim3(1), dim3(KSM_FP), 0, st, cs + (size_t)sh.col_tiles * KSM_CT, c.ksk,
+                c.key_words());
       HX_CHECK(hipEventRecord(e.ready, st));
       e.builder = st;
       e.done = false;
@@ -872,122 +852,144 @@ static bool keyswitch_mfma(hipStream_t st, OutT *lwe_out, const uint64_t *out_id
       // another stream: behind the layout kernel unless it is known to be over (a query, so that a launch under
       // stream capture does not pick up an event from outside the capture once the key is warm)
       if (hipEventQuery(hit->ready) == hipSuccess) hit->done = true;
-      else if (capturing) return false;  // an event from outside the capture cannot be waited for inside it
+      else if (capturing) return nullptr;  // an event from outside the capture cannot be waited for inside it
       else HX_CHECK(hipStreamWaitEvent(st, hit->ready, 0));
     }
     hit->last_use = ++g_ksm_tick;
-    planes = (int8_t *)hit->planes;
-    colsum = (uint64_t *)((char *)hit->planes + hit->plane_bytes);
+    planes = (const int8_t *)hit->planes;
   }
   for (const KsmEntry &e : evicted) ksm_release(e);
-  if (ready != nullptr && num_samples >= g_keyswitch_gemm_min.load() && g_keyswitch_split_digits.load()) {
-    // the A operands were written by the bootstrap that produced lwe_in (PbsArgs::emit_a): the GEMM alone
-    HX_PANIC_IF_FALSE(ready->steps == K / 32 && ready->base_log == base_log && ready->level == level,
-                      "keyswitch: the digits at hand were made for another decomposition");
-    const uint32_t tiles = (num_samples + 31) / 32;
-    launch_ks_gemm<OutT>(dim3(col_tiles, (tiles + 3) / 4), st, K / 32, lwe_out, out_idx, lwe_in, in_idx, (const int8_t *)planes,
-                         (const uint64_t *)colsum, (const int8_t *)ready->aplanes, (const int32_t *)ready->suma, n_in, n_out,
-                         base_log, num_samples, col_tiles, K / 32, ksk, ksk_words);
-    g_last_keyswitch_path.store(3);
-    return true;
+  return planes;
+}
+
+// Run-time (level_pad, level) -> compile-time (LEVEL, PADDED): calls f(integral_constant<int, LEVEL>, bool_constant<PADDED>).
+// level_pad is the next power of two >= level, so at LEVEL 1 and 2 there is nothing to pad: PADDED only at 4, 8 and 16
+template <typename F>
+static void ksm_with_level(uint32_t level_pad, uint32_t level, F &&f) {
+  const bool padded = level < level_pad;
+  switch (level_pad) {
+    case 1: f(std::integral_constant<int, 1>{}, std::false_type{}); break;
+    case 2: f(std::integral_constant<int, 2>{}, std::false_type{}); break;
+    case 4: padded ? f(std::integral_constant<int, 4>{}, std::true_type{}) : f(std::integral_constant<int, 4>{}, std::false_type{}); break;
+    case 8: padded ? f(std::integral_constant<int, 8>{}, std::true_type{}) : f(std::integral_constant<int, 8>{}, std::false_type{}); break;
+    default: padded ? f(std::integral_constant<int, 16>{}, std::true_type{}) : f(std::integral_constant<int, 16>{}, std::false_type{}); break;
   }
-  if (num_samples >= g_keyswitch_gemm_min.load() && g_keyswitch_split_digits.load()) {
-    // large batch: the digits once (A operands in the stream's scratch), then the LDS-staged GEMM
-    const uint32_t tiles = (num_samples + 31) / 32, steps = K / 32;
-    const size_t a_bytes = (size_t)tiles * steps * 1024, need_s = a_bytes + (size_t)tiles * 32 * sizeof(int32_t);
-    int8_t *scr = (int8_t *)ksd_scratch(device, st, need_s, capturing);
-    if (scr != nullptr) {
-      int32_t *suma = (int32_t *)(scr + a_bytes);
-      HX_CHECK(hipMemsetAsync(suma, 0, (size_t)tiles * 32 * sizeof(int32_t), st));
-#define KSD_LAUNCH(L)                                                                                              \
-  do {                                                                                                               \
-    if (level == L)                                                                                                  \
-      HX_LAUNCH((ks_digits_kernel<L, false>), dim3(tiles, KSD_SPLIT), dim3(256), 0, st, scr, suma, lwe_in, in_idx, n_in, \
-                base_log, level, num_samples);                                                                       \
-    else                                                                                                             \
-      HX_LAUNCH((ks_digits_kernel<L, true>), dim3(tiles, KSD_SPLIT), dim3(256), 0, st, scr, suma, lwe_in, in_idx, n_in,  \
-                base_log, level, num_samples);                                                                       \
-  } while (0)
-      switch (level_pad) {
-        case 1: KSD_LAUNCH(1); break;
-        case 2: KSD_LAUNCH(2); break;
-        case 4: KSD_LAUNCH(4); break;
-        case 8: KSD_LAUNCH(8); break;
-        default: KSD_LAUNCH(16); break;
-      }
-#undef KSD_LAUNCH
-      launch_ks_gemm<OutT>(dim3(col_tiles, (tiles + 3) / 4), st, steps, lwe_out, out_idx, lwe_in, in_idx, (const int8_t *)planes,
-                           (const uint64_t *)colsum, (const int8_t *)scr, (const int32_t *)suma, n_in, n_out, base_log,
-                           num_samples, col_tiles, steps, ksk, ksk_words);
-      g_last_keyswitch_path.store(2);
-      return true;
-    }
-  }
+}
+
+// the GEMM alone, on A operands that are at hand: written by the bootstrap that produced lwe_in (PbsArgs::emit_a) or by
+// the digit pass below
+template <typename OutT>
+static void ksm_launch_gemm(const KsCall<OutT> &c, const KsmShape &sh, const int8_t *planes, const int8_t *aplanes,
+                            const int32_t *suma) {
+  const uint32_t tiles = (c.num_samples + 31) / 32;
+  launch_ks_gemm<OutT>(dim3(sh.col_tiles, (tiles + 3) / 4), c.st, sh.steps, c.lwe_out, c.out_idx, c.lwe_in, c.in_idx, planes,
+                       (const uint64_t *)(planes + sh.plane_bytes), aplanes, suma, c.n_in, c.n_out, c.base_log, c.num_samples,
+                       sh.col_tiles, sh.steps, c.ksk, c.key_words());
+}
+
+// large batch: the digits once (A operands in the stream's scratch), then the LDS-staged GEMM.  false: a captured launch
+// that found no scratch (ksd_scratch)
+template <typename OutT>
+static bool ksm_launch_digits_gemm(const KsCall<OutT> &c, const KsmShape &sh, const int8_t *planes, int device, bool capturing) {
+  const uint32_t tiles = (c.num_samples + 31) / 32;
+  const size_t a_bytes = (size_t)tiles * sh.steps * 1024, need = a_bytes + (size_t)tiles * 32 * sizeof(int32_t);
+  int8_t *scr = (int8_t *)ksd_scratch(device, c.st, need, capturing);
+  if (scr == nullptr) return false;
+  int32_t *suma = (int32_t *)(scr + a_bytes);
+  HX_CHECK(hipMemsetAsync(suma, 0, (size_t)tiles * 32 * sizeof(int32_t), c.st));
+  ksm_with_level(sh.level_pad, c.level, [&](auto L, auto P) {
+    HX_LAUNCH((ks_digits_kernel<decltype(L)::value, decltype(P)::value>), dim3(tiles, KSD_SPLIT), dim3(256), 0, c.st, scr, suma,
+              c.lwe_in, c.in_idx, c.n_in, c.base_log, c.level, c.num_samples);
+  });
+  ksm_launch_gemm(c, sh, planes, scr, suma);
+  return true;
+}
+
+// the one-launch kernel
+template <typename OutT>
+static void ksm_launch_one(const KsCall<OutT> &c, const KsmShape &sh, const int8_t *planes) {
   // up to 32 LWEs: one tile of samples, the four waves of a workgroup split K (needs steps = K / 32 divisible by 4)
-  const bool split = num_samples <= 32 && (K / 32) % 4 == 0;
+  const bool split = c.num_samples <= 32 && sh.steps % 4 == 0;
   // ... and K over KS_KPARTS workgroups per column tile when it divides: 29 workgroups alone stream the key at what
   // 29 CUs can pull (0.09 ms for the 121 MB of a 5-level key padded to 8; 0.052 ms at the 2_2 sizes), 232 at what the
   // memory system delivers (0.027-0.032 / 0.019-0.025 ms; measured 4 parts 0.032 / 0.022, 16 parts 0.034 / 0.026)
   // (33 .. 128 LWEs: one workgroup row of up to four tiles; the same sharing of K, over the grid's z dimension)
   // beyond 128 LWEs the grid has several rows of four tiles and proportionally fewer parts
-  uint32_t want = g_keyswitch_kparts.load();
-  for (uint32_t rows = (num_samples + 127) / 128; rows > 1 && want > 1; rows >>= 1) want >>= 1;
-  const uint32_t kparts = (want > 1 && (K / 32) % (4 * want) == 0) ? want : 1u;
+  uint32_t want = g_kparts.load();
+  for (uint32_t rows = (c.num_samples + 127) / 128; rows > 1 && want > 1; rows >>= 1) want >>= 1;
+  const uint32_t kparts = (want > 1 && sh.steps % (4 * want) == 0) ? want : 1u;
   if (kparts > 1)
-    HX_LAUNCH((ks_zero_outputs_kernel<OutT>), dim3((ncols + 255) / 256, num_samples), dim3(256), 0, st, lwe_out, out_idx,
-              n_out, num_samples);
-  const dim3 grid(col_tiles, split ? kparts : (num_samples + 127) / 128, split ? 1 : kparts);
-#define KSM_LAUNCH(L)                                                                                              \
-  do {                                                                                                               \
-    if (split && level == L)                                                                                         \
-      HX_LAUNCH((ks_mfma_kernel<L, false, OutT, 4>), grid, dim3(256), 0, st, lwe_out, out_idx, lwe_in, in_idx,       \
-                planes, colsum, n_in, n_out, base_log, num_samples, col_tiles, level, ksk, ksk_words);               \
-    else if (split)                                                                                                  \
-      HX_LAUNCH((ks_mfma_kernel<L, true, OutT, 4>), grid, dim3(256), 0, st, lwe_out, out_idx, lwe_in, in_idx,        \
-                planes, colsum, n_in, n_out, base_log, num_samples, col_tiles, level, ksk, ksk_words);               \
-    else if (level == L)                                                                                             \
-      HX_LAUNCH((ks_mfma_kernel<L, false, OutT>), grid, dim3(256), 0, st, lwe_out, out_idx, lwe_in, in_idx, planes,   \
-                colsum, n_in, n_out, base_log, num_samples, col_tiles, level, ksk, ksk_words);                       \
-    else                                                                                                             \
-      HX_LAUNCH((ks_mfma_kernel<L, true, OutT>), grid, dim3(256), 0, st, lwe_out, out_idx, lwe_in, in_idx, planes,    \
-                colsum, n_in, n_out, base_log, num_samples, col_tiles, level, ksk, ksk_words);                       \
-  } while (0)
-  switch (level_pad) {
-    case 1: KSM_LAUNCH(1); break;
-    case 2: KSM_LAUNCH(2); break;
-    case 4: KSM_LAUNCH(4); break;
-    case 8: KSM_LAUNCH(8); break;
-    default: KSM_LAUNCH(16); break;
+    HX_LAUNCH((ks_zero_outputs_kernel<OutT>), dim3((c.n_out + 1 + 255) / 256, c.num_samples), dim3(256), 0, c.st, c.lwe_out,
+              c.out_idx, c.n_out, c.num_samples);
+  const dim3 grid(sh.col_tiles, split ? kparts : (c.num_samples + 127) / 128, split ? 1 : kparts);
+  const uint64_t *colsum = (const uint64_t *)(planes + sh.plane_bytes);
+  ksm_with_level(sh.level_pad, c.level, [&](auto L, auto P) {
+    constexpr int LEVEL = decltype(L)::value;
+    constexpr bool PADDED = decltype(P)::value;
+    if (split)
+      HX_LAUNCH((ks_mfma_kernel<LEVEL, PADDED, OutT, 4>), grid, dim3(256), 0, c.st, c.lwe_out, c.out_idx, c.lwe_in, c.in_idx,
+                planes, colsum, c.n_in, c.n_out, c.base_log, c.num_samples, sh.col_tiles, c.level, c.ksk, c.key_words());
+    else
+      HX_LAUNCH((ks_mfma_kernel<LEVEL, PADDED, OutT>), grid, dim3(256), 0, c.st, c.lwe_out, c.out_idx, c.lwe_in, c.in_idx,
+                planes, colsum, c.n_in, c.n_out, c.base_log, c.num_samples, sh.col_tiles, c.level, c.ksk, c.key_words());
+  });
+}
+
+// false: the shape is not the matrix cores', or the key's planes are not to be had under stream capture
+template <typename OutT>
+static bool keyswitch_mfma(const KsCall<OutT> &c, const KsDigits *ready) {
+  const KsmShape sh = ksm_shape(c.n_in, c.n_out, c.base_log, c.level, sizeof(OutT));
+  if (!sh.ok) return false;
+  int device = 0;
+  HX_CHECK(hipGetDevice(&device));
+  const bool capturing = stream_is_capturing(c.st);
+  const int8_t *planes = ksm_planes(c, sh, device, capturing);
+  if (planes == nullptr) return false;
+  if (keyswitch_batch_takes_gemm(c.num_samples)) {
+    if (ready != nullptr) {
+      HX_PANIC_IF_FALSE(ready->steps == sh.steps && ready->base_log == c.base_log && ready->level == c.level,
+                        "keyswitch: the digits at hand were made for another decomposition");
+      ksm_launch_gemm(c, sh, planes, ready->aplanes, ready->suma);
+      g_last_path.store(3);
+      return true;
+    }
+    if (ksm_launch_digits_gemm(c, sh, planes, device, capturing)) {
+      g_last_path.store(2);
+      return true;
+    }
   }
-#undef KSM_LAUNCH
-  g_last_keyswitch_path.store(1);
+  ksm_launch_one(c, sh, planes);
+  g_last_path.store(1);
   return true;
 }
 
 // what a bootstrap can emit for the keyswitch that follows it (PbsArgs::emit_a): level_pad 4 or 8, 32-bit decomposition,
-// and the shape the matrix-core path accepts
+// and the shape the matrix-core path accepts (a u64 key; the output width does not enter the rule)
 bool keyswitch_digits_emittable(uint32_t n_in, uint32_t base_log, uint32_t level, uint32_t *level_pad, uint32_t *steps) {
-  uint32_t lp = 1;
-  while (lp < level) lp <<= 1;
-  const uint32_t K = n_in * lp;
-  uint32_t log_k = 0;
-  while (((uint64_t)1 << log_k) < K) ++log_k;
-  if ((lp != 4 && lp != 8) || K % 32 != 0 || base_log > 6 || base_log + 7 + log_k > 31 || base_log * level > 30) return false;
-  *level_pad = lp;
-  *steps = K / 32;
-  return g_keyswitch_use_mfma.load() && g_keyswitch_split_digits.load();
+  const KsmShape sh = ksm_shape(n_in, 0, base_log, level, sizeof(uint64_t));
+  if (!sh.ok || (sh.level_pad != 4 && sh.level_pad != 8) || base_log * level > 30) return false;
+  *level_pad = sh.level_pad;
+  *steps = sh.steps;
+  return g_use_mfma.load() && g_split_digits.load();
+}
+
+// ------------------------------------------------------------------ entry points
+// Front of both: the decomposition fits max_bits bits, an empty batch is done, the matrix cores take the call when they
+// are selected and the shape is theirs.  false: the caller's scalar kernels
+template <typename OutT>
+static bool keyswitch_front(const char *name, uint32_t max_bits, const KsCall<OutT> &c, const KsDigits *ready) {
+  HX_PANIC_IF_FALSE(c.base_log >= 1 && c.level >= 1 && c.base_log * c.level <= max_bits,
+                    "%s: unsupported decomposition (base_log=%u, level=%u)", name, c.base_log, c.level);
+  if (c.num_samples == 0) return true;
+  return g_use_mfma.load() && keyswitch_mfma(c, ready);
 }
 
 void launch_keyswitch(hipStream_t st, uint64_t *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
                       const uint64_t *in_idx, const uint64_t *ksk, uint32_t n_in, uint32_t n_out,
                       uint32_t base_log, uint32_t level, uint32_t num_samples, const KsDigits *ready) {
-  HX_PANIC_IF_FALSE(base_log >= 1 && level >= 1 && base_log * level < 64,
-                    "keyswitch: unsupported decomposition (base_log=%u, level=%u)", base_log, level);
-  if (num_samples == 0) return;
-  if (g_keyswitch_use_mfma.load() &&
-      keyswitch_mfma(st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out, base_log, level, num_samples, ready))
-    return;
-  g_last_keyswitch_path.store(0);
+  const KsCall<uint64_t> c{st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out, base_log, level, num_samples};
+  if (keyswitch_front("keyswitch", 63, c, ready)) return;
+  g_last_path.store(0);
   // the scalar kernels stage at most KS_MAXL levels per mask element (the matrix-core path above takes up to 16)
   HX_PANIC_IF_FALSE(level <= KS_MAXL, "keyswitch: level_count %u > %d is only supported by the matrix-core kernel (base_log <= 6)",
                     level, KS_MAXL);
@@ -1007,6 +1009,20 @@ void launch_keyswitch(hipStream_t st, uint64_t *lwe_out, const uint64_t *out_idx
     HX_LAUNCH((keyswitch_kernel<int64_t>), grid, dim3(KS_TPB), smem, st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in,
               n_out, base_log, level, num_samples);
   }
+}
+
+void launch_keyswitch_64_32(hipStream_t st, uint32_t *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
+                            const uint64_t *in_idx, const uint32_t *ksk, uint32_t n_in, uint32_t n_out,
+                            uint32_t base_log, uint32_t level, uint32_t num_samples) {
+  const KsCall<uint32_t> c{st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out, base_log, level, num_samples};
+  // lwe_keyswitch.rs:353-359: the decomposition must fit the OUTPUT width
+  if (keyswitch_front("keyswitch 64->32", 32, c, nullptr)) return;
+  HX_PANIC_IF_FALSE(level <= KS_MAXL, "keyswitch 64->32: level_count %u > %d is only supported by the matrix-core kernel",
+                    level, KS_MAXL);
+  const dim3 grid((n_out + 1 + KS_TPB - 1) / KS_TPB, (num_samples + KS_TB - 1) / KS_TB);
+  const size_t smem = sizeof(uint32_t) * KS_IC * level * KS_TB;
+  HX_LAUNCH(keyswitch_64_32_kernel, grid, dim3(KS_TPB), smem, st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out,
+            base_log, level, num_samples);
 }
 
 // ------------------------------------------------------------------ packing keyswitch: LWE list -> GLWE
@@ -1087,24 +1103,6 @@ void launch_packing_keyswitch(hipStream_t st, uint64_t *out, uint64_t *rows, con
   const uint32_t words = s ? (uint32_t)(((uint64_t)nvals * s + 63) / 64) : ncols;
   HX_LAUNCH(pks_rotate_pack_kernel, dim3((nvals + 63) / 64, glwes), dim3(256), 0, st, out, (const uint64_t *)rows, lwe_in,
             n_in, glwe_dim, N, num_lwes, lwe_per_glwe, nvals, s, words);
-}
-
-void launch_keyswitch_64_32(hipStream_t st, uint32_t *lwe_out, const uint64_t *out_idx, const uint64_t *lwe_in,
-                            const uint64_t *in_idx, const uint32_t *ksk, uint32_t n_in, uint32_t n_out,
-                            uint32_t base_log, uint32_t level, uint32_t num_samples) {
-  // lwe_keyswitch.rs:353-359: the decomposition must fit the OUTPUT width
-  HX_PANIC_IF_FALSE(base_log >= 1 && level >= 1 && base_log * level <= 32,
-                    "keyswitch 64->32: unsupported decomposition (base_log=%u, level=%u)", base_log, level);
-  if (num_samples == 0) return;
-  if (g_keyswitch_use_mfma.load() &&
-      keyswitch_mfma(st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out, base_log, level, num_samples))
-    return;
-  HX_PANIC_IF_FALSE(level <= KS_MAXL, "keyswitch 64->32: level_count %u > %d is only supported by the matrix-core kernel",
-                    level, KS_MAXL);
-  const dim3 grid((n_out + 1 + KS_TPB - 1) / KS_TPB, (num_samples + KS_TB - 1) / KS_TB);
-  const size_t smem = sizeof(uint32_t) * KS_IC * level * KS_TB;
-  HX_LAUNCH(keyswitch_64_32_kernel, grid, dim3(KS_TPB), smem, st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out,
-            base_log, level, num_samples);
 }
 
 }  // namespace tfhe_hip
