@@ -258,11 +258,14 @@ class ExactKey:
         return self.ops[((i * p.level + idx) * (p.k + 1) + row) * (p.k + 1) + col]
 
     def pack_digits(self, digits):
+        """digits: N Python integers in [-2^63, 2^63] (base_log 64 reaches both ends, so the signed values do not fit an
+        int64; their magnitudes fit a uint64) -> the Kronecker operand, positive part minus negative part"""
         N = self.p.N
-        d = np.asarray(digits, dtype=np.int64)
+        digits = [int(v) for v in digits]
+        assert len(digits) == N and all(-(1 << 63) <= v <= (1 << 63) for v in digits)
         buf = np.zeros((2, N, self.slot), dtype=np.uint8)
-        buf[0, :, :8] = np.where(d > 0, d, 0).astype(U64).view(np.uint8).reshape(N, 8)
-        buf[1, :, :8] = np.where(d < 0, -d, 0).astype(U64).view(np.uint8).reshape(N, 8)
+        buf[0, :, :8] = np.array([v if v > 0 else 0 for v in digits], dtype=U64).view(np.uint8).reshape(N, 8)
+        buf[1, :, :8] = np.array([-v if v < 0 else 0 for v in digits], dtype=U64).view(np.uint8).reshape(N, 8)
         return int.from_bytes(buf[0].tobytes(), "little") - int.from_bytes(buf[1].tobytes(), "little")
 
     def unpack_negacyclic(self, total):

@@ -175,12 +175,16 @@ def test_transform_product(kind):
 def test_u128_decomposer_word_for_word(kind):
     """The digits of the kernels' u128 decomposer equal the restatement's on 0, 2^127, all ones, values exactly half way
     between two representables and one either side, representables and uniform words; (24, 3) and two toy pairs, and a
-    pair that represents all 128 bits."""
+    pair that represents all 128 bits.  Then the widths the bootstrap rows of test_pbs128_dispatch_coverage.py use and
+    the ends of the documented range: base_log 32 and 33 (the first digits wider than an int32), 43 and 53 (around a
+    double's mantissa), 64 with one and two levels (digits of magnitude 2^63), and 128 levels of one bit / 64 of two."""
     lib, gpu, st = setup(kind)
     rng = np.random.default_rng(130)
-    for base_log, level in ((24, 3), (20, 4), (12, 5), (16, 8)):
+    for base_log, level in ((24, 3), (20, 4), (12, 5), (16, 8),
+                            (32, 4), (64, 2), (64, 1), (43, 2), (53, 2), (33, 3), (1, 128), (2, 64)):
         bits = base_log * level
         vals = [0, 1 << 127, h.M128] + h.from_pairs(_uniform_u128(rng, 64))
+        vals += [(1 << 127) + 1, (1 << 127) - 1, 1 << 63, (1 << 64) - 1, 1 << 64]
         if bits < 128:
             r = [int(v) << (128 - bits) for v in rng.integers(0, 1 << 62, size=32)]
             r = [v & h.M128 for v in r] + [((1 << bits) - 1) << (128 - bits), ((1 << (bits - 1)) - 1) << (128 - bits)]
@@ -198,6 +202,27 @@ def test_u128_decomposer_word_for_word(kind):
             if bits < 128:
                 closest = ((v + (1 << (127 - bits))) >> (128 - bits) << (128 - bits)) & h.M128
                 assert h.recompose128(h.decompose128(v, base_log, level), base_log, level) == closest
+
+
+def test_exact_checker_packs_digits_of_magnitude_two_to_the_63():
+    """base_log 64 gives digits in [-2^63, 2^63]: +2^63 is no int64 (packing through one raised OverflowError: Python
+    int too large to convert to C long).  A polynomial holding +2^63, -2^63, 0, +-1, 2^63 - 1 and uniform digits of that
+    range goes through ExactKey.pack_digits, one product with a key polynomial and unpack_negacyclic, and equals
+    negacyclic_product_exact on the same operands; the same for a (24, 3) key, whose slot width differs."""
+    rng = np.random.default_rng(131)
+    for base_log, level in ((64, 1), (64, 2), (24, 3)):
+        p = h.Params128(f"pack_b{base_log}l{level}", 2, 1, 256, base_log, level)
+        keys = h.make_keys128(p)
+        ekey = h.ExactKey(p, keys)
+        top = 1 << (base_log - 1)
+        digits = [top, -top, 0, 1, -1, top - 1, -(top - 1)]
+        digits += [int(v) - top for v in rng.integers(0, 1 << base_log, size=p.N - len(digits) - 2, dtype=U64)]
+        digits += [-top, top]   # the last coefficients wrap negacyclically
+        assert len(digits) == p.N
+        for i, idx, row, col in ((0, 0, 0, 0), (1, level - 1, 1, 1)):
+            got = ekey.unpack_negacyclic(ekey.pack_digits(digits) * ekey.op(i, idx, row, col))
+            want = h.negacyclic_product_exact(h.from_pairs(keys.bsk[i, idx, row, col]), digits, p.N)
+            assert got == want, (base_log, level, i, idx, row, col)
 
 
 # ------------------------------------------------------------------------------------------------ 4. phase
@@ -436,15 +461,31 @@ def test_noise_squashing_of_a_radix_ciphertext(kind):
     """A 64-bit radix value (32 blocks of 2_2; hip: the compute set PARAM_MESSAGE_2_CARRY_2 and the production squashing
     set, emu: toy sets) becomes 16 u128 blocks, block i decrypting to lo + 4 hi of its pair; 5 blocks become 3; the input
     is unchanged.  Slow on hip only (the 812 MB key of the full-size test, shared with it)."""
+    _squash_and_check(kind, lambda cp: h.PRODUCTION if kind == "hip" else TOY_SQUASH,
+                      ((32, 0xD1CEB00C5EEDF00D), (5, 0b1110010011)))
+
+
+@pytest.mark.gpu
+def test_noise_squashing_on_the_device_with_a_toy_squashing_ring():
+    """The device's compute set (PARAM_MESSAGE_2_CARRY_2: its keyswitch and its small key, n = 918) with a toy squashing
+    ring (k = 1, N = 512, 3 levels of 24 bits, centred switch; a key of about 90 MB instead of 812 MB): 5 blocks become
+    3, block i decrypting to lo + 4 hi of its pair, the input unchanged.  The assertions of the test above, without the
+    production squashing key and therefore not slow."""
+    _squash_and_check("hip", lambda cp: h.Params128(f"toy128_squash_k1_N512_n{cp.n}", cp.n, 1, 512, 24, 3, ms_type=1),
+                      ((5, 0b1110010011),))
+
+
+def _squash_and_check(kind, squashing_set, cases):
+    """squashing_set(compute set) -> the Params128 of the squashing key; cases: (blocks, value) pairs"""
     from tfhe_rs_amd import integer_gpu as igpu
     from .test_radix_integer import encrypt_radix
     from .test_radix_integer import setup as radix_setup
     cp, ckeys, st, sks, _ = radix_setup(kind)
     gpu = __import__("tfhe_rs_amd.core_crypto_gpu", fromlist=["x"])
-    sp = h.PRODUCTION if kind == "hip" else TOY_SQUASH
+    sp = squashing_set(cp)
     skeys = h.make_keys128(sp, compute=cp)
     nsk = igpu.CudaNoiseSquashingKey(upload_key(gpu, st, sp, skeys), 4, 4)
-    for blocks, value in ((32, 0xD1CEB00C5EEDF00D), (5, 0b1110010011)):
+    for blocks, value in cases:
         h_in = encrypt_radix(cp, ckeys, [value], blocks, seed=70 + blocks)
         ct = igpu.CudaUnsignedRadixCiphertext.from_blocks(h_in, st)
         ct.set_degrees(3)
