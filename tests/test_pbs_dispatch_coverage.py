@@ -145,6 +145,10 @@ CASES = [
          many_lut=2 if (N, K1) == (512, 3) else 1) for N, K1 in NK],
     C_("generic_big_8192", toy(1, 8192, 23, 1, n=3), 3, 0, (GENERIC, 0, 0, 0, BIG, 1, 8192, 2)),
     C_("generic_big_16384", toy(1, 16384, 15, 2, n=3), 3, 0, (GENERIC, 0, 0, 0, BIG, 1, 16384, 2)),
+    # the centred modulus switch with more mask words than threads: a term in every thread and a ragged last stride
+    C_("generic_256_2_centered_n131", toy(1, 256, 21, 3, n=131, ms_type=1), 3, 1, (GENERIC, 0, 0, 0, PAR, 1, 256, 2)),
+    C_("ntt_256_2_centered_n131", toy(1, 256, 21, 3, n=131, ms_type=1), 3, 0, (NTT, 0, 0, 0, PAR, 1, 256, 2), engine="ntt64"),
+    C_("generic_512_3_centered_n259", toy(2, 512, 18, 2, n=259, ms_type=1), 3, 1, (GENERIC, 0, 0, 0, PLAIN, 1, 512, 3)),
     # -------- multi-bit wave kernel: plain (one LWE per workgroup), SHARE (2 or 4 per workgroup), OCTET (4, L >= 1)
     *[C_(f"mb_wave_{L}_{B}_{G}_plain", p, 9, 2, _mbw(L, B, G, PLAIN, 1), many_lut=2 if G == 2 and L == 0 else 1)
       for p, L, B, G in ((MB_G3L2, 2, 15, 3), (MB_G3B14, 2, 14, 3), (MB_G4L1, 1, 22, 4), (MB_G3L1, 1, 22, 3),
@@ -237,15 +241,15 @@ def _function_body(text, name):
 def extract_instantiations():
     """{(launcher, 'template,args')} of every launch the dispatch functions can make."""
     found = set()
-    generic = open(os.path.join(CSRC, "pbs_generic.hip")).read()
-    macro = re.search(r"#define HX_DISPATCH_NK\(FN, \.\.\.\)(.*?)\n\n", generic, re.S)
-    assert macro, "HX_DISPATCH_NK not found"
-    nk = re.findall(r"FN<(\d+), (\d+)>", macro.group(1))
+    shapes = open(os.path.join(CSRC, "pbs_generic.h")).read()
+    table = re.search(r"constexpr ShapeNK PBS_SHAPES_NK\[\] = \{(.*?)\};", shapes, re.S)
+    assert table, "PBS_SHAPES_NK not found"
+    nk = re.findall(r"\{(\d+), (\d+)\}", table.group(1))
     for fname, func in DISPATCHERS:
         body = _function_body(open(os.path.join(CSRC, fname)).read(), func)
         for launcher, args in re.findall(r"\b(launch_\w+)<([^<>()]*)>\s*\(", body):
             found.add((launcher, ",".join(a.strip() for a in args.split(","))))
-        for launcher in re.findall(r"HX_DISPATCH_NK\((\w+)", body):
+        for launcher in re.findall(r"dispatch_nk\([^;]*?\b(launch_\w+)<", body):
             found.update((launcher, f"{N},{K1}") for N, K1 in nk)
     return found
 

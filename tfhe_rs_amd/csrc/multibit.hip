@@ -12,10 +12,13 @@
 // throughput kernels.  Operation order fixed (pbs_common.h), so results are bit-exact against the oracle.
 //
 // pbs_multi_bit_kernel: one workgroup per LWE runs all groups in one launch, building every keybundle element in
-// registers right where the multiply-accumulate consumes it.
+// registers right where the multiply-accumulate consumes it.  The latency path parks the keybundles first
+// (mb_keybundle*_kernel) and runs the products from them (mb_accumulate*_kernel).  The three product kernels share
+// their prologue and untwist with the classic generic kernels (pbs_generic.h); their loops decompose the accumulator
+// itself, assign instead of add, and differ in where a key element comes from.
 #include <atomic>
 
-#include "kernels.h"
+#include "pbs_generic.h"
 
 namespace tfhe_hip {
 
@@ -41,22 +44,15 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB)
   const uint32_t sample = blockIdx.x;
   uint64_t *acc = ACC_GLOBAL ? a.acc_scratch + (size_t)sample * K1 * N : (uint64_t *)smem;  // K1*N torus words (src, then dst)
   const FBuf fbuf{(cplx *)(smem + (ACC_GLOBAL ? 0 : (size_t)K1 * N * 8))};                  // n complex points (padded)
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  const PbsSample<N, K1> s(a, sample);
   const cplx *bsk = (const cplx *)a.bsk;  // Fourier domain: [group][subset][level][row][col][slot]
   const uint32_t per = 1u << grouping, groups = a.n / grouping;
   const size_t kb_polys = (size_t)a.level * K1 * K1;
   const size_t ggsw_c = kb_polys * n;  // complex elements per GGSW
 
   // standard modulus switch of the body (multi-bit sets use no centered correction, :98-103)
-  const uint32_t b_hat = (uint32_t)modulus_switch(lwe[a.n], LOG2N2);
-  for (int p = 0; p < K1; ++p)
-    for (uint32_t j = tid; j < (uint32_t)N; j += TPB) {
-      bool neg;
-      const uint32_t src = monomial_div_src(j, b_hat, N, neg);
-      const uint64_t v = lut[p * N + src];
-      acc[p * N + j] = neg ? (uint64_t)0 - v : v;
-    }
+  const uint32_t b_hat = (uint32_t)modulus_switch(s.lwe[a.n], LOG2N2);
+  block_load_lut<N, TPB>(acc, s.lut, b_hat, 0, K1, tid);
   __syncthreads();
 
   for (uint32_t grp = 0; grp < groups; ++grp) {
@@ -64,9 +60,9 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB)
     uint32_t deg[16];
     if (a.mb_degrees != nullptr) {  // noise-test entry point: degrees switched ahead, [input][group][subset]
       const uint64_t *pre = a.mb_degrees + ((size_t)a.in_idx[sample] * groups + grp) * per;
-      for (uint32_t s = 1; s < per; ++s) deg[s] = (uint32_t)pre[s];
+      for (uint32_t sb = 1; sb < per; ++sb) deg[sb] = (uint32_t)pre[sb];
     } else {
-      multi_bit_degrees(lwe + (size_t)grp * grouping, grouping, LOG2N2, deg);
+      multi_bit_degrees(s.lwe + (size_t)grp * grouping, grouping, LOG2N2, deg);
     }
     // ---- dst = 0 + src (x) keybundle   (ggsw.rs:483-602 with a zeroed output), keybundle built point by point
     cplx facc[K1][PER];
@@ -96,13 +92,7 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB)
       for (int q = 0; q < PER; ++q) fbuf[tid + q * TPB] = facc[c][q];
       __syncthreads();
       lds_fft_inverse<N, TPB>(fbuf, tb.inv, tid);
-      for (int q = 0; q < PER; ++q) {
-        const int j = tid + q * TPB;
-        const cplx y = fbuf[j];
-        const double ur = tb.untw[2 * j], ui = tb.untw[2 * j + 1];
-        acc[c * N + j] = from_torus(fma(-y.im, ui, y.re * ur));
-        acc[c * N + j + n] = from_torus(fma(y.im, ur, y.re * ui));
-      }
+      for (int q = 0; q < PER; ++q) untwist_to_torus<N, false>(fbuf[tid + q * TPB], tb.untw, acc, c, tid + q * TPB);
       __syncthreads();
     }
   }
@@ -140,8 +130,7 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB)
     uint32_t deg[16];
     for (int q = 0; q < 16; ++q) deg[q] = 0;
     if ((uint32_t)tid < count) {
-      const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[s0 + tid] * (a.n + 1);
-      multi_bit_degrees(lwe + (size_t)grp * grouping, grouping, LOG2N2, deg);
+      multi_bit_degrees(sample_lwe(a, s0 + tid) + (size_t)grp * grouping, grouping, LOG2N2, deg);
     }
     for (int q = 0; q < 16; ++q) sdeg[tid][q] = deg[q];
   }
@@ -194,8 +183,7 @@ __global__ void __launch_bounds__(256)
     uint32_t deg[16];
     for (int q = 0; q < 16; ++q) deg[q] = 0;
     if ((uint32_t)tid < count) {
-      const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[s0 + tid] * (a.n + 1);
-      multi_bit_degrees(lwe + (size_t)grp * grouping, grouping, LOG2N2, deg);
+      multi_bit_degrees(sample_lwe(a, s0 + tid) + (size_t)grp * grouping, grouping, LOG2N2, deg);
     }
     for (int q = 0; q < 16; ++q) sdeg[tid][q] = deg[q];
   }
@@ -264,19 +252,11 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB)
   const FBuf fbuf{(cplx *)(smem + (size_t)K1 * N * 8)};
   const int tid = threadIdx.x;
   const uint32_t sample = blockIdx.x;
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  const PbsSample<N, K1> s(a, sample);
   const size_t kb_polys = (size_t)a.level * K1 * K1;
   uint64_t *mine = acc_g + (size_t)sample * K1 * N;
   if (first) {
-    const uint32_t b_hat = (uint32_t)modulus_switch(lwe[a.n], LOG2N2);
-    for (int p = 0; p < K1; ++p)
-      for (uint32_t j = tid; j < (uint32_t)N; j += TPB) {
-        bool neg;
-        const uint32_t src = monomial_div_src(j, b_hat, N, neg);
-        const uint64_t v = lut[p * N + src];
-        acc[p * N + j] = neg ? (uint64_t)0 - v : v;
-      }
+    block_load_lut<N, TPB>(acc, s.lut, (uint32_t)modulus_switch(s.lwe[a.n], LOG2N2), 0, K1, tid);
   } else {
     for (uint32_t j = tid; j < (uint32_t)(K1 * N); j += TPB) acc[j] = mine[j];
   }
@@ -310,13 +290,7 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB)
       for (int q = 0; q < PER; ++q) fbuf[tid + q * TPB] = facc[c][q];
       __syncthreads();
       lds_fft_inverse<N, TPB>(fbuf, tb.inv, tid);
-      for (int q = 0; q < PER; ++q) {
-        const int j = tid + q * TPB;
-        const cplx y = fbuf[j];
-        const double ur = tb.untw[2 * j], ui = tb.untw[2 * j + 1];
-        acc[c * N + j] = from_torus(fma(-y.im, ui, y.re * ur));
-        acc[c * N + j + n] = from_torus(fma(y.im, ur, y.re * ui));
-      }
+      for (int q = 0; q < PER; ++q) untwist_to_torus<N, false>(fbuf[tid + q * TPB], tb.untw, acc, c, tid + q * TPB);
       __syncthreads();
     }
   }
@@ -341,19 +315,12 @@ __global__ void __launch_bounds__(K1 *GenericCfg<N>::TPB)
   const int tid = threadIdx.x;
   const int grp = tid / TPB, lt = tid - grp * TPB;  // my row (forward) / column (inverse), thread inside it
   const uint32_t sample = blockIdx.x;
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  const PbsSample<N, K1> s(a, sample);
   const size_t kb_polys = (size_t)a.level * K1 * K1;
   uint64_t *mine = acc_g + (size_t)sample * K1 * N;
   const FBuf mybuf{fbase + (size_t)grp * fbuf_slots(N)};
   if (first) {
-    const uint32_t b_hat = (uint32_t)modulus_switch(lwe[a.n], LOG2N2);
-    for (uint32_t j = lt; j < (uint32_t)N; j += TPB) {
-      bool neg;
-      const uint32_t src = monomial_div_src(j, b_hat, N, neg);
-      const uint64_t v = lut[grp * N + src];
-      acc[grp * N + j] = neg ? (uint64_t)0 - v : v;
-    }
+    block_load_lut<N, TPB>(acc, s.lut, (uint32_t)modulus_switch(s.lwe[a.n], LOG2N2), grp, grp + 1, lt);
   } else {
     for (uint32_t j = tid; j < (uint32_t)(K1 * N); j += TPBT) acc[j] = mine[j];
   }
@@ -384,13 +351,7 @@ __global__ void __launch_bounds__(K1 *GenericCfg<N>::TPB)
     for (int q = 0; q < PER; ++q) mybuf[lt + q * TPB] = facc[q];
     __syncthreads();
     lds_fft_inverse<N, TPB>(mybuf, tb.inv, lt);
-    for (int q = 0; q < PER; ++q) {
-      const int j = lt + q * TPB;
-      const cplx y = mybuf[j];
-      const double ur = tb.untw[2 * j], ui = tb.untw[2 * j + 1];
-      acc[grp * N + j] = from_torus(fma(-y.im, ui, y.re * ur));
-      acc[grp * N + j + n] = from_torus(fma(y.im, ur, y.re * ui));
-    }
+    for (int q = 0; q < PER; ++q) untwist_to_torus<N, false>(mybuf[lt + q * TPB], tb.untw, acc, grp, lt + q * TPB);
     __syncthreads();
   }
   if (last) {
@@ -400,59 +361,68 @@ __global__ void __launch_bounds__(K1 *GenericCfg<N>::TPB)
   }
 }
 
+// the products of one chunk of groups on the generic kernels, in the schedule of generic_runs_par (as launch_fft)
+template <int N, int K1>
+static void launch_mb_products(hipStream_t st, const PbsArgs &a, const FftTables &tb, const cplx *kb_lat, uint64_t *acc_g,
+                               uint32_t group_chunk, uint32_t gpass, int first, int last) {
+  const bool par = generic_runs_par(K1);
+  note_pbs_instantiation(0, 0, 0, par ? PBS_INST_PAR : PBS_INST_PLAIN, 1, N, K1);
+  if constexpr (K1 == 2) {
+    if (par) {
+      const size_t smem = (size_t)K1 * N * 8 + (size_t)K1 * fbuf_bytes(N);
+      hx_set_dynamic_smem_once<mb_accumulate_par_kernel<N, K1>>(smem);
+      HX_LAUNCH((mb_accumulate_par_kernel<N, K1>), dim3(a.num_samples), dim3(K1 * GenericCfg<N>::TPB), smem, st, a, kb_lat,
+                tb, acc_g, group_chunk, gpass, first, last);
+      return;
+    }
+  }
+  const size_t smem = (size_t)K1 * N * 8 + fbuf_bytes(N);
+  hx_set_dynamic_smem_once<mb_accumulate_kernel<N, K1>>(smem);
+  HX_LAUNCH((mb_accumulate_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a, kb_lat, tb, acc_g,
+            group_chunk, gpass, first, last);
+}
+
 template <int N, int K1>
 static void launch_mb_latency(hipStream_t st, const MultiBitArgs &m, const FftTables &tb, cplx *kb_lat,
                               uint32_t group_chunk, uint64_t *acc_g) {
   const PbsArgs &a = m.pbs;
   const uint32_t groups = a.n / m.grouping_factor, kb_polys = a.level * K1 * K1;
-  const size_t smem_b = (size_t)K1 * N * 8 + fbuf_bytes(N);
-  const size_t smem_p = (size_t)K1 * N * 8 + (size_t)K1 * fbuf_bytes(N);
-  const bool par = K1 == 2 && !g_ntt_kernel_serial;  // same rule as the classic generic kernels (hip_backend_set_ntt_kernel)
-  if (par)
-    hx_set_dynamic_smem_once<mb_accumulate_par_kernel<N, K1>>(smem_p);
-  else
-    hx_set_dynamic_smem_once<mb_accumulate_kernel<N, K1>>(smem_b);
   for (uint32_t g0 = 0; g0 < groups; g0 += group_chunk) {
     const uint32_t gpass = groups - g0 < group_chunk ? groups - g0 : group_chunk;
+    const int first = (int)(g0 == 0), last = (int)(g0 + gpass == groups);
     const bool block_products = N == 2048 && K1 == 2 && a.level <= 8 && !g_ntt_kernel_serial && !a.mb_generic_products;
     // From MB_KB_SLOTS_FROM ciphertexts on the keybundles stay in the key's slot order (the latency kernel reads them
     // like a classic key): the keybundle kernel drops its slot -> position transposition, 4-10 % of a round of 32-256
     // blocks; below, position order — one 64-byte run per thread and row is worth 3 % to a PBS that runs alone
     const bool slots = block_products && a.num_samples >= MB_KB_SLOTS_FROM;
-    if (N == 2048 && K1 == 2 && a.num_samples < 4) {
-      if (slots)
-        HX_LAUNCH((mb_keybundle_2048_kernel<1, true>), dim3(gpass * kb_polys, a.num_samples), dim3(256), 0, st, a,
-                  m.grouping_factor, kb_lat, tb, g0, group_chunk);
-      else
-        HX_LAUNCH((mb_keybundle_2048_kernel<1, false>), dim3(gpass * kb_polys, a.num_samples), dim3(256), 0, st, a,
-                  m.grouping_factor, kb_lat, tb, g0, group_chunk);
-    } else if (N == 2048 && K1 == 2) {
-      const dim3 grid(gpass * kb_polys, (a.num_samples + MB_KB_TILE - 1) / MB_KB_TILE);
-      if (slots)
+    const bool tiled = a.num_samples >= 4;  // MB_KB_TILE ciphertexts per workgroup; below, one
+    const dim3 grid(gpass * kb_polys, tiled ? (a.num_samples + MB_KB_TILE - 1) / MB_KB_TILE : a.num_samples);
+    if constexpr (N == 2048 && K1 == 2) {
+      if (!tiled && slots)
+        HX_LAUNCH((mb_keybundle_2048_kernel<1, true>), grid, dim3(256), 0, st, a, m.grouping_factor, kb_lat, tb, g0,
+                  group_chunk);
+      else if (!tiled)
+        HX_LAUNCH((mb_keybundle_2048_kernel<1, false>), grid, dim3(256), 0, st, a, m.grouping_factor, kb_lat, tb, g0,
+                  group_chunk);
+      else if (slots)
         HX_LAUNCH((mb_keybundle_2048_kernel<MB_KB_TILE, true>), grid, dim3(256), 0, st, a, m.grouping_factor, kb_lat, tb,
                   g0, group_chunk);
       else
         HX_LAUNCH((mb_keybundle_2048_kernel<MB_KB_TILE, false>), grid, dim3(256), 0, st, a, m.grouping_factor, kb_lat,
                   tb, g0, group_chunk);
+    } else {
+      if (!tiled)
+        HX_LAUNCH((mb_keybundle_kernel<N, K1, 1>), grid, dim3(GenericCfg<N>::TPB), 16 * sizeof(uint32_t), st, a,
+                  m.grouping_factor, kb_lat, tb, g0, group_chunk);
+      else
+        HX_LAUNCH((mb_keybundle_kernel<N, K1, MB_KB_TILE>), grid, dim3(GenericCfg<N>::TPB),
+                  MB_KB_TILE * 16 * sizeof(uint32_t), st, a, m.grouping_factor, kb_lat, tb, g0, group_chunk);
     }
-    else if (a.num_samples < 4)
-      HX_LAUNCH((mb_keybundle_kernel<N, K1, 1>), dim3(gpass * kb_polys, a.num_samples), dim3(GenericCfg<N>::TPB),
-                16 * sizeof(uint32_t), st, a, m.grouping_factor, kb_lat, tb, g0, group_chunk);
-    else
-      HX_LAUNCH((mb_keybundle_kernel<N, K1, MB_KB_TILE>), dim3(gpass * kb_polys, (a.num_samples + MB_KB_TILE - 1) / MB_KB_TILE),
-                dim3(GenericCfg<N>::TPB), MB_KB_TILE * 16 * sizeof(uint32_t), st, a, m.grouping_factor, kb_lat, tb, g0,
-                group_chunk);
-    if (!block_products) note_pbs_instantiation(0, 0, 0, par ? PBS_INST_PAR : PBS_INST_PLAIN, 1, N, K1);
     if (block_products)
       // the latency kernel's structure (registers + wave-local exchanges, 4 barriers per product)
-      launch_mb_accumulate_block(st, a, tb, (const cplx *)kb_lat, acc_g, group_chunk, gpass, (int)(g0 == 0),
-                                 (int)(g0 + gpass == groups), (int)slots);
-    else if (par)
-      HX_LAUNCH((mb_accumulate_par_kernel<N, K1>), dim3(a.num_samples), dim3(K1 * GenericCfg<N>::TPB), smem_p, st, a,
-                (const cplx *)kb_lat, tb, acc_g, group_chunk, gpass, (int)(g0 == 0), (int)(g0 + gpass == groups));
+      launch_mb_accumulate_block(st, a, tb, (const cplx *)kb_lat, acc_g, group_chunk, gpass, first, last, (int)slots);
     else
-      HX_LAUNCH((mb_accumulate_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem_b, st, a,
-                (const cplx *)kb_lat, tb, acc_g, group_chunk, gpass, (int)(g0 == 0), (int)(g0 + gpass == groups));
+      launch_mb_products<N, K1>(st, a, tb, (const cplx *)kb_lat, acc_g, group_chunk, gpass, first, last);
   }
 }
 
@@ -478,34 +448,18 @@ void launch_pbs_multi_bit(hipStream_t st, uint32_t N, uint32_t glwe_dim, const M
                           uint64_t *acc_scratch) {
   MultiBitArgs m = m0;
   m.pbs.acc_scratch = acc_scratch;
-  const uint32_t k1 = glwe_dim + 1;
-  bool ok = true;
-  switch (N) {
-    case 8192: if (k1 == 2) launch_mb_big<8192>(st, m, tb); else ok = false; break;
-    case 16384: if (k1 == 2) launch_mb_big<16384>(st, m, tb); else ok = false; break;
-    case 256: if (k1 == 2) launch_mb<256, 2>(st, m, tb); else if (k1 == 3) launch_mb<256, 3>(st, m, tb); else if (k1 == 4) launch_mb<256, 4>(st, m, tb); else ok = false; break;
-    case 512: if (k1 == 2) launch_mb<512, 2>(st, m, tb); else if (k1 == 3) launch_mb<512, 3>(st, m, tb); else if (k1 == 4) launch_mb<512, 4>(st, m, tb); else ok = false; break;
-    case 1024: if (k1 == 2) launch_mb<1024, 2>(st, m, tb); else if (k1 == 3) launch_mb<1024, 3>(st, m, tb); else if (k1 == 4) launch_mb<1024, 4>(st, m, tb); else ok = false; break;
-    case 2048: if (k1 == 2) launch_mb<2048, 2>(st, m, tb); else if (k1 == 3) launch_mb<2048, 3>(st, m, tb); else ok = false; break;
-    case 4096: if (k1 == 2) launch_mb<4096, 2>(st, m, tb); else ok = false; break;
-    default: ok = false;
-  }
-  if (!ok) HX_PANIC("unsupported (polynomial_size=%u, glwe_dimension=%u) for the multi-bit PBS", N, glwe_dim);
+  if (glwe_dim == 1 && N == 8192) return launch_mb_big<8192>(st, m, tb);
+  if (glwe_dim == 1 && N == 16384) return launch_mb_big<16384>(st, m, tb);
+  dispatch_nk(N, glwe_dim, "multi-bit PBS", [&](auto n, auto k1) {
+    launch_mb<decltype(n)::value, decltype(k1)::value>(st, m, tb);
+  });
 }
 
 void launch_pbs_multi_bit_latency(hipStream_t st, uint32_t N, uint32_t glwe_dim, const MultiBitArgs &m,
                                   const FftTables &tb, cplx *kb_lat, uint32_t group_chunk, uint64_t *acc_g) {
-  const uint32_t k1 = glwe_dim + 1;
-  bool ok = true;
-  switch (N) {
-    case 256: if (k1 == 2) launch_mb_latency<256, 2>(st, m, tb, kb_lat, group_chunk, acc_g); else if (k1 == 3) launch_mb_latency<256, 3>(st, m, tb, kb_lat, group_chunk, acc_g); else if (k1 == 4) launch_mb_latency<256, 4>(st, m, tb, kb_lat, group_chunk, acc_g); else ok = false; break;
-    case 512: if (k1 == 2) launch_mb_latency<512, 2>(st, m, tb, kb_lat, group_chunk, acc_g); else if (k1 == 3) launch_mb_latency<512, 3>(st, m, tb, kb_lat, group_chunk, acc_g); else if (k1 == 4) launch_mb_latency<512, 4>(st, m, tb, kb_lat, group_chunk, acc_g); else ok = false; break;
-    case 1024: if (k1 == 2) launch_mb_latency<1024, 2>(st, m, tb, kb_lat, group_chunk, acc_g); else if (k1 == 3) launch_mb_latency<1024, 3>(st, m, tb, kb_lat, group_chunk, acc_g); else if (k1 == 4) launch_mb_latency<1024, 4>(st, m, tb, kb_lat, group_chunk, acc_g); else ok = false; break;
-    case 2048: if (k1 == 2) launch_mb_latency<2048, 2>(st, m, tb, kb_lat, group_chunk, acc_g); else if (k1 == 3) launch_mb_latency<2048, 3>(st, m, tb, kb_lat, group_chunk, acc_g); else ok = false; break;
-    case 4096: if (k1 == 2) launch_mb_latency<4096, 2>(st, m, tb, kb_lat, group_chunk, acc_g); else ok = false; break;
-    default: ok = false;
-  }
-  if (!ok) HX_PANIC("unsupported (polynomial_size=%u, glwe_dimension=%u) for the multi-bit PBS", N, glwe_dim);
+  dispatch_nk(N, glwe_dim, "multi-bit PBS", [&](auto n, auto k1) {
+    launch_mb_latency<decltype(n)::value, decltype(k1)::value>(st, m, tb, kb_lat, group_chunk, acc_g);
+  });
 }
 
 }  // namespace tfhe_hip

@@ -7,10 +7,14 @@
 // replaces backends/tfhe-cuda-backend/cuda/src/pbs/programmable_bootstrap_classic.cuh:783-1033
 // (two launches per iteration there; the whole loop is one launch here).
 //
+// Every kernel here is prologue (PbsSample, block_body_modulus_switch, block_load_lut of pbs_generic.h), CMUX loop,
+// sample extraction.  The CMUX loops stay written out per kernel: the f64 ones in two schedules (a single thread group,
+// or one group per GLWE polynomial) that share untwist_to_torus, the NTT and exact ones on integers.  The shapes are
+// the rows of PBS_SHAPES_NK, reached through dispatch_nk.
+//
 // These kernels favour generality; the throughput kernel for the headline parameter set lives
 // in pbs_fft_wave.hip and produces bit-identical results (same butterfly dataflow).
-#include "pbs_common.h"
-#include "kernels.h"
+#include "pbs_generic.h"
 
 namespace tfhe_hip {
 bool g_ntt_kernel_serial = false;
@@ -43,23 +47,15 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB) pbs_fft_generic_kernel(Pbs
   const uint32_t sample = blockIdx.x;
   uint64_t *acc = ACC_GLOBAL ? a.acc_scratch + (size_t)sample * K1 * N : (uint64_t *)smem;  // K1*N torus words
   const FBuf fbuf{(cplx *)(smem + (ACC_GLOBAL ? 0 : (size_t)K1 * N * 8))};                  // n complex points, padded
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  const PbsSample<N, K1> s(a, sample);
   const cplx *bsk = (const cplx *)a.bsk;
 
-  const uint32_t b_hat = block_body_modulus_switch<TPB>(lwe, a.n, LOG2N2, a.ms_type, (uint64_t *)fbuf.p, tid);
-  // acc <- LUT * X^{-b_hat}
-  for (int p = 0; p < K1; ++p)
-    for (uint32_t j = tid; j < (uint32_t)N; j += TPB) {
-      bool neg;
-      const uint32_t src = monomial_div_src(j, b_hat, N, neg);
-      const uint64_t v = lut[p * N + src];
-      acc[p * N + j] = neg ? (uint64_t)0 - v : v;
-    }
+  const uint32_t b_hat = block_body_modulus_switch<TPB>(s.lwe, a.n, LOG2N2, a.ms_type, (uint64_t *)fbuf.p, tid);
+  block_load_lut<N, TPB>(acc, s.lut, b_hat, 0, K1, tid);
   __syncthreads();
 
   for (uint32_t i = 0; i < a.n; ++i) {
-    const uint32_t a_hat = (uint32_t)modulus_switch(lwe[i], LOG2N2);
+    const uint32_t a_hat = (uint32_t)modulus_switch(s.lwe[i], LOG2N2);
     if (a_hat == 0) continue;  // uniform across the workgroup (bootstrap.rs:334)
     cplx facc[K1][PER];
     bool first = true;
@@ -90,15 +86,7 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB) pbs_fft_generic_kernel(Pbs
       for (int q = 0; q < PER; ++q) fbuf[tid + q * TPB] = facc[c][q];
       __syncthreads();
       lds_fft_inverse<N, TPB>(fbuf, tb.inv, tid);
-      for (int q = 0; q < PER; ++q) {
-        const int j = tid + q * TPB;
-        const cplx y = fbuf[j];
-        const double ur = tb.untw[2 * j], ui = tb.untw[2 * j + 1];
-        const double tr = fma(-y.im, ui, y.re * ur);
-        const double ti = fma(y.im, ur, y.re * ui);
-        acc[c * N + j] += from_torus(tr);
-        acc[c * N + j + n] += from_torus(ti);
-      }
+      for (int q = 0; q < PER; ++q) untwist_to_torus<N, true>(fbuf[tid + q * TPB], tb.untw, acc, c, tid + q * TPB);
       __syncthreads();
     }
   }
@@ -111,52 +99,24 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB) pbs_fft_generic_kernel(Pbs
 template <int N, int K1>
 __global__ void __launch_bounds__(K1 *GenericCfg<N>::TPB) pbs_fft_par_kernel(PbsArgs a, FftTables tb) {
   constexpr int n = N / 2, TPB = GenericCfg<N>::TPB, TPBT = K1 * TPB, PER = n / TPB, LOG2N2 = ilog2_c(2 * N);
+  // block_body_modulus_switch<TPBT>: TPBT a power of two, 2*TPBT words of scratch in the transform buffers
+  static_assert((TPBT & (TPBT - 1)) == 0 && (size_t)2 * TPBT * 8 <= K1 * fbuf_bytes(N), "modulus-switch scratch");
   HX_DYN_SMEM(smem);
   uint64_t *acc = (uint64_t *)smem;                  // K1*N torus words
   cplx *fbase = (cplx *)(smem + (size_t)K1 * N * 8);  // K1 padded transform buffers of n complex points
   const int tid = threadIdx.x;
   const int grp = tid / TPB, lt = tid - grp * TPB;   // my row (forward) / column (inverse), thread inside it
   const uint32_t sample = blockIdx.x;
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  const PbsSample<N, K1> s(a, sample);
   const cplx *bsk = (const cplx *)a.bsk;
   const FBuf mybuf{fbase + (size_t)grp * fbuf_slots(N)};
 
-  // body modulus switch; TPBT need not be a power of two (k = 2), so the reduction is a plain sum
-  uint64_t corr = 0;
-  if (a.ms_type == 1) {
-    uint64_t *scratch = (uint64_t *)fbase;
-    uint64_t sh = 0;
-    int64_t sd = 0;
-    for (uint32_t i = tid; i < a.n; i += TPBT) {
-      uint64_t h;
-      int64_t d;
-      centered_ms_terms(lwe[i], LOG2N2, h, d);
-      sh += h;
-      sd += d;
-    }
-    scratch[tid] = sh;
-    scratch[TPBT + tid] = (uint64_t)sd;
-    __syncthreads();
-    uint64_t th = 0, td = 0;
-    for (int l = 0; l < TPBT; ++l) {
-      th += scratch[l];
-      td += scratch[TPBT + l];
-    }
-    __syncthreads();
-    corr = centered_ms_finish(th, (int64_t)td, LOG2N2);
-  }
-  const uint32_t b_hat = (uint32_t)modulus_switch(lwe[a.n] + corr, LOG2N2);
-  for (uint32_t j = lt; j < (uint32_t)N; j += TPB) {  // acc <- LUT * X^{-b_hat}
-    bool neg;
-    const uint32_t src = monomial_div_src(j, b_hat, N, neg);
-    const uint64_t v = lut[grp * N + src];
-    acc[grp * N + j] = neg ? (uint64_t)0 - v : v;
-  }
+  const uint32_t b_hat = block_body_modulus_switch<TPBT>(s.lwe, a.n, LOG2N2, a.ms_type, (uint64_t *)fbase, tid);
+  block_load_lut<N, TPB>(acc, s.lut, b_hat, grp, grp + 1, lt);
   __syncthreads();
 
   for (uint32_t i = 0; i < a.n; ++i) {
-    const uint32_t a_hat = (uint32_t)modulus_switch(lwe[i], LOG2N2);
+    const uint32_t a_hat = (uint32_t)modulus_switch(s.lwe[i], LOG2N2);
     if (a_hat == 0) continue;  // uniform across the workgroup (bootstrap.rs:334)
     cplx facc[PER];
     for (uint32_t idx = 0; idx < a.level; ++idx) {
@@ -181,13 +141,7 @@ __global__ void __launch_bounds__(K1 *GenericCfg<N>::TPB) pbs_fft_par_kernel(Pbs
     for (int q = 0; q < PER; ++q) mybuf[lt + q * TPB] = facc[q];
     __syncthreads();
     lds_fft_inverse<N, TPB>(mybuf, tb.inv, lt);
-    for (int q = 0; q < PER; ++q) {
-      const int j = lt + q * TPB;
-      const cplx y = mybuf[j];
-      const double ur = tb.untw[2 * j], ui = tb.untw[2 * j + 1];
-      acc[grp * N + j] += from_torus(fma(-y.im, ui, y.re * ur));
-      acc[grp * N + j + n] += from_torus(fma(y.im, ur, y.re * ui));
-    }
+    for (int q = 0; q < PER; ++q) untwist_to_torus<N, true>(mybuf[lt + q * TPB], tb.untw, acc, grp, lt + q * TPB);
     __syncthreads();
   }
   block_sample_extract<N, K1, TPBT>(a, acc, sample, 0, false, tid);
@@ -206,22 +160,15 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB) pbs_exact_generic_kernel(P
   int64_t *dig = (int64_t *)(acc + (size_t)K1 * N);  // N digits of one (level, row)
   const int tid = threadIdx.x;
   const uint32_t sample = blockIdx.x;
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  const PbsSample<N, K1> s(a, sample);
   const uint64_t *bsk = (const uint64_t *)a.bsk;
 
-  const uint32_t b_hat = block_body_modulus_switch<TPB>(lwe, a.n, LOG2N2, a.ms_type, (uint64_t *)dig, tid);
-  for (int p = 0; p < K1; ++p)
-    for (uint32_t j = tid; j < (uint32_t)N; j += TPB) {
-      bool neg;
-      const uint32_t src = monomial_div_src(j, b_hat, N, neg);
-      const uint64_t v = lut[p * N + src];
-      acc[p * N + j] = neg ? (uint64_t)0 - v : v;
-    }
+  const uint32_t b_hat = block_body_modulus_switch<TPB>(s.lwe, a.n, LOG2N2, a.ms_type, (uint64_t *)dig, tid);
+  block_load_lut<N, TPB>(acc, s.lut, b_hat, 0, K1, tid);
   __syncthreads();
 
   for (uint32_t i = 0; i < a.n; ++i) {
-    const uint32_t a_hat = (uint32_t)modulus_switch(lwe[i], LOG2N2);
+    const uint32_t a_hat = (uint32_t)modulus_switch(s.lwe[i], LOG2N2);
     if (a_hat == 0) continue;
     uint64_t oacc[K1][PER];
     for (int c = 0; c < K1; ++c)
@@ -261,21 +208,16 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB) pbs_ntt_generic_kernel(Pbs
   uint64_t *nbuf = acc + (size_t)K1 * N;  // N
   const int tid = threadIdx.x;
   const uint32_t sample = blockIdx.x;
-  if (a.only_flagged != nullptr) {  // the recomputation behind a split-key launch: its flagged ciphertexts only
-    if (a.only_flagged[sample] == 0u) return;
-    if (tid == 0 && a.recomputed != nullptr) atomicAdd(a.recomputed, 1u);
-  }
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  if (skip_unflagged_and_count(a, sample, tid)) return;
+  const PbsSample<N, K1> s(a, sample);
   const uint64_t *bsk = (const uint64_t *)a.bsk;
 
-  const uint32_t b_hat = block_body_modulus_switch<TPB>(lwe, a.n, LOG2N2, a.ms_type, nbuf, tid);
-  for (int p = 0; p < K1; ++p)
-    for (uint32_t j = tid; j < (uint32_t)N; j += TPB) acc[p * N + j] = lut[p * N + j];
+  const uint32_t b_hat = block_body_modulus_switch<TPB>(s.lwe, a.n, LOG2N2, a.ms_type, nbuf, tid);
+  block_copy_lut<N, TPB>(acc, s.lut, 0, K1, tid);
   __syncthreads();
 
   for (uint32_t i = 0; i < a.n; ++i) {
-    const uint32_t a_hat = (uint32_t)modulus_switch(lwe[i], LOG2N2);
+    const uint32_t a_hat = (uint32_t)modulus_switch(s.lwe[i], LOG2N2);
     if (a_hat == 0) continue;
     uint64_t nacc[K1][PER];
     for (int c = 0; c < K1; ++c)
@@ -319,50 +261,25 @@ __global__ void __launch_bounds__(GenericCfg<N>::TPB) pbs_ntt_generic_kernel(Pbs
 template <int N, int K1>
 __global__ void __launch_bounds__(K1 *GenericCfg<N>::TPB) pbs_ntt_par_kernel(PbsArgs a, NttTables tb) {
   constexpr int TPB = GenericCfg<N>::TPB, TPBT = K1 * TPB, PER = N / TPB, LOG2N2 = ilog2_c(2 * N);
+  // block_body_modulus_switch<TPBT>: TPBT a power of two, 2*TPBT words of scratch in the transform buffers
+  static_assert((TPBT & (TPBT - 1)) == 0 && 2 * TPBT * 8 <= K1 * N * 8, "modulus-switch scratch");
   HX_DYN_SMEM(smem);
   uint64_t *acc = (uint64_t *)smem;          // K1*N torus words
   uint64_t *nbuf = acc + (size_t)K1 * N;     // K1*N field elements (one transform buffer per group)
   const int tid = threadIdx.x;
   const int grp = tid / TPB, lt = tid - grp * TPB;  // my row (forward) / column (inverse), thread inside it
   const uint32_t sample = blockIdx.x;
-  if (a.only_flagged != nullptr) {  // the recomputation behind a split-key launch: its flagged ciphertexts only
-    if (a.only_flagged[sample] == 0u) return;
-    if (tid == 0 && a.recomputed != nullptr) atomicAdd(a.recomputed, 1u);
-  }
-  const uint64_t *lwe = a.lwe_in + (size_t)a.in_idx[sample] * (a.n + 1);
-  const uint64_t *lut = a.lut + (size_t)a.lut_idx[sample] * K1 * N;
+  if (skip_unflagged_and_count(a, sample, tid)) return;
+  const PbsSample<N, K1> s(a, sample);
   const uint64_t *bsk = (const uint64_t *)a.bsk;
   uint64_t *mybuf = nbuf + (size_t)grp * N;
 
-  // body modulus switch; TPBT need not be a power of two (k = 2), so the reduction is a plain sum
-  uint64_t corr = 0;
-  if (a.ms_type == 1) {
-    uint64_t sh = 0;
-    int64_t sd = 0;
-    for (uint32_t i = tid; i < a.n; i += TPBT) {
-      uint64_t h;
-      int64_t d;
-      centered_ms_terms(lwe[i], LOG2N2, h, d);
-      sh += h;
-      sd += d;
-    }
-    nbuf[tid] = sh;
-    nbuf[TPBT + tid] = (uint64_t)sd;
-    __syncthreads();
-    uint64_t th = 0, td = 0;
-    for (int l = 0; l < TPBT; ++l) {
-      th += nbuf[l];
-      td += nbuf[TPBT + l];
-    }
-    __syncthreads();
-    corr = centered_ms_finish(th, (int64_t)td, LOG2N2);
-  }
-  const uint32_t b_hat = (uint32_t)modulus_switch(lwe[a.n] + corr, LOG2N2);
-  for (uint32_t j = lt; j < (uint32_t)N; j += TPB) acc[grp * N + j] = lut[grp * N + j];
+  const uint32_t b_hat = block_body_modulus_switch<TPBT>(s.lwe, a.n, LOG2N2, a.ms_type, nbuf, tid);
+  block_copy_lut<N, TPB>(acc, s.lut, grp, grp + 1, lt);
   __syncthreads();
 
   for (uint32_t i = 0; i < a.n; ++i) {
-    const uint32_t a_hat = (uint32_t)modulus_switch(lwe[i], LOG2N2);
+    const uint32_t a_hat = (uint32_t)modulus_switch(s.lwe[i], LOG2N2);
     if (a_hat == 0) continue;
     uint64_t nacc[PER];
     for (int q = 0; q < PER; ++q) nacc[q] = 0;
@@ -475,56 +392,35 @@ static void launch_fft_big(hipStream_t st, const PbsArgs &a, const FftTables &tb
 }
 template <int N, int K1>
 static void launch_fft(hipStream_t st, const PbsArgs &a, const FftTables &tb) {
-  // one group per polynomial pays off for k = 1 (43.5k PBS/s at 2_2); with three groups (k = 2, N = 1024) the
-  // larger workgroup costs more occupancy than the shorter barrier chain returns (45.9k vs 59.0k): single group
-  note_pbs_instantiation(0, 0, 0, (g_ntt_kernel_serial || K1 != 2) ? PBS_INST_PLAIN : PBS_INST_PAR, 1, N, K1);
-  if (g_ntt_kernel_serial || K1 != 2) {
-    const size_t smem = (size_t)K1 * N * 8 + fbuf_bytes(N);
-    hx_set_dynamic_smem_once<pbs_fft_generic_kernel<N, K1>>(smem);
-    HX_LAUNCH((pbs_fft_generic_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a, tb);
-    return;
+  const bool par = generic_runs_par(K1);
+  note_pbs_instantiation(0, 0, 0, par ? PBS_INST_PAR : PBS_INST_PLAIN, 1, N, K1);
+  if constexpr (K1 == 2) {
+    if (par) {
+      const size_t smem = (size_t)K1 * N * 8 + (size_t)K1 * fbuf_bytes(N);
+      hx_set_dynamic_smem_once<pbs_fft_par_kernel<N, K1>>(smem);
+      HX_LAUNCH((pbs_fft_par_kernel<N, K1>), dim3(a.num_samples), dim3(K1 * GenericCfg<N>::TPB), smem, st, a, tb);
+      return;
+    }
   }
-  const size_t smem = (size_t)K1 * N * 8 + (size_t)K1 * fbuf_bytes(N);
-  hx_set_dynamic_smem_once<pbs_fft_par_kernel<N, K1>>(smem);
-  HX_LAUNCH((pbs_fft_par_kernel<N, K1>), dim3(a.num_samples), dim3(K1 * GenericCfg<N>::TPB), smem, st, a, tb);
+  const size_t smem = (size_t)K1 * N * 8 + fbuf_bytes(N);
+  hx_set_dynamic_smem_once<pbs_fft_generic_kernel<N, K1>>(smem);
+  HX_LAUNCH((pbs_fft_generic_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a, tb);
 }
 template <int N, int K1>
 static void launch_ntt(hipStream_t st, const PbsArgs &a, const NttTables &tb) {
-  note_pbs_instantiation(0, 0, 0, (g_ntt_kernel_serial || K1 != 2) ? PBS_INST_PLAIN : PBS_INST_PAR, 1, N, K1);
-  if (g_ntt_kernel_serial || K1 != 2) {  // same rule as the f64 engine above
-    const size_t smem = (size_t)(K1 + 1) * N * 8;
-    hx_set_dynamic_smem_once<pbs_ntt_generic_kernel<N, K1>>(smem);
-    HX_LAUNCH((pbs_ntt_generic_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a, tb);
-    return;
+  const bool par = generic_runs_par(K1);
+  note_pbs_instantiation(0, 0, 0, par ? PBS_INST_PAR : PBS_INST_PLAIN, 1, N, K1);
+  if constexpr (K1 == 2) {
+    if (par) {
+      const size_t smem = (size_t)2 * K1 * N * 8;
+      hx_set_dynamic_smem_once<pbs_ntt_par_kernel<N, K1>>(smem);
+      HX_LAUNCH((pbs_ntt_par_kernel<N, K1>), dim3(a.num_samples), dim3(K1 * GenericCfg<N>::TPB), smem, st, a, tb);
+      return;
+    }
   }
-  const size_t smem = (size_t)2 * K1 * N * 8;
-  hx_set_dynamic_smem_once<pbs_ntt_par_kernel<N, K1>>(smem);
-  HX_LAUNCH((pbs_ntt_par_kernel<N, K1>), dim3(a.num_samples), dim3(K1 * GenericCfg<N>::TPB), smem, st, a, tb);
-}
-
-#define HX_DISPATCH_NK(FN, ...)                                                              \
-  do {                                                                                       \
-    const uint32_t k1_ = glwe_dim + 1;                                                       \
-    bool ok_ = true;                                                                         \
-    switch (N) {                                                                             \
-      case 256: if (k1_ == 2) FN<256, 2>(__VA_ARGS__); else if (k1_ == 3) FN<256, 3>(__VA_ARGS__); else if (k1_ == 4) FN<256, 4>(__VA_ARGS__); else ok_ = false; break; \
-      case 512: if (k1_ == 2) FN<512, 2>(__VA_ARGS__); else if (k1_ == 3) FN<512, 3>(__VA_ARGS__); else if (k1_ == 4) FN<512, 4>(__VA_ARGS__); else ok_ = false; break; \
-      case 1024: if (k1_ == 2) FN<1024, 2>(__VA_ARGS__); else if (k1_ == 3) FN<1024, 3>(__VA_ARGS__); else if (k1_ == 4) FN<1024, 4>(__VA_ARGS__); else ok_ = false; break; \
-      case 2048: if (k1_ == 2) FN<2048, 2>(__VA_ARGS__); else if (k1_ == 3) FN<2048, 3>(__VA_ARGS__); else ok_ = false; break; \
-      case 4096: if (k1_ == 2) FN<4096, 2>(__VA_ARGS__); else ok_ = false; break;             \
-      default: ok_ = false;                                                                  \
-    }                                                                                        \
-    if (!ok_) HX_PANIC("unsupported (polynomial_size=%u, glwe_dimension=%u) for the MI355X PBS", N, glwe_dim); \
-  } while (0)
-
-void launch_pbs_fft_generic(hipStream_t st, uint32_t N, uint32_t glwe_dim, const PbsArgs &a, const FftTables &tb) {
-  if (N > 4096) {  // f64 engine only, k = 1 (the reference's 3_3 / 4_4 sets)
-    HX_PANIC_IF_FALSE(glwe_dim == 1 && (N == 8192 || N == 16384),
-                      "unsupported (polynomial_size=%u, glwe_dimension=%u) for the MI355X PBS", N, glwe_dim);
-    if (N == 8192) launch_fft_big<8192>(st, a, tb); else launch_fft_big<16384>(st, a, tb);
-    return;
-  }
-  HX_DISPATCH_NK(launch_fft, st, a, tb);
+  const size_t smem = (size_t)(K1 + 1) * N * 8;
+  hx_set_dynamic_smem_once<pbs_ntt_generic_kernel<N, K1>>(smem);
+  HX_LAUNCH((pbs_ntt_generic_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a, tb);
 }
 template <int N, int K1>
 static void launch_exact(hipStream_t st, const PbsArgs &a) {
@@ -533,11 +429,27 @@ static void launch_exact(hipStream_t st, const PbsArgs &a) {
   note_pbs_instantiation(0, 0, 0, PBS_INST_PLAIN, 1, N, K1);
   HX_LAUNCH((pbs_exact_generic_kernel<N, K1>), dim3(a.num_samples), dim3(GenericCfg<N>::TPB), smem, st, a);
 }
+
+void launch_pbs_fft_generic(hipStream_t st, uint32_t N, uint32_t glwe_dim, const PbsArgs &a, const FftTables &tb) {
+  if (N > 4096) {  // f64 engine only, k = 1 (the reference's 3_3 / 4_4 sets)
+    HX_PANIC_IF_FALSE(glwe_dim == 1 && (N == 8192 || N == 16384),
+                      "unsupported (polynomial_size=%u, glwe_dimension=%u) for the MI355X PBS", N, glwe_dim);
+    if (N == 8192) launch_fft_big<8192>(st, a, tb); else launch_fft_big<16384>(st, a, tb);
+    return;
+  }
+  dispatch_nk(N, glwe_dim, "MI355X PBS", [&](auto n, auto k1) {
+    launch_fft<decltype(n)::value, decltype(k1)::value>(st, a, tb);
+  });
+}
 void launch_pbs_exact_generic(hipStream_t st, uint32_t N, uint32_t glwe_dim, const PbsArgs &a) {
-  HX_DISPATCH_NK(launch_exact, st, a);
+  dispatch_nk(N, glwe_dim, "MI355X PBS", [&](auto n, auto k1) {
+    launch_exact<decltype(n)::value, decltype(k1)::value>(st, a);
+  });
 }
 void launch_pbs_ntt_generic(hipStream_t st, uint32_t N, uint32_t glwe_dim, const PbsArgs &a, const NttTables &tb) {
-  HX_DISPATCH_NK(launch_ntt, st, a, tb);
+  dispatch_nk(N, glwe_dim, "MI355X PBS", [&](auto n, auto k1) {
+    launch_ntt<decltype(n)::value, decltype(k1)::value>(st, a, tb);
+  });
 }
 
 template <int N> static void launch_conv_f(hipStream_t st, const uint64_t *src, void *dst, size_t polys, const FftTables &tb, int slot_order) {
@@ -548,21 +460,24 @@ template <int N> static void launch_conv_f(hipStream_t st, const uint64_t *src, 
 template <int N> static void launch_conv_n(hipStream_t st, const uint64_t *src, void *dst, size_t polys, const NttTables &tb) {
   HX_LAUNCH((bsk_to_ntt_kernel<N>), dim3((unsigned)polys), dim3(GenericCfg<N>::TPB), (size_t)N * 8, st, src, (uint64_t *)dst, tb);
 }
-#define HX_DISPATCH_N(FN, ...)                                              \
-  switch (N) {                                                              \
-    case 256: FN<256>(__VA_ARGS__); break;                                  \
-    case 512: FN<512>(__VA_ARGS__); break;                                  \
-    case 1024: FN<1024>(__VA_ARGS__); break;                                \
-    case 2048: FN<2048>(__VA_ARGS__); break;                                \
-    case 4096: FN<4096>(__VA_ARGS__); break;                                \
-    default: HX_PANIC("unsupported polynomial_size=%u", N);                 \
+// f(N) with the ring size of a key conversion as a compile-time constant
+template <class F>
+static void dispatch_n(uint32_t N, F &&f) {
+  switch (N) {
+    case 256: f(std::integral_constant<int, 256>{}); break;
+    case 512: f(std::integral_constant<int, 512>{}); break;
+    case 1024: f(std::integral_constant<int, 1024>{}); break;
+    case 2048: f(std::integral_constant<int, 2048>{}); break;
+    case 4096: f(std::integral_constant<int, 4096>{}); break;
+    default: HX_PANIC("unsupported polynomial_size=%u", N);
   }
+}
 void launch_bsk_to_fourier(hipStream_t st, uint32_t N, uint32_t glwe_dim, const uint64_t *src_dev, void *dst, size_t polys, const FftTables &tb) {
   // must agree with bsk_slot<N, K1>
   const int slot_order = (N == 2048 && glwe_dim == 1) ? 1 : (N == 1024 && (glwe_dim == 1 || glwe_dim == 2)) ? 2 : 0;
   if (N == 8192) return launch_conv_f<8192>(st, src_dev, dst, polys, tb, slot_order);
   if (N == 16384) return launch_conv_f<16384>(st, src_dev, dst, polys, tb, slot_order);
-  HX_DISPATCH_N(launch_conv_f, st, src_dev, dst, polys, tb, slot_order);
+  dispatch_n(N, [&](auto n) { launch_conv_f<decltype(n)::value>(st, src_dev, dst, polys, tb, slot_order); });
 }
 void launch_bsk_to_split(hipStream_t st, uint32_t N, const uint64_t *src_dev, void *dst, size_t polys, const FftTables &tb) {
   HX_PANIC_IF_FALSE(N == 2048, "split-key exact engine: polynomial_size %u not supported (2048)", N);
@@ -570,7 +485,7 @@ void launch_bsk_to_split(hipStream_t st, uint32_t N, const uint64_t *src_dev, vo
             fbuf_bytes(2048), st, src_dev, (cplx *)dst, tb);
 }
 void launch_bsk_to_ntt(hipStream_t st, uint32_t N, const uint64_t *src_dev, void *dst, size_t polys, const NttTables &tb) {
-  HX_DISPATCH_N(launch_conv_n, st, src_dev, dst, polys, tb);
+  dispatch_n(N, [&](auto n) { launch_conv_n<decltype(n)::value>(st, src_dev, dst, polys, tb); });
 }
 
 }  // namespace tfhe_hip
