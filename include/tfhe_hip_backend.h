@@ -732,6 +732,51 @@ void hip_integer_apply_noise_squashing_64_async(
     CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out, CudaRadixCiphertextFFI const *lwe_array_in,
     int8_t *mem_ptr, void *const *ksks, void *const *bsks);
 void hip_cleanup_integer_apply_noise_squashing_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* The multi-bit programmable bootstrap over the 128-bit torus (std_multi_bit_f128_deterministic_blind_rotate_assign; the
+ * reference's cuda/include/pbs/programmable_bootstrap_multibit.h:18-21,64-80), under hip_ names with the reference's
+ * parameter lists.  The reference-named *_multi_bit_*_128 symbols remain link stubs.
+ *
+ * Key: src is the standard-domain u128 key on the HOST in the reference's container order [input_lwe_dim /
+ * grouping_factor][2^grouping_factor][level, index 0 = last level][glwe_dim + 1][glwe_dim + 1][polynomial_size]; dest takes
+ * as many bytes and keeps that form: the key bundles are summed exactly modulo 2^128 and transformed afterwards.
+ * Bootstrap: sample s reads the u64 LWE lwe_input_indexes[s] of lwe_array_in and writes the u128 LWE lwe_output_indexes[s]
+ * of lwe_array_out; lut_vector is ONE u128 GLWE.  Plain modulus switch, groups in ascending order.  Per chunk of groups one
+ * key-bundle launch and one accumulate launch on `stream`; the scratch fixes the chunk (the largest number of groups whose
+ * bundles fit 512 MiB for its sample count).  Sizes as for hip_programmable_bootstrap_128_async; grouping_factor 2..4
+ * dividing lwe_dimension; num_many_lut must be 1.
+ * Panics: a grouping factor outside 2..4 or not dividing lwe_dimension, an unsupported size, an invalid decomposition, a
+ * scratch of another kind or other sizes, more samples than the scratch holds, a key converted for other sizes or another
+ * grouping factor, a classic 128-bit key (and a multi-bit key given to hip_programmable_bootstrap_128_async). */
+void hip_convert_lwe_multi_bit_programmable_bootstrap_key_128_async(
+    void *stream, uint32_t gpu_index, void *dest, void const *src, uint32_t input_lwe_dim, uint32_t glwe_dim,
+    uint32_t level_count, uint32_t polynomial_size, uint32_t grouping_factor);
+uint64_t hip_scratch_multi_bit_programmable_bootstrap_128_async(
+    void *stream, uint32_t gpu_index, int8_t **buffer, uint32_t glwe_dimension, uint32_t polynomial_size,
+    uint32_t level_count, uint32_t input_lwe_ciphertext_count, bool allocate_gpu_memory);
+void hip_multi_bit_programmable_bootstrap_128_async(
+    void *stream, uint32_t gpu_index, void *lwe_array_out, void const *lwe_output_indexes, void const *lut_vector,
+    void const *lwe_array_in, void const *lwe_input_indexes, void const *bootstrapping_key, int8_t *mem_ptr,
+    uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t grouping_factor, uint32_t base_log,
+    uint32_t level_count, uint32_t num_samples, uint32_t num_many_lut, uint32_t lut_stride);
+void hip_cleanup_multi_bit_programmable_bootstrap_128(void *stream, const uint32_t gpu_index, int8_t **buffer);
+/* Noise squashing with a multi-bit 128-bit key: hip_scratch_integer_apply_noise_squashing_64_async's parameter list plus
+ * grouping_factor.  The scratch remembers its kind: hip_integer_apply_noise_squashing_64_async and
+ * hip_cleanup_integer_apply_noise_squashing_64 serve both.  Multi-bit takes the plain modulus switch: a non-zero
+ * noise_reduction_type panics. */
+uint64_t hip_scratch_integer_apply_noise_squashing_multi_bit_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+    uint32_t input_glwe_dimension, uint32_t input_polynomial_size, uint32_t ks_level, uint32_t ks_base_log,
+    uint32_t pbs_level, uint32_t pbs_base_log, uint32_t num_radix_blocks, uint32_t num_original_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t grouping_factor);
+/* test hooks of the multi-bit 128-bit path: groups per pass for scratches created afterwards (0: automatic); the
+ * Fourier-domain key bundle of one group for the LWE lwe_input_indexes[0] of lwe_array_in, (glwe_dimension + 1)^2 *
+ * level_count polynomials of four planes of polynomial_size / 2 doubles */
+void hip_backend_set_pbs128_multibit_chunk(uint32_t groups);
+void hip_test_pbs128_multibit_keybundle_async(
+    void *stream, uint32_t gpu_index, void *bundle_out, void const *bootstrapping_key, void const *lwe_array_in,
+    void const *lwe_input_indexes, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+    uint32_t level_count, uint32_t grouping_factor, uint32_t group);
 /* test hooks of the 128-bit path: the host-built double-double tables (four doubles per entry: re_hi, re_lo, im_hi,
  * im_lo; polynomial_size / 2 entries per table, indexed like hip_test_fft_tables_host's); the u128 signed decomposer
  * (level_count digits per word, least significant first, as i128); the kernels' own complex f128 product of `count`

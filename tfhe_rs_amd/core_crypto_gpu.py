@@ -14,6 +14,7 @@ the Rust module it mirrors:
   cuda_keyswitch_lwe_ciphertext                        gpu/algorithms/lwe_keyswitch.rs:12-143
   cuda_extract_lwe_samples_from_glwe_ciphertext_list   gpu/algorithms/glwe_sample_extraction.rs:12
   CudaLweBootstrapKey128 / cuda_programmable_bootstrap_128_lwe_ciphertext   the u128 bootstrap of noise squashing
+  CudaLweMultiBitBootstrapKey128 / cuda_multi_bit_programmable_bootstrap_128_lwe_ciphertext   the same on a multi-bit key
   cuda_fourier_transform_{forward_as_torus,forward_as_integer,backward_as_torus}_f128   gpu/ffi.rs, fft/fft128.h
 The Rust original is the reference's host language; no Rust toolchain exists in this image,
 so the mirror is Python (INTEGRATION.md shows the Rust binding a maintainer would add).
@@ -476,6 +477,71 @@ def cuda_programmable_bootstrap_128_lwe_ciphertext(input, output, accumulator, b
     lib.hip_programmable_bootstrap_128_async(s, g, output.d_vec.ptr, accumulator.d_vec.ptr, input.d_vec.ptr, bsk.d_vec.ptr,
                                              buf, *shape, bsk.decomp_base_log, bsk.decomp_level_count, num_samples)
     lib.hip_cleanup_programmable_bootstrap_128(s, g, C.byref(buf))
+
+
+class CudaLweMultiBitBootstrapKey128:
+    """gpu/entities/lwe_multi_bit_bootstrap_key.rs (the u128 multi-bit key of noise squashing): the standard-domain key,
+    [n / g][2^g][level][k + 1][k + 1][N] u128 words given as uint64 pairs.  It stays in the standard domain on the device:
+    the bootstrap sums a group's key bundle exactly and transforms it afterwards."""
+
+    @classmethod
+    def from_lwe_multi_bit_bootstrap_key(cls, h_bsk, input_lwe_dimension, glwe_dimension, polynomial_size, decomp_base_log,
+                                         decomp_level_count, grouping_factor, streams):
+        self = cls()
+        self.input_lwe_dimension = int(input_lwe_dimension)
+        self.glwe_dimension = int(glwe_dimension)
+        self.polynomial_size = int(polynomial_size)
+        self.decomp_base_log = int(decomp_base_log)
+        self.decomp_level_count = int(decomp_level_count)
+        self.grouping_factor = int(grouping_factor)
+        self.ms_noise_reduction = False  # multi-bit has the plain modulus switch only
+        h_bsk = np.ascontiguousarray(h_bsk, dtype=U64)
+        elems = ((self.input_lwe_dimension // max(self.grouping_factor, 1)) * (1 << self.grouping_factor)
+                 * (glwe_dimension + 1) ** 2 * decomp_level_count * polynomial_size)
+        assert h_bsk.size == 2 * elems and h_bsk.shape[-1] == 2, "multi-bit bootstrap key container has the wrong size"
+        self.d_vecs = []
+        for i in range(len(streams)):
+            d = CudaVec(elems, streams, i, elem_words=2)
+            _lib().hip_convert_lwe_multi_bit_programmable_bootstrap_key_128_async(
+                streams.ptr[i], streams.gpu_indexes[i], d.ptr, h_bsk.ctypes.data_as(C.c_void_p),
+                self.input_lwe_dimension, glwe_dimension, decomp_level_count, polynomial_size, self.grouping_factor)
+            self.d_vecs.append(d)
+        streams.synchronize()
+        self.d_vec = self.d_vecs[0]
+        return self
+
+    @property
+    def output_lwe_dimension(self):
+        return self.glwe_dimension * self.polynomial_size
+
+
+def cuda_multi_bit_programmable_bootstrap_128_lwe_ciphertext(input, output, accumulator, output_indexes, input_indexes, bsk,
+                                                             streams):
+    """gpu/algorithms/lwe_multi_bit_programmable_bootstrapping.rs (cuda_multi_bit_programmable_bootstrap_128_lwe_
+    ciphertext): u64 inputs, one u128 accumulator, u128 outputs; sample s reads input_indexes[s] and writes
+    output_indexes[s] (scratch -> launch -> cleanup on streams.ptr[0])."""
+    assert input.lwe_dimension == bsk.input_lwe_dimension, (
+        f"Mismatched input LweDimension. LweCiphertext input LweDimension {input.lwe_dimension}. "
+        f"BootstrapKey input LweDimension {bsk.input_lwe_dimension}.")
+    assert output.lwe_dimension == bsk.output_lwe_dimension, (
+        f"Mismatched output LweDimension. LweCiphertext output LweDimension {output.lwe_dimension}. "
+        f"BootstrapKey output LweDimension {bsk.output_lwe_dimension}.")
+    assert accumulator.glwe_dimension == bsk.glwe_dimension, "Mismatched GlweSize"
+    assert accumulator.polynomial_size == bsk.polynomial_size, "Mismatched PolynomialSize"
+    assert input.d_vec.elem_words == 1 and output.d_vec.elem_words == 2 and accumulator.d_vec.elem_words == 2, \
+        "the 128-bit bootstrap takes u64 inputs, a u128 accumulator and u128 outputs"
+    num_samples = input.lwe_ciphertext_count
+    assert output.lwe_ciphertext_count >= num_samples
+    lib = _lib()
+    buf = C.c_void_p()
+    s, g = streams.ptr[0], streams.gpu_indexes[0]
+    lib.hip_scratch_multi_bit_programmable_bootstrap_128_async(s, g, C.byref(buf), bsk.glwe_dimension, bsk.polynomial_size,
+                                                               bsk.decomp_level_count, num_samples, True)
+    lib.hip_multi_bit_programmable_bootstrap_128_async(
+        s, g, output.d_vec.ptr, output_indexes.ptr, accumulator.d_vec.ptr, input.d_vec.ptr, input_indexes.ptr, bsk.d_vec.ptr,
+        buf, bsk.input_lwe_dimension, bsk.glwe_dimension, bsk.polynomial_size, bsk.grouping_factor, bsk.decomp_base_log,
+        bsk.decomp_level_count, num_samples, 1, 0)
+    lib.hip_cleanup_multi_bit_programmable_bootstrap_128(s, g, C.byref(buf))
 
 
 def _f128_planes(polynomial_size, number_of_samples, streams):

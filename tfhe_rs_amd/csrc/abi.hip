@@ -5,6 +5,7 @@
 #include "arena.h"
 #include "profile.h"
 #include "pbs128.h"
+#include "pbs128_multibit.h"
 #include "ranges.h"
 #include "scratch.h"
 
@@ -130,10 +131,11 @@ PbsArgs make_args(void *lwe_array_out, void const *lwe_output_indexes, void cons
 // Goldilocks kernel's operand), made next to the split form by hip_convert_lwe_programmable_bootstrap_key_ntt64_split_async
 // and kept by the library for as long as the split key's device memory is neither dropped nor overwritten
 RangeRegistry<void *> g_split_twins;
-// What hip_convert_lwe_programmable_bootstrap_key_128_async wrote where: a bootstrap whose key pointer is a converted
-// key of other sizes is refused.
+// What hip_convert_lwe_programmable_bootstrap_key_128_async and its multi-bit companion wrote where: a bootstrap whose
+// key pointer is a converted key of other sizes, or of the other kind, is refused.  g: the grouping factor, 0 for a
+// classic key.
 struct Key128Sizes {
-  uint32_t n, glwe_dim, level, N;
+  uint32_t n, glwe_dim, level, N, g;
 };
 RangeRegistry<Key128Sizes> g_key128;
 // device memory [p, p + bytes) is about to be freed or written: what the library derived from it goes
@@ -1183,7 +1185,7 @@ void hip_convert_lwe_programmable_bootstrap_key_128_async(void *stream, uint32_t
     launch_fft128_forward(S(stream), polynomial_size, (double *)dest, nullptr, nullptr, nullptr, (const u128 *)staged, polys,
                           get_fft128_tables(gpu_index, polynomial_size), 0, 1);
   });
-  g_key128.add((int)gpu_index, dest, bytes, Key128Sizes{input_lwe_dim, glwe_dim, level_count, polynomial_size});
+  g_key128.add((int)gpu_index, dest, bytes, Key128Sizes{input_lwe_dim, glwe_dim, level_count, polynomial_size, 0});
 }
 uint64_t hip_scratch_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, int8_t **buffer,
                                                       uint32_t lwe_dimension, uint32_t glwe_dimension,
@@ -1228,11 +1230,14 @@ void hip_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void
   HX_PANIC_IF_FALSE(base_log >= 1 && base_log <= 64 && (uint64_t)base_log * level_count <= 128,
                     "invalid decomposition (base_log=%u, level=%u)", base_log, level_count);
   Key128Sizes rec;
-  if (g_key128.find((int)gpu_index, bootstrapping_key, &rec))
+  if (g_key128.find((int)gpu_index, bootstrapping_key, &rec)) {
+    HX_PANIC_IF_FALSE(rec.g == 0, "the bootstrap key is a multi-bit 128-bit key (grouping_factor=%u): it belongs to "
+                                  "hip_multi_bit_programmable_bootstrap_128_async", rec.g);
     HX_PANIC_IF_FALSE(rec.n == lwe_dimension && rec.glwe_dim == glwe_dimension && rec.level == level_count &&
                           rec.N == polynomial_size,
                       "the bootstrap key was converted for other sizes (n=%u, k=%u, level=%u, N=%u)", rec.n, rec.glwe_dim,
                       rec.level, rec.N);
+  }
   if (num_samples == 0) return;
   HX_PANIC_IF_FALSE(lwe_array_out != nullptr && lut_vector != nullptr && lwe_array_in != nullptr && bootstrapping_key != nullptr,
                     "128-bit PBS: null pointer");
@@ -1251,6 +1256,164 @@ void hip_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void
 }
 void hip_cleanup_programmable_bootstrap_128(void *stream, uint32_t gpu_index, int8_t **pbs_buffer) {
   scratch_destroy<Pbs128Buffer>(gpu_index, S(stream), pbs_buffer, "cleanup of a foreign 128-bit PBS buffer", "");
+}
+// =========================================================================== multi-bit 128-bit PBS (pbs128_multibit.h)
+// The reference's *_multi_bit_*_128 entry points under hip_ names, parameter lists unchanged
+// (cuda/include/pbs/programmable_bootstrap_multibit.h:18-21,64-80).
+struct Pbs128MultiBitBuffer : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x4D423238;  // "MB28"
+  uint32_t glwe_dimension = 0, polynomial_size = 0, level_count = 0, max_samples = 0;
+  uint32_t chunk = 1;  // groups per (key-bundle, accumulate) pass
+  Fft128Tables fft{};
+  double *bundle = nullptr;  // the key bundles of one chunk
+  u128 *acc = nullptr;       // ACC per sample between chunks
+  void release() {
+    for (void *d : {(void *)bundle, (void *)acc})
+      if (d) scratch_free(d);
+  }
+};
+std::atomic<uint32_t> g_pbs128_multibit_chunk{0};  // test hook: groups per pass (0 = what kPbs128MbBundleBytes holds)
+void hip_backend_set_pbs128_multibit_chunk(uint32_t groups) { g_pbs128_multibit_chunk.store(groups); }
+
+static void check_multi_bit_128_shape(uint32_t lwe_dimension, uint32_t grouping_factor) {
+  HX_PANIC_IF_FALSE(grouping_factor >= 2 && grouping_factor <= 4 && lwe_dimension >= grouping_factor &&
+                        lwe_dimension % grouping_factor == 0,
+                    "unsupported grouping_factor %u for lwe_dimension %u (multi-bit 128-bit PBS: 2..4, dividing it)",
+                    grouping_factor, lwe_dimension);
+}
+static size_t multi_bit_128_key_bytes(uint32_t input_lwe_dim, uint32_t glwe_dim, uint32_t level_count, uint32_t polynomial_size,
+                                      uint32_t grouping_factor) {
+  return (size_t)(input_lwe_dim / grouping_factor) * ((size_t)1 << grouping_factor) * pbs128_mb_polys(glwe_dim, level_count) *
+         polynomial_size * sizeof(u128);
+}
+void hip_convert_lwe_multi_bit_programmable_bootstrap_key_128_async(void *stream, uint32_t gpu_index, void *dest,
+                                                                    void const *src, uint32_t input_lwe_dim,
+                                                                    uint32_t glwe_dim, uint32_t level_count,
+                                                                    uint32_t polynomial_size, uint32_t grouping_factor) {
+  set_device(gpu_index);
+  pbs128_check_poly(polynomial_size);
+  check_multi_bit_128_shape(input_lwe_dim, grouping_factor);
+  // the key stays in the standard domain: the bundles are summed exactly before anything is transformed
+  const size_t bytes = multi_bit_128_key_bytes(input_lwe_dim, glwe_dim, level_count, polynomial_size, grouping_factor);
+  convert_staged_key(stream, gpu_index, dest, bytes, src, bytes, "multi-bit bootstrap key conversion", [&](const void *staged) {
+    HX_CHECK(hipMemcpyAsync(dest, staged, bytes, hipMemcpyDeviceToDevice, S(stream)));
+  });
+  g_key128.add((int)gpu_index, dest, bytes, Key128Sizes{input_lwe_dim, glwe_dim, level_count, polynomial_size, grouping_factor});
+}
+uint64_t hip_scratch_multi_bit_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, int8_t **buffer,
+                                                                uint32_t glwe_dimension, uint32_t polynomial_size,
+                                                                uint32_t level_count, uint32_t input_lwe_ciphertext_count,
+                                                                bool allocate_gpu_memory) {
+  (void)stream;
+  set_device(gpu_index);
+  pbs128_check_poly(polynomial_size);
+  HX_PANIC_IF_FALSE(pbs128_mb_dispatch(nullptr, polynomial_size, glwe_dimension, nullptr, nullptr),
+                    "unsupported (polynomial_size=%u, glwe_dimension=%u) for the 128-bit PBS", polynomial_size, glwe_dimension);
+  HX_PANIC_IF_FALSE(level_count >= 1 && level_count <= 128, "invalid decomposition (level=%u)", level_count);
+  auto *b = new Pbs128MultiBitBuffer();
+  b->glwe_dimension = glwe_dimension;
+  b->polynomial_size = polynomial_size;
+  b->level_count = level_count;
+  b->max_samples = input_lwe_ciphertext_count;
+  const uint64_t samples = input_lwe_ciphertext_count ? input_lwe_ciphertext_count : 1;
+  const uint64_t per_group = samples * pbs128_mb_polys(glwe_dimension, level_count) * 16 * polynomial_size;
+  uint64_t chunk = g_pbs128_multibit_chunk.load();
+  if (chunk == 0) chunk = kPbs128MbBundleBytes / per_group;
+  b->chunk = (uint32_t)(chunk < 1 ? 1 : chunk > kPbs128MbMaxChunk ? kPbs128MbMaxChunk : chunk);
+  const uint64_t bundle_bytes = b->chunk * per_group;
+  const uint64_t acc_bytes = samples * (glwe_dimension + 1) * polynomial_size * sizeof(u128);
+  if (allocate_gpu_memory) {
+    b->fft = get_fft128_tables(gpu_index, polynomial_size);  // built here, so that the launch stays capture-safe
+    b->bundle = (double *)scratch_alloc(bundle_bytes);
+    b->acc = (u128 *)scratch_alloc(acc_bytes);
+  }
+  scratch_hand_out(b, allocate_gpu_memory, buffer);
+  return bundle_bytes + acc_bytes;
+}
+// scratch, decomposition, shape and key of a multi-bit 128-bit launch (the bootstrap and the key-bundle test hook)
+static Pbs128MultiBitBuffer *checked_multi_bit_128(uint32_t gpu_index, int8_t *mem_ptr, void const *bootstrapping_key,
+                                                   uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+                                                   uint32_t grouping_factor, uint32_t base_log, uint32_t level_count,
+                                                   uint32_t num_samples) {
+  auto *b = scratch_use<Pbs128MultiBitBuffer>(mem_ptr, "multi-bit PBS buffer",
+                                              " was not created by hip_scratch_multi_bit_programmable_bootstrap_128_async");
+  HX_PANIC_IF_FALSE(b->glwe_dimension == glwe_dimension && b->polynomial_size == polynomial_size && b->level_count == level_count,
+                    "multi-bit PBS buffer parameters do not match the call");
+  HX_PANIC_IF_FALSE(num_samples <= b->max_samples, "num_samples %u exceeds the scratch capacity %u", num_samples, b->max_samples);
+  HX_PANIC_IF_FALSE(base_log >= 1 && base_log <= 64 && (uint64_t)base_log * level_count <= 128,
+                    "invalid decomposition (base_log=%u, level=%u)", base_log, level_count);
+  check_multi_bit_128_shape(lwe_dimension, grouping_factor);
+  Key128Sizes rec;
+  if (g_key128.find((int)gpu_index, bootstrapping_key, &rec)) {
+    HX_PANIC_IF_FALSE(rec.g != 0, "the bootstrap key is a classic 128-bit key: it belongs to hip_programmable_bootstrap_128_async");
+    HX_PANIC_IF_FALSE(rec.n == lwe_dimension && rec.glwe_dim == glwe_dimension && rec.level == level_count &&
+                          rec.N == polynomial_size && rec.g == grouping_factor,
+                      "the multi-bit bootstrap key was converted for other sizes (n=%u, k=%u, level=%u, N=%u, g=%u)", rec.n,
+                      rec.glwe_dim, rec.level, rec.N, rec.g);
+  }
+  return b;
+}
+void hip_multi_bit_programmable_bootstrap_128_async(void *stream, uint32_t gpu_index, void *lwe_array_out,
+                                                    void const *lwe_output_indexes, void const *lut_vector,
+                                                    void const *lwe_array_in, void const *lwe_input_indexes,
+                                                    void const *bootstrapping_key, int8_t *mem_ptr, uint32_t lwe_dimension,
+                                                    uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t grouping_factor,
+                                                    uint32_t base_log, uint32_t level_count, uint32_t num_samples,
+                                                    uint32_t num_many_lut, uint32_t lut_stride) {
+  (void)lut_stride;
+  set_device(gpu_index);
+  HX_PANIC_IF_FALSE(num_many_lut == 1, "multi-bit 128-bit PBS: num_many_lut = %u is not supported (one table per call)",
+                    num_many_lut);
+  auto *b = checked_multi_bit_128(gpu_index, mem_ptr, bootstrapping_key, lwe_dimension, glwe_dimension, polynomial_size,
+                                  grouping_factor, base_log, level_count, num_samples);
+  if (num_samples == 0) return;
+  HX_PANIC_IF_FALSE(lwe_array_out != nullptr && lwe_output_indexes != nullptr && lut_vector != nullptr && lwe_array_in != nullptr &&
+                        lwe_input_indexes != nullptr && bootstrapping_key != nullptr,
+                    "multi-bit 128-bit PBS: null pointer");
+  Pbs128MbArgs a{};
+  a.lwe_out = (u128 *)lwe_array_out;
+  a.out_idx = (const uint64_t *)lwe_output_indexes;
+  a.lut = (const u128 *)lut_vector;
+  a.lwe_in = (const uint64_t *)lwe_array_in;
+  a.in_idx = (const uint64_t *)lwe_input_indexes;
+  a.bsk = (const u128 *)bootstrapping_key;
+  a.bundle = b->bundle;
+  a.acc_buf = b->acc;
+  a.n = lwe_dimension;
+  a.g = grouping_factor;
+  a.base_log = base_log;
+  a.level = level_count;
+  a.num_samples = num_samples;
+  launch_pbs128_multibit(S(stream), polynomial_size, glwe_dimension, a, b->chunk, b->fft);
+}
+void hip_cleanup_multi_bit_programmable_bootstrap_128(void *stream, const uint32_t gpu_index, int8_t **buffer) {
+  scratch_destroy<Pbs128MultiBitBuffer>(gpu_index, S(stream), buffer, "cleanup of a foreign multi-bit 128-bit PBS buffer", "");
+}
+// test hook: the Fourier-domain key bundle of ONE group for the LWE lwe_input_indexes[0] of lwe_array_in, (k + 1)^2 level
+// polynomials of four planes of N / 2 doubles in bundle_out (the layout the accumulate kernel reads)
+void hip_test_pbs128_multibit_keybundle_async(void *stream, uint32_t gpu_index, void *bundle_out, void const *bootstrapping_key,
+                                              void const *lwe_array_in, void const *lwe_input_indexes, uint32_t lwe_dimension,
+                                              uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t level_count,
+                                              uint32_t grouping_factor, uint32_t group) {
+  set_device(gpu_index);
+  pbs128_check_poly(polynomial_size);
+  check_multi_bit_128_shape(lwe_dimension, grouping_factor);
+  HX_PANIC_IF_FALSE(group < lwe_dimension / grouping_factor, "key-bundle hook: group %u of %u", group,
+                    lwe_dimension / grouping_factor);
+  HX_PANIC_IF_FALSE(bundle_out != nullptr && bootstrapping_key != nullptr && lwe_array_in != nullptr && lwe_input_indexes != nullptr,
+                    "key-bundle hook: null pointer");
+  Pbs128MbArgs a{};
+  a.lwe_in = (const uint64_t *)lwe_array_in;
+  a.in_idx = (const uint64_t *)lwe_input_indexes;
+  a.bsk = (const u128 *)bootstrapping_key;
+  a.bundle = (double *)bundle_out;
+  a.n = lwe_dimension;
+  a.g = grouping_factor;
+  a.level = level_count;
+  a.num_samples = 1;
+  a.group0 = group;
+  a.groups = 1;
+  launch_pbs128_mb_keybundle(S(stream), polynomial_size, glwe_dimension, a, get_fft128_tables(gpu_index, polynomial_size));
 }
 void hip_fourier_transform_forward_as_torus_f128_async(void *stream, uint32_t gpu_index, void *re0, void *re1, void *im0,
                                                        void *im1, void const *standard, uint32_t const N,

@@ -1605,8 +1605,10 @@ struct NoiseSquashMem : ScratchHeader {
   uint64_t *d_packed = nullptr, *d_after_ks = nullptr, *d_trivial = nullptr, *d_lo = nullptr, *d_hi = nullptr;
   unsigned __int128 *d_lut = nullptr;
   int8_t *pbs_buf = nullptr;
+  uint32_t grouping = 0;  // the kind: 0 a classic 128-bit key, otherwise the grouping factor of a multi-bit one
   void release(const CudaStreamsFFI &s) {
-    if (pbs_buf) hip_cleanup_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
+    if (pbs_buf && grouping) hip_cleanup_multi_bit_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
+    else if (pbs_buf) hip_cleanup_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
     for (void *d : {(void *)d_packed, (void *)d_after_ks, (void *)d_trivial, (void *)d_lo, (void *)d_hi, (void *)d_lut})
       if (d) scratch_free(d);
   }
@@ -2769,12 +2771,13 @@ void hip_integer_extract_glwe_64_async(CudaStreamsFFI streams, void *glwe_out, v
 // ---- noise squashing (integer.cuh:2776-2840; tfhe/src/integer/gpu/noise_squashing).  lwe_dimension: the small key's;
 // glwe_dimension x polynomial_size: the squashing key's output ring; input_*: the compute set's ring (the big key the
 // blocks are under).  num_radix_blocks: blocks of the OUTPUT (ceil(num_original_blocks / 2)).  One GPU.
-uint64_t hip_scratch_integer_apply_noise_squashing_64_async(
+// grouping_factor 0: the classic 128-bit bootstrap; otherwise the multi-bit one
+static uint64_t scratch_noise_squashing(
     CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
     uint32_t input_glwe_dimension, uint32_t input_polynomial_size, uint32_t ks_level, uint32_t ks_base_log,
     uint32_t pbs_level, uint32_t pbs_base_log, uint32_t num_radix_blocks, uint32_t num_original_blocks,
     uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
-    enum PBS_MS_REDUCTION_T noise_reduction_type) {
+    enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t grouping_factor) {
   HX_PANIC_IF_FALSE(num_radix_blocks == (num_original_blocks + 1) / 2,
                     "apply_noise_squashing: num output radix blocks (%u) should be half ceil the number input radix blocks (%u)",
                     num_radix_blocks, num_original_blocks);
@@ -2791,6 +2794,7 @@ uint64_t hip_scratch_integer_apply_noise_squashing_64_async(
     m.msg = message_modulus, m.carry = carry_modulus;
     m.cap_in = std::max(1u, num_original_blocks), m.cap_out = std::max(1u, num_radix_blocks);
     m.gpu = G0(streams);
+    m.grouping = grouping_factor;
     radix_alloc((void **)&m.d_packed, (size_t)m.cap_out * (m.big_n + 1) * sizeof(uint64_t));
     radix_alloc((void **)&m.d_after_ks, (size_t)m.cap_out * (m.small_n + 1) * sizeof(uint64_t));
     std::vector<uint64_t> triv(m.cap_out), lo(m.cap_out), hi(m.cap_out);
@@ -2808,9 +2812,41 @@ uint64_t hip_scratch_integer_apply_noise_squashing_64_async(
     for (uint32_t i = 0; i < half; ++i) body[i] = (unsigned __int128)0 - body[i];
     std::rotate(body, body + half, body + m.N);
     m.d_lut = dev_upload(st, lut);
-    t_bytes += hip_scratch_programmable_bootstrap_128_async(st, m.gpu, &m.pbs_buf, m.small_n, m.k, m.N, m.pbs_level, m.cap_out,
-                                                            !t_dry, noise_reduction_type);
+    if (m.grouping)
+      t_bytes += hip_scratch_multi_bit_programmable_bootstrap_128_async(st, m.gpu, &m.pbs_buf, m.k, m.N, m.pbs_level, m.cap_out,
+                                                                        !t_dry);
+    else
+      t_bytes += hip_scratch_programmable_bootstrap_128_async(st, m.gpu, &m.pbs_buf, m.small_n, m.k, m.N, m.pbs_level, m.cap_out,
+                                                              !t_dry, noise_reduction_type);
   });
+}
+uint64_t hip_scratch_integer_apply_noise_squashing_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+    uint32_t input_glwe_dimension, uint32_t input_polynomial_size, uint32_t ks_level, uint32_t ks_base_log,
+    uint32_t pbs_level, uint32_t pbs_base_log, uint32_t num_radix_blocks, uint32_t num_original_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  return scratch_noise_squashing(streams, mem_ptr, lwe_dimension, glwe_dimension, polynomial_size, input_glwe_dimension,
+                                 input_polynomial_size, ks_level, ks_base_log, pbs_level, pbs_base_log, num_radix_blocks,
+                                 num_original_blocks, message_modulus, carry_modulus, allocate_gpu_memory, noise_reduction_type, 0);
+}
+// the squashing key is a multi-bit 128-bit key; the plain modulus switch is the only one multi-bit has
+uint64_t hip_scratch_integer_apply_noise_squashing_multi_bit_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size,
+    uint32_t input_glwe_dimension, uint32_t input_polynomial_size, uint32_t ks_level, uint32_t ks_base_log,
+    uint32_t pbs_level, uint32_t pbs_base_log, uint32_t num_radix_blocks, uint32_t num_original_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t grouping_factor) {
+  HX_PANIC_IF_FALSE((uint32_t)noise_reduction_type == 0,
+                    "apply_noise_squashing: the multi-bit bootstrap has no noise_reduction_type %u (plain modulus switch only)",
+                    (uint32_t)noise_reduction_type);
+  HX_PANIC_IF_FALSE(grouping_factor >= 2 && grouping_factor <= 4 && lwe_dimension >= grouping_factor &&
+                        lwe_dimension % grouping_factor == 0,
+                    "apply_noise_squashing: unsupported grouping_factor %u for lwe_dimension %u", grouping_factor, lwe_dimension);
+  return scratch_noise_squashing(streams, mem_ptr, lwe_dimension, glwe_dimension, polynomial_size, input_glwe_dimension,
+                                 input_polynomial_size, ks_level, ks_base_log, pbs_level, pbs_base_log, num_radix_blocks,
+                                 num_original_blocks, message_modulus, carry_modulus, allocate_gpu_memory, noise_reduction_type,
+                                 grouping_factor);
 }
 
 void hip_integer_apply_noise_squashing_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out,
@@ -2839,8 +2875,13 @@ void hip_integer_apply_noise_squashing_64_async(CudaStreamsFFI streams, CudaRadi
   if (n_in & 1) axpy(st, m->d_packed + (size_t)pairs * words, nullptr, in + (size_t)(n_in - 1) * words, nullptr, 1, nullptr, nullptr, words, 1);
   launch_keyswitch(st, m->d_after_ks, m->d_trivial, m->d_packed, m->d_trivial, (const uint64_t *)ksks[0], m->big_n, m->small_n,
                    m->ks_base_log, m->ks_level, n_out);
-  hip_programmable_bootstrap_128_async(st, m->gpu, lwe_array_out->ptr, m->d_lut, m->d_after_ks, bsks[0], m->pbs_buf, m->small_n,
-                                       m->k, m->N, m->pbs_base_log, m->pbs_level, n_out);
+  if (m->grouping)
+    hip_multi_bit_programmable_bootstrap_128_async(st, m->gpu, lwe_array_out->ptr, m->d_trivial, m->d_lut, m->d_after_ks,
+                                                   m->d_trivial, bsks[0], m->pbs_buf, m->small_n, m->k, m->N, m->grouping,
+                                                   m->pbs_base_log, m->pbs_level, n_out, 1, 0);
+  else
+    hip_programmable_bootstrap_128_async(st, m->gpu, lwe_array_out->ptr, m->d_lut, m->d_after_ks, bsks[0], m->pbs_buf, m->small_n,
+                                         m->k, m->N, m->pbs_base_log, m->pbs_level, n_out);
   set_block_info(lwe_array_out, 0, n_out, (uint64_t)m->msg * m->msg - 1, 1);
 }
 

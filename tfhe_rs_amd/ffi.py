@@ -228,6 +228,15 @@ SIGNATURES = {
         (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _b, _u32]),
     "hip_integer_apply_noise_squashing_64_async": (None, [_S, _R, _R, _v, _i8pp, _i8pp]),
     "hip_cleanup_integer_apply_noise_squashing_64": (None, [_S, _i8pp]),
+    "hip_convert_lwe_multi_bit_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32, _u32]),
+    "hip_scratch_multi_bit_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _b]),
+    "hip_multi_bit_programmable_bootstrap_128_async":
+        (None, [_v, _u32, _v, _v, _v, _v, _v, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "hip_cleanup_multi_bit_programmable_bootstrap_128": (None, [_v, _u32, _i8pp]),
+    "hip_scratch_integer_apply_noise_squashing_multi_bit_64_async":
+        (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _b, _u32, _u32]),
+    "hip_backend_set_pbs128_multibit_chunk": (None, [_u32]),
+    "hip_test_pbs128_multibit_keybundle_async": (None, [_v, _u32, _v, _v, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32]),
     "hip_test_fft128_tables_host": (None, [_u32, _v, _v, _v]),
     "hip_test_decompose_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32]),
     "hip_test_f128_cmul_async": (None, [_v, _u32, _v, _v, _v, _u32]),

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import ffi
-from .core_crypto_gpu import CudaLweBootstrapKey, CudaLweKeyswitchKey, CudaVec, _lib
+from .core_crypto_gpu import CudaLweBootstrapKey, CudaLweKeyswitchKey, CudaLweMultiBitBootstrapKey128, CudaVec, _lib
 
 U64 = np.uint64
 PBS_TYPE_MULTI_BIT, PBS_TYPE_CLASSICAL = 0, 1          # pbs/pbs_enums.h:4
@@ -609,8 +609,8 @@ class CudaSquashedNoiseRadixCiphertext:
 
 
 class CudaNoiseSquashingKey:
-    """keys.rs: the u128 bootstrap key (a CudaLweBootstrapKey128 from the compute set's small key to the squashing GLWE
-    key) and the moduli of the blocks it squashes."""
+    """keys.rs: the u128 bootstrap key (a CudaLweBootstrapKey128 or a CudaLweMultiBitBootstrapKey128 from the compute set's
+    small key to the squashing GLWE key) and the moduli of the blocks it squashes."""
 
     def __init__(self, bootstrapping_key, message_modulus, carry_modulus):
         self.bootstrapping_key = bootstrapping_key
@@ -634,10 +634,13 @@ class CudaNoiseSquashingKey:
         ksks, bsks = (C.c_void_p * 1)(k.d_vec.ptr), (C.c_void_p * 1)(b.d_vec.ptr)
         big = src_server_key.bootstrapping_key
         lib = _lib()
-        lib.hip_scratch_integer_apply_noise_squashing_64_async(
-            s, C.byref(mem), b.input_lwe_dimension, b.glwe_dimension, b.polynomial_size, big.glwe_dimension,
-            big.polynomial_size, k.decomp_level_count, k.decomp_base_log, b.decomp_level_count, b.decomp_base_log, n_out,
-            n_in, self.message_modulus, self.carry_modulus, True, 1 if b.ms_noise_reduction else 0)
+        shape = (s, C.byref(mem), b.input_lwe_dimension, b.glwe_dimension, b.polynomial_size, big.glwe_dimension,
+                 big.polynomial_size, k.decomp_level_count, k.decomp_base_log, b.decomp_level_count, b.decomp_base_log, n_out,
+                 n_in, self.message_modulus, self.carry_modulus, True)
+        if isinstance(b, CudaLweMultiBitBootstrapKey128):   # the scratch remembers its kind: apply and cleanup serve both
+            lib.hip_scratch_integer_apply_noise_squashing_multi_bit_64_async(*shape, 0, b.grouping_factor)
+        else:
+            lib.hip_scratch_integer_apply_noise_squashing_64_async(*shape, 1 if b.ms_noise_reduction else 0)
         lib.hip_integer_apply_noise_squashing_64_async(s, C.byref(out._ffi()), C.byref(ciphertext._ffi()), mem, ksks, bsks)
         lib.hip_cleanup_integer_apply_noise_squashing_64(s, C.byref(mem))
         return out
