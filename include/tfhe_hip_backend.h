@@ -678,6 +678,89 @@ uint64_t hip_integer_compressed_size_words(
     uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
     uint32_t total_blocks);
 
+/* ------------------------------------------------------------------ compression of squashed-noise lists (extensions)
+ * What tfhe/src/shortint/list_compression/noise_squashing_compression.rs computes over Scalar = u128 and the reference's
+ * GPU backend serves with cuda_packing_keyswitch_lwe_list_to_glwe_128_async, cuda_integer_{compress,decompress}_radix_
+ * ciphertext_128_async and cuda_integer_extract_glwe_128_async — here under hip_ names with the argument lists of the
+ * _64 entry points above (the reference-named *_128 symbols remain link stubs).  A u128 word is two u64
+ * words, (lo, hi).  Single GPU: entry 0 of `streams`.
+ *
+ * Packing keyswitch key: [input_lwe_dimension][level_count][(glwe_dimension + 1) * polynomial_size] u128 on the device,
+ * row idx of an input element holding level level_count - idx (a plain memcpy uploads it).  1 <= base_log <= 62,
+ * base_log * level_count <= 128.  Two kernels compute the decomposed products with identical words: a general one on the
+ * vector ALU (any shape) and one on the int8 matrix cores, which needs the key a second time in a byte-plane layout:
+ * hip_lwe_packing_keyswitch_key_128_planes_size_bytes gives that layout's size, or 0 where the matrix-core kernel
+ * declines the shape (input_lwe_dimension * level_count not a multiple of 32, or ceil((base_log + 1) / 8) *
+ * input_lwe_dimension * level_count * 2^14 >= 2^31: an int32 accumulator could overflow);
+ * hip_convert_lwe_packing_keyswitch_key_128_async builds it from the key ON THE DEVICE, once, when the key is uploaded.
+ * Every launch takes both pointers; fp_ksk_planes may be null (then the general kernel runs).
+ * hip_backend_set_pks128_kernel: 0 = automatic, 1 = general kernel, 2 = matrix-core kernel wherever it carries the shape
+ * and the planes are given; hip_backend_last_pks128_path: 0 general, 1 matrix core (tests).
+ * Small batches split K = input_lwe_dimension * level_count over up to 8 partial sums that the epilogue adds (same words):
+ * hip_backend_set_pks128_max_parts caps that count (0 = no cap, 1 = the whole K in one pass: every accumulator of the
+ * matrix-core kernel then runs over all K terms), hip_backend_last_pks128_parts reports what the last call took (tests). */
+void hip_backend_set_pks128_kernel(uint32_t which);
+uint32_t hip_backend_last_pks128_path(void);
+void hip_backend_set_pks128_max_parts(uint32_t parts);
+uint32_t hip_backend_last_pks128_parts(void);
+uint64_t hip_lwe_packing_keyswitch_key_128_planes_size_bytes(
+    uint32_t input_lwe_dimension, uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t base_log,
+    uint32_t level_count);
+void hip_convert_lwe_packing_keyswitch_key_128_async(
+    CudaStreamsFFI streams, void *dest_planes, void const *src_key, uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t base_log, uint32_t level_count);
+/* Core level (core_crypto/algorithms/lwe_packing_keyswitch.rs:102-187, 296-379): every chunk of lwe_per_glwe of the
+ * num_lwes contiguous u128 LWEs of lwe_array_in (the last may be partial) becomes one GLWE  sum_i X^i * G_i  of
+ * glwe_array_out, (glwe_dimension + 1) * polynomial_size u128 words each, not modulus switched.
+ * Panics: lwe_per_glwe > polynomial_size, num_lwes above the scratch's, parameters other than the scratch's, base_log
+ * above 62, base_log * level_count above 128. */
+uint64_t hip_scratch_packing_keyswitch_lwe_list_to_glwe_128_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t base_log, uint32_t level_count, uint32_t num_lwes, bool allocate_gpu_memory);
+void hip_packing_keyswitch_lwe_list_to_glwe_128_async(
+    CudaStreamsFFI streams, void *glwe_array_out, void const *lwe_array_in, void const *fp_ksk,
+    void const *fp_ksk_planes, int8_t *mem_ptr, uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t base_log, uint32_t level_count, uint32_t num_lwes, uint32_t lwe_per_glwe);
+void hip_cleanup_packing_keyswitch_lwe_list_to_glwe_128(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* Compress: the u128 blocks of lwe_array_in (a squashed radix ciphertext; no multiplication by message_modulus) are
+ * packed lwe_per_glwe per GLWE; the first glwe_dimension * polynomial_size + lwe_per_glwe values of every GLWE are
+ * switched to storage_log_modulus = s bits, (x + 2^(127-s)) >> (128-s), the identity at s = 128 (1..128), and bit-packed
+ * least significant first into ceil(values * s / 128) u128 words per GLWE (PackedIntegers,
+ * compressed_modulus_switched_glwe_ciphertext.rs:171-250); the padding bits are zero.  packed_out: device array of
+ * hip_integer_compressed_size_words_128(...) u128 words.  fp_ksks / fp_ksk_planes: one key (and one plane layout, or
+ * null) per stream of the set (entry 0 is used).
+ * Panics: more blocks than the scratch's num_radix_blocks, another input LWE dimension than the key's. */
+uint64_t hip_scratch_integer_compress_radix_ciphertext_128_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t input_lwe_dimension, uint32_t compression_glwe_dimension,
+    uint32_t compression_polynomial_size, uint32_t ks_base_log, uint32_t ks_level, uint32_t num_radix_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
+    bool allocate_gpu_memory);
+void hip_integer_compress_radix_ciphertext_128_async(
+    CudaStreamsFFI streams, void *packed_out, CudaRadixCiphertextFFI const *lwe_array_in, void *const *fp_ksks,
+    void *const *fp_ksk_planes, int8_t *mem_ptr);
+void hip_cleanup_integer_compress_radix_ciphertext_128(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* Decompress: no bootstrap.  For every h_indexes[i] (a HOST array) the u128 LWE of dimension compression_glwe_dimension
+ * * compression_polynomial_size at that position of the packed list is unpacked, scaled back by << (128 - s) and sample
+ * extracted into block i of lwe_array_out.  Panics as the _64 entry point: an index at or above total_lwe_bodies_count,
+ * more indexes than the scratch's or the output's blocks, indexes not non-decreasing in GLWE index. */
+uint64_t hip_scratch_integer_decompress_radix_ciphertext_128_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t compression_glwe_dimension, uint32_t compression_polynomial_size,
+    uint32_t lwe_per_glwe, uint32_t storage_log_modulus, uint32_t num_blocks_to_decompress, uint32_t message_modulus,
+    uint32_t carry_modulus, bool allocate_gpu_memory);
+void hip_integer_decompress_radix_ciphertext_128_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out, void const *packed_in,
+    uint32_t total_lwe_bodies_count, uint32_t const *h_indexes, uint32_t num_indexes, int8_t *mem_ptr);
+void hip_cleanup_integer_decompress_radix_ciphertext_128(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+/* GLWE glwe_index of a packed list as (glwe_dimension + 1) * polynomial_size u128 words; the body coefficients beyond
+ * that GLWE's count are zero. */
+void hip_integer_extract_glwe_128_async(
+    CudaStreamsFFI streams, void *glwe_out, void const *packed_in, uint32_t glwe_index, uint32_t glwe_dimension,
+    uint32_t polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus, uint32_t total_lwe_bodies_count);
+/* pure host helper: u128 words of the packed list of total_blocks blocks */
+uint64_t hip_integer_compressed_size_words_128(
+    uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
+    uint32_t total_blocks);
+
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's
  * cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103 and cuda/include/fft/fft128.h), under hip_ names

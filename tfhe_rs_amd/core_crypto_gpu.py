@@ -302,6 +302,68 @@ def _streams_ffi(streams):
     return ffi.CudaStreamsFFI(ptrs, idx, len(streams)), (ptrs, idx)
 
 
+class CudaLwePackingKeyswitchKey128:
+    """The u128 packing keyswitch key of squashed-noise list compression: [input_lwe_dimension][level]
+    [(glwe_dimension + 1) * polynomial_size] u128 words given as uint64 pairs, on the first GPU of `streams`.  It owns both
+    device layouts: the key as it is (d_vec, the general kernel's) and, where the matrix-core kernel carries the shape, its
+    byte planes (d_planes, else None), converted once here."""
+
+    @classmethod
+    def from_lwe_packing_keyswitch_key(cls, h_pksk, input_key_lwe_dimension, output_glwe_dimension, output_polynomial_size,
+                                       decomp_base_log, decomp_level_count, streams):
+        self = cls()
+        self.input_key_lwe_dimension = int(input_key_lwe_dimension)
+        self.output_glwe_dimension = int(output_glwe_dimension)
+        self.output_polynomial_size = int(output_polynomial_size)
+        self.decomp_base_log = int(decomp_base_log)
+        self.decomp_level_count = int(decomp_level_count)
+        h_pksk = np.ascontiguousarray(h_pksk, dtype=U64)
+        assert h_pksk.shape[-1] == 2 and h_pksk.size == 2 * (
+            self.input_key_lwe_dimension * self.decomp_level_count * (self.output_glwe_dimension + 1) *
+            self.output_polynomial_size), "packing keyswitch key container has the wrong size"
+        self.d_vec = CudaVec.from_cpu_async(h_pksk.reshape(-1, 2), streams, elem_words=2)
+        shape = (self.input_key_lwe_dimension, self.output_glwe_dimension, self.output_polynomial_size,
+                 self.decomp_base_log, self.decomp_level_count)
+        self.d_planes = None
+        planes_bytes = int(_lib().hip_lwe_packing_keyswitch_key_128_planes_size_bytes(*shape))
+        if planes_bytes:
+            s, keep = _streams_ffi(streams)
+            self.d_planes = CudaVec(planes_bytes // 8, streams)
+            _lib().hip_convert_lwe_packing_keyswitch_key_128_async(s, self.d_planes.ptr, self.d_vec.ptr, *shape)
+        return self
+
+    @property
+    def planes_ptr(self):
+        return self.d_planes.ptr if self.d_planes is not None else None
+
+    def size_bytes(self):
+        return 16 * self.d_vec.len
+
+
+def cuda_keyswitch_lwe_ciphertext_list_and_pack_in_glwe_ciphertext_128(pksk, input_lwe_list, output_glwe_list, streams,
+                                                                       lwe_per_glwe=None):
+    """The u128 packing keyswitch: the LWEs of `input_lwe_list` (u128), in chunks of `lwe_per_glwe` (default: all of them
+    in one GLWE), are keyswitched and packed, LWE i of a chunk at X^i, into the u128 GLWEs of `output_glwe_list`."""
+    assert pksk.input_key_lwe_dimension == input_lwe_list.lwe_dimension, (
+        f"Mismatched input LweDimension. LwePackingKeyswitchKey input LweDimension: {pksk.input_key_lwe_dimension}, "
+        f"input LweCiphertext LweDimension {input_lwe_list.lwe_dimension}.")
+    assert (pksk.output_glwe_dimension == output_glwe_list.glwe_dimension and
+            pksk.output_polynomial_size == output_glwe_list.polynomial_size), "Mismatched output GlweSize / PolynomialSize"
+    assert input_lwe_list.d_vec.elem_words == 2 and output_glwe_list.d_vec.elem_words == 2, "u128 ciphertexts expected"
+    n = input_lwe_list.lwe_ciphertext_count
+    per = n if lwe_per_glwe is None else int(lwe_per_glwe)
+    assert output_glwe_list.glwe_ciphertext_count * per >= n, "output GLWE list too short"
+    s, keep = _streams_ffi(streams)
+    mem = C.c_void_p()
+    shape = (pksk.input_key_lwe_dimension, pksk.output_glwe_dimension, pksk.output_polynomial_size, pksk.decomp_base_log,
+             pksk.decomp_level_count)
+    lib = _lib()
+    lib.hip_scratch_packing_keyswitch_lwe_list_to_glwe_128_async(s, C.byref(mem), *shape, n, True)
+    lib.hip_packing_keyswitch_lwe_list_to_glwe_128_async(s, output_glwe_list.d_vec.ptr, input_lwe_list.d_vec.ptr,
+                                                         pksk.d_vec.ptr, pksk.planes_ptr, mem, *shape, n, per)
+    lib.hip_cleanup_packing_keyswitch_lwe_list_to_glwe_128(s, C.byref(mem))
+
+
 def cuda_keyswitch_lwe_ciphertext_list_and_pack_in_glwe_ciphertext(pksk, input_lwe_list, output_glwe_list, streams,
                                                                    lwe_per_glwe=None):
     """gpu/algorithms/lwe_packing_keyswitch.rs: the LWEs of `input_lwe_list`, in chunks of `lwe_per_glwe` (default: all

@@ -17,6 +17,7 @@
 //   * rounds are described by device index arrays (gather / scatter / LUT index per block), so no
 //     ciphertext is ever moved to be "aligned" for a round.
 #include "kernels.h"
+#include "pks128.h"
 #include "arena.h"
 #include "profile.h"
 #include "scratch.h"
@@ -2768,6 +2769,249 @@ void hip_integer_extract_glwe_64_async(CudaStreamsFFI streams, void *glwe_out, v
                      glwe_dimension, polynomial_size, bodies, storage_log_modulus);
 }
 
+// ---- compression of squashed-noise (128-bit) ciphertext lists (hip_ names: the reference-named *_128 compression symbols
+// stay link stubs).  shortint/list_compression/noise_squashing_compression.rs; the kernels are pks128_kernels.h.
+namespace {
+struct Pks128Shape {
+  uint32_t n_in = 0, k = 0, N = 0, base_log = 0, level = 0;  // packing key: [n_in][level][(k+1)*N] u128
+  uint32_t ncols() const { return (k + 1) * N; }
+  bool operator==(const Pks128Shape &o) const {
+    return n_in == o.n_in && k == o.k && N == o.N && base_log == o.base_log && level == o.level;
+  }
+  // the shapes the kernels of pks128_kernels.h are written for; anything else is refused here
+  static Pks128Shape checked(uint32_t n_in, uint32_t k, uint32_t N, uint32_t base_log, uint32_t level, const char *who) {
+    check_compression_glwe(k, N, who);
+    HX_PANIC_IF_FALSE(n_in >= 1 && base_log >= 1 && level >= 1,
+                      "%s: unsupported packing key (input dimension %u, base_log %u, level %u)", who, n_in, base_log, level);
+    HX_PANIC_IF_FALSE(base_log <= 62, "%s: base_log %u above 62: a digit must fit a signed 64-bit value", who, base_log);
+    HX_PANIC_IF_FALSE((uint64_t)base_log * level <= 128, "%s: base_log %u * level %u exceeds the 128 bits of a word", who,
+                      base_log, level);
+    Pks128Shape sh;
+    sh.n_in = n_in, sh.k = k, sh.N = N, sh.base_log = base_log, sh.level = level;
+    return sh;
+  }
+};
+void check_storage128(uint32_t N, uint32_t lwe_per_glwe, uint32_t bits, const char *who) {
+  HX_PANIC_IF_FALSE(lwe_per_glwe >= 1 && lwe_per_glwe <= N,
+                    "%s: cannot pack more than polynomial_size (%u) LWEs per GLWE, %u requested", who, N, lwe_per_glwe);
+  HX_PANIC_IF_FALSE(bits >= 1 && bits <= 128, "%s: storage_log_modulus %u must be in 1..128", who, bits);
+}
+
+// core level: u128 LWE list -> unswitched u128 GLWEs
+struct PackingKs128Mem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x504B3132;  // "PK12"
+  Pks128Shape sh;
+  uint32_t cap = 0;  // LWEs per call
+  Pks128Workspace ws;
+  void init(const Pks128Shape &shape, uint32_t capacity) {
+    sh = shape;
+    cap = std::max(1u, capacity);
+    radix_alloc((void **)&ws.rows, pks128_rows_bytes(cap, sh.n_in, sh.ncols(), sh.base_log, sh.level));
+    if (const uint64_t bytes = pks128_digits_bytes(cap, sh.n_in, sh.base_log, sh.level)) {
+      radix_alloc(&ws.digits, bytes);
+      radix_alloc((void **)&ws.digit_sums, (size_t)cap * 16);
+    }
+  }
+  void release(const CudaStreamsFFI &) {
+    for (void *d : {(void *)ws.rows, ws.digits, (void *)ws.digit_sums})
+      if (d) scratch_free(d);
+  }
+};
+struct Compress128Mem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x434D3132;  // "CM12"
+  PackingKs128Mem pks;  // member: no header of its own in use
+  uint32_t msg = 0, carry = 0, lwe_per_glwe = 0, bits = 0;
+  void release(const CudaStreamsFFI &s) { pks.release(s); }
+};
+struct Decompress128Mem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x44433132;  // "DC12"
+  uint32_t kc = 0, Nc = 0, lwe_per_glwe = 0, bits = 0, cap = 0, msg = 0, carry = 0;
+  uint32_t *d_indexes = nullptr, *h_indexes = nullptr;  // h_indexes: pinned staging of the caller's host array
+  hipEvent_t uploaded = nullptr;                         // behind the last copy out of h_indexes
+  void release(const CudaStreamsFFI &) {
+    if (d_indexes) scratch_free(d_indexes);
+    if (h_indexes) HX_CHECK(hipHostFree(h_indexes));
+    if (uploaded) HX_CHECK(hipEventDestroy(uploaded));
+  }
+};
+}  // namespace
+
+void hip_backend_set_pks128_kernel(uint32_t which) { pks128_set_kernel(which); }
+uint32_t hip_backend_last_pks128_path(void) { return pks128_last_path(); }
+void hip_backend_set_pks128_max_parts(uint32_t parts) { pks128_set_max_parts(parts); }
+uint32_t hip_backend_last_pks128_parts(void) { return pks128_last_parts(); }
+
+uint64_t hip_integer_compressed_size_words_128(uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe,
+                                               uint32_t storage_log_modulus, uint32_t total_blocks) {
+  check_compression_glwe(glwe_dimension, polynomial_size, "compressed_size_words_128");
+  check_storage128(polynomial_size, lwe_per_glwe, storage_log_modulus, "compressed_size_words_128");
+  const uint64_t glwes = ((uint64_t)total_blocks + lwe_per_glwe - 1) / lwe_per_glwe;
+  return glwes * pks128_words_per_glwe(glwe_dimension, polynomial_size, lwe_per_glwe, storage_log_modulus);
+}
+
+uint64_t hip_lwe_packing_keyswitch_key_128_planes_size_bytes(uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+                                                             uint32_t polynomial_size, uint32_t base_log,
+                                                             uint32_t level_count) {
+  const Pks128Shape sh = Pks128Shape::checked(input_lwe_dimension, glwe_dimension, polynomial_size, base_log, level_count,
+                                      "packing_keyswitch_key_128_planes_size");
+  return pks128_planes_bytes(sh.n_in, sh.ncols(), sh.base_log, sh.level);
+}
+
+void hip_convert_lwe_packing_keyswitch_key_128_async(CudaStreamsFFI streams, void *dest_planes, void const *src_key,
+                                                     uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+                                                     uint32_t polynomial_size, uint32_t base_log, uint32_t level_count) {
+  first_gpu(streams);
+  const Pks128Shape sh = Pks128Shape::checked(input_lwe_dimension, glwe_dimension, polynomial_size, base_log, level_count,
+                                      "convert_packing_keyswitch_key_128");
+  HX_PANIC_IF_FALSE(dest_planes && src_key, "convert_packing_keyswitch_key_128: null pointer");
+  HX_PANIC_IF_FALSE(pks128_planes_bytes(sh.n_in, sh.ncols(), sh.base_log, sh.level) != 0,
+                    "convert_packing_keyswitch_key_128: the matrix-core kernel does not carry this shape (the planes size is 0)");
+  launch_pks128_convert_key(S0(streams), dest_planes, (const uint64_t *)src_key, sh.n_in, sh.ncols(), sh.level);
+}
+
+uint64_t hip_scratch_packing_keyswitch_lwe_list_to_glwe_128_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                                                  uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+                                                                  uint32_t polynomial_size, uint32_t base_log,
+                                                                  uint32_t level_count, uint32_t num_lwes,
+                                                                  bool allocate_gpu_memory) {
+  const Pks128Shape sh = Pks128Shape::checked(input_lwe_dimension, glwe_dimension, polynomial_size, base_log, level_count,
+                                      "packing_keyswitch_128");
+  return scratch_create<PackingKs128Mem>(streams, mem_ptr, allocate_gpu_memory, "packing_keyswitch_128",
+                                         [&](PackingKs128Mem &m) { m.init(sh, num_lwes); });
+}
+
+void hip_packing_keyswitch_lwe_list_to_glwe_128_async(CudaStreamsFFI streams, void *glwe_array_out, void const *lwe_array_in,
+                                                      void const *fp_ksk, void const *fp_ksk_planes, int8_t *mem_ptr,
+                                                      uint32_t input_lwe_dimension, uint32_t glwe_dimension,
+                                                      uint32_t polynomial_size, uint32_t base_log, uint32_t level_count,
+                                                      uint32_t num_lwes, uint32_t lwe_per_glwe) {
+  first_gpu(streams);
+  auto *m = scratch_use<PackingKs128Mem>(mem_ptr, "packing_keyswitch_128");
+  HX_PANIC_IF_FALSE(glwe_array_out && lwe_array_in && fp_ksk, "packing_keyswitch_128: null pointer");
+  Pks128Shape given;
+  given.n_in = input_lwe_dimension, given.k = glwe_dimension, given.N = polynomial_size, given.base_log = base_log,
+  given.level = level_count;
+  HX_PANIC_IF_FALSE(m->sh == given, "packing_keyswitch_128: parameters differ from the ones the scratch was created with");
+  HX_PANIC_IF_FALSE(lwe_per_glwe >= 1 && lwe_per_glwe <= polynomial_size,
+                    "packing_keyswitch_128: cannot pack more than polynomial_size (%u) LWEs per GLWE, %u requested",
+                    polynomial_size, lwe_per_glwe);
+  HX_PANIC_IF_FALSE(num_lwes <= m->cap, "packing_keyswitch_128: %u LWEs exceed the scratch capacity %u", num_lwes, m->cap);
+  launch_packing_keyswitch128(S0(streams), (uint64_t *)glwe_array_out, m->ws, (const uint64_t *)lwe_array_in,
+                              (const uint64_t *)fp_ksk, fp_ksk_planes, m->sh.n_in, m->sh.k, m->sh.N, m->sh.base_log,
+                              m->sh.level, num_lwes, lwe_per_glwe, 0);
+}
+
+void hip_cleanup_packing_keyswitch_lwe_list_to_glwe_128(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<PackingKs128Mem>(streams, mem_ptr_void, "cleanup packing_keyswitch_128");
+}
+
+uint64_t hip_scratch_integer_compress_radix_ciphertext_128_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t input_lwe_dimension, uint32_t compression_glwe_dimension,
+    uint32_t compression_polynomial_size, uint32_t ks_base_log, uint32_t ks_level, uint32_t num_radix_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
+    bool allocate_gpu_memory) {
+  const Pks128Shape sh = Pks128Shape::checked(input_lwe_dimension, compression_glwe_dimension, compression_polynomial_size,
+                                      ks_base_log, ks_level, "integer_compress_128");
+  check_storage128(compression_polynomial_size, lwe_per_glwe, storage_log_modulus, "integer_compress_128");
+  return scratch_create<Compress128Mem>(streams, mem_ptr, allocate_gpu_memory, "integer_compress_128", [&](Compress128Mem &m) {
+    m.pks.init(sh, num_radix_blocks);
+    m.msg = message_modulus, m.carry = carry_modulus, m.lwe_per_glwe = lwe_per_glwe, m.bits = storage_log_modulus;
+  });
+}
+
+void hip_integer_compress_radix_ciphertext_128_async(CudaStreamsFFI streams, void *packed_out,
+                                                     CudaRadixCiphertextFFI const *lwe_array_in, void *const *fp_ksks,
+                                                     void *const *fp_ksk_planes, int8_t *mem_ptr) {
+  first_gpu(streams);
+  auto *m = scratch_use<Compress128Mem>(mem_ptr, "integer_compress_128");
+  HX_PANIC_IF_FALSE(packed_out && lwe_array_in && lwe_array_in->ptr && fp_ksks && fp_ksks[0], "integer_compress_128: null pointer");
+  const Pks128Shape &sh = m->pks.sh;
+  HX_PANIC_IF_FALSE(lwe_array_in->lwe_dimension == sh.n_in,
+                    "integer_compress_128: ciphertexts do not have the lwe dimension of the packing keyswitch key (%u, key %u)",
+                    lwe_array_in->lwe_dimension, sh.n_in);
+  const uint32_t n = lwe_array_in->num_radix_blocks;
+  HX_PANIC_IF_FALSE(n <= m->pks.cap, "integer_compress_128: %u blocks exceed the scratch capacity %u", n, m->pks.cap);
+  launch_packing_keyswitch128(S0(streams), (uint64_t *)packed_out, m->pks.ws, (const uint64_t *)lwe_array_in->ptr,
+                              (const uint64_t *)fp_ksks[0], fp_ksk_planes ? fp_ksk_planes[0] : nullptr, sh.n_in, sh.k, sh.N,
+                              sh.base_log, sh.level, n, m->lwe_per_glwe, m->bits);
+}
+
+void hip_cleanup_integer_compress_radix_ciphertext_128(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<Compress128Mem>(streams, mem_ptr_void, "cleanup integer_compress_128");
+}
+
+uint64_t hip_scratch_integer_decompress_radix_ciphertext_128_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t compression_glwe_dimension, uint32_t compression_polynomial_size,
+    uint32_t lwe_per_glwe, uint32_t storage_log_modulus, uint32_t num_blocks_to_decompress, uint32_t message_modulus,
+    uint32_t carry_modulus, bool allocate_gpu_memory) {
+  check_compression_glwe(compression_glwe_dimension, compression_polynomial_size, "integer_decompress_128");
+  check_storage128(compression_polynomial_size, lwe_per_glwe, storage_log_modulus, "integer_decompress_128");
+  return scratch_create<Decompress128Mem>(streams, mem_ptr, allocate_gpu_memory, "integer_decompress_128", [&](Decompress128Mem &m) {
+    m.kc = compression_glwe_dimension, m.Nc = compression_polynomial_size;
+    m.lwe_per_glwe = lwe_per_glwe, m.bits = storage_log_modulus;
+    m.msg = message_modulus, m.carry = carry_modulus;
+    m.cap = std::max(1u, num_blocks_to_decompress);
+    radix_alloc((void **)&m.d_indexes, (size_t)m.cap * sizeof(uint32_t));
+    if (!t_dry) {
+      HX_CHECK(hipHostMalloc((void **)&m.h_indexes, (size_t)m.cap * sizeof(uint32_t), 0));
+      HX_CHECK(hipEventCreateWithFlags(&m.uploaded, hipEventDisableTiming));
+    }
+  });
+}
+
+void hip_integer_decompress_radix_ciphertext_128_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array_out,
+                                                       void const *packed_in, uint32_t total_lwe_bodies_count,
+                                                       uint32_t const *h_indexes, uint32_t num_indexes, int8_t *mem_ptr) {
+  first_gpu(streams);
+  auto *m = scratch_use<Decompress128Mem>(mem_ptr, "integer_decompress_128");
+  HX_PANIC_IF_FALSE(lwe_array_out && lwe_array_out->ptr && packed_in && (h_indexes || num_indexes == 0),
+                    "integer_decompress_128: null pointer");
+  HX_PANIC_IF_FALSE(lwe_array_out->lwe_dimension == m->kc * m->Nc,
+                    "integer_decompress_128: output blocks of lwe dimension %u, the compression GLWE extracts to %u",
+                    lwe_array_out->lwe_dimension, m->kc * m->Nc);
+  HX_PANIC_IF_FALSE(num_indexes <= m->cap && num_indexes <= lwe_array_out->num_radix_blocks,
+                    "integer_decompress_128: %u indexes exceed the scratch capacity %u or the output's %u blocks", num_indexes,
+                    m->cap, lwe_array_out->num_radix_blocks);
+  for (uint32_t i = 0; i < num_indexes; ++i) {
+    HX_PANIC_IF_FALSE(h_indexes[i] < total_lwe_bodies_count,
+                      "integer_decompress_128: tried getting index %u for a compressed list with %u elements, out of bound access",
+                      h_indexes[i], total_lwe_bodies_count);
+    HX_PANIC_IF_FALSE(i == 0 || h_indexes[i] / m->lwe_per_glwe >= h_indexes[i - 1] / m->lwe_per_glwe,
+                      "integer_decompress_128: indexes must be non-decreasing in GLWE index (index %u after %u)", h_indexes[i],
+                      h_indexes[i - 1]);
+  }
+  if (num_indexes == 0) return;
+  const hipStream_t st = S0(streams);
+  HX_CHECK(hipEventSynchronize(m->uploaded));  // the previous call's copy out of the staging buffer (no-op before the first)
+  std::copy(h_indexes, h_indexes + num_indexes, m->h_indexes);
+  HX_CHECK(hipMemcpyAsync(m->d_indexes, m->h_indexes, (size_t)num_indexes * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HX_CHECK(hipEventRecord(m->uploaded, st));
+  launch_unpack_extract128(st, (uint64_t *)lwe_array_out->ptr, (const uint64_t *)packed_in, m->d_indexes, num_indexes, m->kc,
+                           m->Nc, m->lwe_per_glwe, m->bits);
+  // a squashed block holds two packed messages: shortint/ciphertext/squashed_noise.rs, degree msg * carry - 1
+  set_block_info(lwe_array_out, 0, num_indexes, (uint64_t)m->msg * m->carry - 1, 1);
+}
+
+void hip_cleanup_integer_decompress_radix_ciphertext_128(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<Decompress128Mem>(streams, mem_ptr_void, "cleanup integer_decompress_128");
+}
+
+void hip_integer_extract_glwe_128_async(CudaStreamsFFI streams, void *glwe_out, void const *packed_in, uint32_t glwe_index,
+                                        uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe,
+                                        uint32_t storage_log_modulus, uint32_t total_lwe_bodies_count) {
+  first_gpu(streams);
+  HX_PANIC_IF_FALSE(glwe_out && packed_in, "integer_extract_glwe_128: null pointer");
+  check_compression_glwe(glwe_dimension, polynomial_size, "integer_extract_glwe_128");
+  check_storage128(polynomial_size, lwe_per_glwe, storage_log_modulus, "integer_extract_glwe_128");
+  HX_PANIC_IF_FALSE((uint64_t)glwe_index * lwe_per_glwe < total_lwe_bodies_count,
+                    "integer_extract_glwe_128: GLWE %u of a compressed list with %u elements, out of bound access", glwe_index,
+                    total_lwe_bodies_count);
+  const uint32_t bodies = std::min(lwe_per_glwe, total_lwe_bodies_count - glwe_index * lwe_per_glwe);
+  const size_t words64 = 2 * (size_t)pks128_words_per_glwe(glwe_dimension, polynomial_size, lwe_per_glwe, storage_log_modulus);
+  launch_unpack_glwe128(S0(streams), (uint64_t *)glwe_out, (const uint64_t *)packed_in + (size_t)glwe_index * words64,
+                        glwe_dimension, polynomial_size, bodies, storage_log_modulus);
+}
+
 // ---- noise squashing (integer.cuh:2776-2840; tfhe/src/integer/gpu/noise_squashing).  lwe_dimension: the small key's;
 // glwe_dimension x polynomial_size: the squashing key's output ring; input_*: the compute set's ring (the big key the
 // blocks are under).  num_radix_blocks: blocks of the OUTPUT (ceil(num_original_blocks / 2)).  One GPU.
@@ -2890,3 +3134,7 @@ void hip_cleanup_integer_apply_noise_squashing_64(CudaStreamsFFI streams, int8_t
 }
 
 }  // extern "C"
+
+// The kernels and launchers of the 128-bit packing keyswitch (declared in pks128.h): a header, as pbs128.h is for abi.hip,
+// because the host emulation build lists its translation units by name.
+#include "pks128_kernels.h"

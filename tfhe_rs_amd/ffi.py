@@ -213,6 +213,27 @@ SIGNATURES = {
     "hip_cleanup_integer_decompress_radix_ciphertext_64": (None, [_S, _i8pp]),
     "hip_integer_extract_glwe_64_async": (None, [_S, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32]),
     "hip_integer_compressed_size_words": (_u64, [_u32, _u32, _u32, _u32, _u32]),
+    # compression of squashed-noise (128-bit) lists
+    "hip_backend_set_pks128_kernel": (None, [_u32]),
+    "hip_backend_last_pks128_path": (_u32, []),
+    "hip_backend_set_pks128_max_parts": (None, [_u32]),
+    "hip_backend_last_pks128_parts": (_u32, []),
+    "hip_lwe_packing_keyswitch_key_128_planes_size_bytes": (_u64, [_u32, _u32, _u32, _u32, _u32]),
+    "hip_convert_lwe_packing_keyswitch_key_128_async": (None, [_S, _v, _v, _u32, _u32, _u32, _u32, _u32]),
+    "hip_scratch_packing_keyswitch_lwe_list_to_glwe_128_async": (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _b]),
+    "hip_packing_keyswitch_lwe_list_to_glwe_128_async":
+        (None, [_S, _v, _v, _v, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "hip_cleanup_packing_keyswitch_lwe_list_to_glwe_128": (None, [_S, _i8pp]),
+    "hip_scratch_integer_compress_radix_ciphertext_128_async":
+        (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _b]),
+    "hip_integer_compress_radix_ciphertext_128_async": (None, [_S, _v, _R, _i8pp, _i8pp, _v]),
+    "hip_cleanup_integer_compress_radix_ciphertext_128": (None, [_S, _i8pp]),
+    "hip_scratch_integer_decompress_radix_ciphertext_128_async":
+        (_u64, [_S, _i8pp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _b]),
+    "hip_integer_decompress_radix_ciphertext_128_async": (None, [_S, _R, _v, _u32, C.POINTER(C.c_uint32), _u32, _v]),
+    "hip_cleanup_integer_decompress_radix_ciphertext_128": (None, [_S, _i8pp]),
+    "hip_integer_extract_glwe_128_async": (None, [_S, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "hip_integer_compressed_size_words_128": (_u64, [_u32, _u32, _u32, _u32, _u32]),
     "hip_integer_scratch_batch": (None, [_u32]),
     "hip_integer_mult_pbs_count": (_u64, [_v]),
     "hip_integer_propagate_pbs_count": (_u64, [_u32]),

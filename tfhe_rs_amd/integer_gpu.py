@@ -648,3 +648,149 @@ class CudaNoiseSquashingKey:
 
 def squash_radix_ciphertext_noise(noise_squashing_key, src_server_key, ciphertext, streams):
     return noise_squashing_key.squash_radix_ciphertext_noise(src_server_key, ciphertext, streams)
+
+
+# ---------------------------------------------------------------------------------------------- squashed-noise list compression
+# integer/gpu/list_compression/server_keys.rs (CudaNoiseSquashingCompressionKey) and
+# integer/gpu/ciphertext/compressed_noise_squashed_ciphertext_list.rs (CudaCompressedSquashedNoiseCiphertextList), over the
+# hip_ entry points of include/tfhe_hip_backend.h, "compression of squashed-noise lists".  Unpacking needs no key and no
+# bootstrap: a sample extract of the packed GLWE.
+STORAGE_LOG_MODULUS_128 = 128   # noise_squashing_compression.rs: the ciphertext modulus itself (the switch is the identity)
+
+
+class CudaNoiseSquashingCompressionKey:
+    """server_keys.rs: the u128 packing keyswitch key (squashing GLWE key, flattened -> compression GLWE key) and how many
+    squashed blocks go into one GLWE."""
+
+    def __init__(self, packing_key_switching_key, lwe_per_glwe, message_modulus, carry_modulus,
+                 storage_log_modulus=STORAGE_LOG_MODULUS_128):
+        self.packing_key_switching_key = packing_key_switching_key
+        self.lwe_per_glwe, self.storage_log_modulus = int(lwe_per_glwe), int(storage_log_modulus)
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+        assert 1 <= self.lwe_per_glwe <= packing_key_switching_key.output_polynomial_size, \
+            "Cannot pack more than polynomial_size elements per glwe"
+
+    def compress_noise_squashed_ciphertexts_into_list(self, ciphertexts, streams):
+        """`ciphertexts`: CudaSquashedNoiseRadixCiphertext (any block counts).  Their blocks are laid end to end, packed
+        lwe_per_glwe per GLWE, switched to storage_log_modulus bits and bit-packed."""
+        k = self.packing_key_switching_key
+        for ct in ciphertexts:
+            assert ct.lwe_dimension == k.input_key_lwe_dimension, \
+                "All ciphertexts do not have the same lwe size as the packing keyswitch key"
+        counts = [ct.num_blocks for ct in ciphertexts]
+        originals = [ct.original_block_count for ct in ciphertexts]
+        total = sum(counts)
+        assert total >= 1, "nothing to compress"
+        w = (k.input_key_lwe_dimension + 1) * 16   # bytes of one u128 block
+        s, keep = CudaServerKey._streams(streams)
+        flat = CudaSquashedNoiseRadixCiphertext(CudaVec(total * (k.input_key_lwe_dimension + 1), streams, elem_words=2),
+                                                total, k.input_key_lwe_dimension, 2 * total)
+        at = 0
+        for ct, c in zip(ciphertexts, counts):
+            _lib().cuda_memcpy_async_gpu_to_gpu(flat.d_blocks.ptr + at * w, ct.d_blocks.ptr, c * w, streams.ptr[0],
+                                                streams.gpu_indexes[0])
+            at += c
+        words = int(_lib().hip_integer_compressed_size_words_128(k.output_glwe_dimension, k.output_polynomial_size,
+                                                                 self.lwe_per_glwe, self.storage_log_modulus, total))
+        packed = CudaVec(words, streams, elem_words=2)
+        mem = C.c_void_p()
+        keys = (C.c_void_p * 1)(k.d_vec.ptr)
+        planes = (C.c_void_p * 1)(k.planes_ptr)
+        _lib().hip_scratch_integer_compress_radix_ciphertext_128_async(
+            s, C.byref(mem), k.input_key_lwe_dimension, k.output_glwe_dimension, k.output_polynomial_size,
+            k.decomp_base_log, k.decomp_level_count, total, self.message_modulus, self.carry_modulus, self.lwe_per_glwe,
+            self.storage_log_modulus, True)
+        _lib().hip_integer_compress_radix_ciphertext_128_async(s, packed.ptr, C.byref(flat._ffi()), keys, planes, mem)
+        _lib().hip_cleanup_integer_compress_radix_ciphertext_128(s, C.byref(mem))
+        return CudaCompressedSquashedNoiseCiphertextList(packed, counts, originals, k.output_glwe_dimension,
+                                                         k.output_polynomial_size, self.lwe_per_glwe,
+                                                         self.storage_log_modulus, self.message_modulus, self.carry_modulus)
+
+
+class CudaCompressedSquashedNoiseCiphertextList:
+    """The packed u128 words on the device plus what unpacking needs: the squashed block count and the original block
+    count of every entry, the compression GLWE shape, lwe_per_glwe, storage_log_modulus and the moduli
+    (CompressedSquashedNoiseCiphertextListMeta)."""
+
+    def __init__(self, d_packed, block_counts, original_block_counts, glwe_dimension, polynomial_size, lwe_per_glwe,
+                 storage_log_modulus, message_modulus, carry_modulus):
+        self.d_packed = d_packed
+        self.block_counts = [int(c) for c in block_counts]
+        self.original_block_counts = [int(c) for c in original_block_counts]
+        self.glwe_dimension, self.polynomial_size = int(glwe_dimension), int(polynomial_size)
+        self.lwe_per_glwe, self.storage_log_modulus = int(lwe_per_glwe), int(storage_log_modulus)
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+
+    class Builder:
+        """compressed_noise_squashed_ciphertext_list.rs builder(): push squashed ciphertexts, then build with a key"""
+
+        def __init__(self):
+            self.ciphertexts = []
+
+        def push(self, ciphertext):
+            assert isinstance(ciphertext, CudaSquashedNoiseRadixCiphertext)
+            self.ciphertexts.append(ciphertext)
+            return self
+
+        def build(self, compression_key, streams):
+            return compression_key.compress_noise_squashed_ciphertexts_into_list(self.ciphertexts, streams)
+
+    @classmethod
+    def builder(cls):
+        return cls.Builder()
+
+    @property
+    def total_blocks(self):
+        return sum(self.block_counts)
+
+    def __len__(self):
+        return len(self.block_counts)
+
+    def unpack_indexes(self, indexes, streams, original_block_count=None):
+        """The squashed blocks at `indexes` (non-decreasing in GLWE index) as one CudaSquashedNoiseRadixCiphertext of LWE
+        dimension glwe_dimension * polynomial_size."""
+        idx = np.ascontiguousarray(indexes, dtype=np.uint32)
+        dim = self.glwe_dimension * self.polynomial_size
+        s, keep = CudaServerKey._streams(streams)
+        out = CudaSquashedNoiseRadixCiphertext(CudaVec(max(idx.size, 1) * (dim + 1), streams, elem_words=2), idx.size, dim,
+                                               2 * idx.size if original_block_count is None else original_block_count)
+        mem = C.c_void_p()
+        _lib().hip_scratch_integer_decompress_radix_ciphertext_128_async(
+            s, C.byref(mem), self.glwe_dimension, self.polynomial_size, self.lwe_per_glwe, self.storage_log_modulus,
+            idx.size, self.message_modulus, self.carry_modulus, True)
+        _lib().hip_integer_decompress_radix_ciphertext_128_async(
+            s, C.byref(out._ffi()), self.d_packed.ptr, self.total_blocks, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+            idx.size, mem)
+        _lib().hip_cleanup_integer_decompress_radix_ciphertext_128(s, C.byref(mem))   # synchronises: idx may go
+        return out
+
+    def get(self, i, streams):
+        """Entry i with its original block count (compressed_noise_squashed_ciphertext_list.rs get)."""
+        if not 0 <= i < len(self):
+            raise IndexError(f"Tried getting index {i} for CudaCompressedSquashedNoiseCiphertextList with {len(self)} elements")
+        start = sum(self.block_counts[:i])
+        return self.unpack_indexes(np.arange(start, start + self.block_counts[i]), streams, self.original_block_counts[i])
+
+    def size_bytes(self):
+        return 16 * self.d_packed.len
+
+    def metadata(self):
+        return {"block_counts": list(self.block_counts), "original_block_counts": list(self.original_block_counts),
+                "glwe_dimension": self.glwe_dimension, "polynomial_size": self.polynomial_size,
+                "lwe_per_glwe": self.lwe_per_glwe, "storage_log_modulus": self.storage_log_modulus,
+                "message_modulus": self.message_modulus, "carry_modulus": self.carry_modulus}
+
+    def to_host(self, streams):
+        """(packed u128 words as [words][2] uint64, metadata dict)"""
+        return self.d_packed.copy_to_cpu(streams), self.metadata()
+
+    @classmethod
+    def from_host(cls, words, metadata, streams):
+        words = np.ascontiguousarray(words, dtype=U64).reshape(-1, 2)
+        m = metadata
+        want = int(_lib().hip_integer_compressed_size_words_128(m["glwe_dimension"], m["polynomial_size"], m["lwe_per_glwe"],
+                                                                m["storage_log_modulus"], sum(m["block_counts"])))
+        assert words.shape[0] == want, "packed words do not have the size the metadata describes"
+        return cls(CudaVec.from_cpu_async(words, streams, elem_words=2), m["block_counts"], m["original_block_counts"],
+                   m["glwe_dimension"], m["polynomial_size"], m["lwe_per_glwe"], m["storage_log_modulus"],
+                   m["message_modulus"], m["carry_modulus"])
