@@ -1,5 +1,5 @@
 //! Enums and `repr(C)` structs of the boundary — field for field those bindgen emits for the reference
-//! (backends/tfhe-cuda-backend/src/bindings.rs: PBS_* at :115-123, CudaLweKeyswitchKeyParamsFFI :129-134,
+//! (backends/tfhe-cuda-backend/src/bindings.rs: PBS_* at :115-123, the integer / keyswitch / zk enums, CudaLweKeyswitchKeyParamsFFI :129-134,
 //! CudaStreamsFFI :330-334, CudaRadixCiphertextFFI :348-355, CudaLweBootstrapKeyParamsFFI :506-515);
 //! C side: include/tfhe_hip_backend.h.
 use crate::ffi;
@@ -14,6 +14,34 @@ pub type PBS_VARIANT = ffi::c_uint;
 pub const PBS_MS_REDUCTION_T_NO_REDUCTION: PBS_MS_REDUCTION_T = 0;
 pub const PBS_MS_REDUCTION_T_CENTERED: PBS_MS_REDUCTION_T = 1;
 pub type PBS_MS_REDUCTION_T = ffi::c_uint;
+pub const SHIFT_OR_ROTATE_TYPE_LEFT_SHIFT: SHIFT_OR_ROTATE_TYPE = 0;
+pub const SHIFT_OR_ROTATE_TYPE_RIGHT_SHIFT: SHIFT_OR_ROTATE_TYPE = 1;
+pub const SHIFT_OR_ROTATE_TYPE_LEFT_ROTATE: SHIFT_OR_ROTATE_TYPE = 2;
+pub const SHIFT_OR_ROTATE_TYPE_RIGHT_ROTATE: SHIFT_OR_ROTATE_TYPE = 3;
+pub type SHIFT_OR_ROTATE_TYPE = ffi::c_uint;
+pub const BITOP_TYPE_BITAND: BITOP_TYPE = 0;
+pub const BITOP_TYPE_BITOR: BITOP_TYPE = 1;
+pub const BITOP_TYPE_BITXOR: BITOP_TYPE = 2;
+pub const BITOP_TYPE_SCALAR_BITAND: BITOP_TYPE = 3;
+pub const BITOP_TYPE_SCALAR_BITOR: BITOP_TYPE = 4;
+pub const BITOP_TYPE_SCALAR_BITXOR: BITOP_TYPE = 5;
+pub type BITOP_TYPE = ffi::c_uint;
+pub const COMPARISON_TYPE_EQ: COMPARISON_TYPE = 0;
+pub const COMPARISON_TYPE_NE: COMPARISON_TYPE = 1;
+pub const COMPARISON_TYPE_GT: COMPARISON_TYPE = 2;
+pub const COMPARISON_TYPE_GE: COMPARISON_TYPE = 3;
+pub const COMPARISON_TYPE_LT: COMPARISON_TYPE = 4;
+pub const COMPARISON_TYPE_LE: COMPARISON_TYPE = 5;
+pub const COMPARISON_TYPE_MAX: COMPARISON_TYPE = 6;
+pub const COMPARISON_TYPE_MIN: COMPARISON_TYPE = 7;
+pub type COMPARISON_TYPE = ffi::c_uint;
+pub const KS_TYPE_BIG_TO_SMALL: KS_TYPE = 0;
+pub const KS_TYPE_SMALL_TO_BIG: KS_TYPE = 1;
+pub type KS_TYPE = ffi::c_uint;
+pub const EXPAND_KIND_NO_CASTING: EXPAND_KIND = 0;
+pub const EXPAND_KIND_CASTING: EXPAND_KIND = 1;
+pub const EXPAND_KIND_SANITY_CHECK: EXPAND_KIND = 2;
+pub type EXPAND_KIND = ffi::c_uint;
 
 #[repr(C)]
 #[derive(Debug, Copy, Clone)]

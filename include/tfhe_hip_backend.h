@@ -47,6 +47,9 @@ enum SHIFT_OR_ROTATE_TYPE { LEFT_SHIFT = 0, RIGHT_SHIFT = 1, LEFT_ROTATE = 2, RI
 enum BITOP_TYPE { BITAND = 0, BITOR = 1, BITXOR = 2, SCALAR_BITAND = 3, SCALAR_BITOR = 4, SCALAR_BITXOR = 5 };
 /* cuda/include/integer/integer.h:24-33 */
 enum COMPARISON_TYPE { EQ = 0, NE = 1, GT = 2, GE = 3, LT = 4, LE = 5, MAX = 6, MIN = 7 };
+/* cuda/include/keyswitch/ks_enums.h, cuda/include/zk/zk_enums.h */
+enum KS_TYPE { BIG_TO_SMALL = 0, SMALL_TO_BIG = 1 };
+enum EXPAND_KIND { NO_CASTING = 0, CASTING = 1, SANITY_CHECK = 2 };
 
 /* ------------------------------------------------------------------ device runtime
  * backends/tfhe-cuda-common/cuda/include/device.h:58-92 (cuda_bind.rs:5-150) */
@@ -760,6 +763,40 @@ void hip_integer_extract_glwe_128_async(
 uint64_t hip_integer_compressed_size_words_128(
     uint32_t glwe_dimension, uint32_t polynomial_size, uint32_t lwe_per_glwe, uint32_t storage_log_modulus,
     uint32_t total_blocks);
+
+/* ------------------------------------------------------------------ expansion of compact ciphertext lists (extensions)
+ * cuda/include/zk/zk.h:10-27 (scratch_cuda_expand_without_verification_64_async, cuda_expand_without_verification_64_async,
+ * cleanup_cuda_expand_without_verification_64; caller: tfhe/src/integer/gpu/ciphertext/compact_list.rs expand), under hip_
+ * names with the reference's parameter lists.  The reference-named symbols remain link stubs.
+ *
+ * lwe_flattened_compact_array_in: for every compact list l, n_c mask words then num_lwes_per_compact_list[l] body words, the
+ * lists end to end, on the device; n_c = casting_ksk_params.input_lwe_dimension, any n_c >= 1, 1 <= bodies per list <= n_c.
+ * Body d of a list expands to the LWE (mask * X^d in Z[X]/(X^n_c + 1), body d); num_lwes = the bodies of all lists.
+ *   NO_CASTING:   lwe_array_out receives the num_lwes expanded LWEs of dimension n_c.  The key arguments are not read.
+ *   CASTING:      lwe_array_out receives 2 * num_lwes LWEs of dimension glwe_dimension * polynomial_size: block 2i is
+ *                 x % message_modulus of the value x packed in body i, block 2i + 1 is (x / carry_modulus) % message_modulus;
+ *                 a block q with is_boolean_array[q] set is clamped to {0, 1}.  BIG_TO_SMALL: casting_keys[g] (n_c -> the
+ *                 bootstrap key's input dimension) is the keyswitch key of the one keyswitch + bootstrap round, which shards
+ *                 over the stream set like every round.  SMALL_TO_BIG: casting_keys[0] (n_c -> glwe_dimension *
+ *                 polynomial_size) first, on the first GPU, then the round with computing_ksks.
+ *   SANITY_CHECK: BIG_TO_SMALL only; blocks 2i and 2i + 1 both receive the packed value of body i (identity table).
+ * The scratch call builds and uploads everything a launch needs (a per-output table of mask offset and rotation, the
+ * round's indexes and tables) and reads the host arrays only then; a launch enqueues one expansion kernel, for
+ * SMALL_TO_BIG one keyswitch, and the round: no host-to-device copy, no allocation, no synchronisation.
+ * Panics: zero lists, a list of zero bodies or of more than n_c, is_boolean_array_len < 2 * num_lwes (pad with false),
+ * CASTING with carry_modulus != message_modulus, SANITY_CHECK with SMALL_TO_BIG, key dimensions that do not chain, a launch on
+ * a scratch created with allocate_gpu_memory = false. */
+uint64_t hip_scratch_expand_without_verification_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t glwe_dimension, uint32_t polynomial_size,
+    CudaLweKeyswitchKeyParamsFFI computing_ksk_params, CudaLweKeyswitchKeyParamsFFI casting_ksk_params, uint32_t pbs_level,
+    uint32_t pbs_base_log, uint32_t grouping_factor, const uint32_t *num_lwes_per_compact_list, const bool *is_boolean_array,
+    const uint32_t is_boolean_array_len, uint32_t num_compact_lists, uint32_t message_modulus, uint32_t carry_modulus,
+    enum PBS_TYPE pbs_type, enum KS_TYPE casting_key_type, bool allocate_gpu_memory, enum EXPAND_KIND expand_kind,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_expand_without_verification_64_async(
+    CudaStreamsFFI streams, void *lwe_array_out, const void *lwe_flattened_compact_array_in, int8_t *mem_ptr,
+    void *const *bsks, void *const *computing_ksks, void *const *casting_keys);
+void hip_cleanup_expand_without_verification_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
 
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's

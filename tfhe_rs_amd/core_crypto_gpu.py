@@ -149,6 +149,37 @@ class CudaLweCiphertextList:
         return flat.reshape(self.lwe_ciphertext_count, self.lwe_dimension + 1)
 
 
+class CudaLweCompactCiphertextList:
+    """Compact LWE lists end to end on the device, as the expansion entry points read them (the flattened array of
+    integer/gpu/ciphertext/compact_list.rs): per list n_c mask words, then one body word per ciphertext of the list."""
+
+    def __init__(self, d_vec, n_c, num_lwe_per_compact_list):
+        self.d_vec = d_vec
+        self.n_c = int(n_c)
+        self.num_lwe_per_compact_list = [int(c) for c in num_lwe_per_compact_list]
+        assert self.n_c >= 1 and self.num_lwe_per_compact_list, "no compact list"
+        assert all(1 <= c <= self.n_c for c in self.num_lwe_per_compact_list), \
+            "a compact list holds between 1 and n_c bodies"
+        assert d_vec.len == self.size_words(self.n_c, self.num_lwe_per_compact_list), \
+            "the flattened words do not have the size the list counts describe"
+
+    @staticmethod
+    def size_words(n_c, num_lwe_per_compact_list):
+        return sum(int(n_c) + int(c) for c in num_lwe_per_compact_list)
+
+    @classmethod
+    def from_flat_words(cls, words, n_c, num_lwe_per_compact_list, streams):
+        words = np.ascontiguousarray(words, dtype=U64).reshape(-1)
+        return cls(CudaVec.from_cpu_async(words, streams), n_c, num_lwe_per_compact_list)
+
+    @property
+    def lwe_ciphertext_count(self):
+        return sum(self.num_lwe_per_compact_list)
+
+    def to_flat_words(self, streams):
+        return self.d_vec.copy_to_cpu(streams)
+
+
 class CudaGlweCiphertextList:
     def __init__(self, d_vec, glwe_ciphertext_count, glwe_dimension, polynomial_size):
         self.d_vec = d_vec

@@ -197,6 +197,50 @@ void launch_unpack_glwe(hipStream_t st, uint64_t *glwe_out, const uint64_t *word
   HX_LAUNCH(unpack_glwe_kernel, dim3(((k + 1) * N + 255) / 256), dim3(256), 0, st, glwe_out, words, k, N, bodies, bits);
 }
 
+// ------------------------------------------------------------------ compact LWE lists: expansion
+// Output row o is the list's shared mask times X^d in Z[X]/(X^n_c + 1) followed by body d
+// (cc/algorithms/polynomial_algorithms.rs polynomial_wrapping_monic_monomial_mul; cuda/src/zk/expand.cuh lwe_expand):
+//   row[e] = mask[e - d]            for d <= e < n_c
+//   row[e] = -mask[e - d + n_c]     for e < d
+//   row[n_c] = body d, the word at mask + n_c + d
+// Only data moves: (n_c + 1) * 8 bytes written per row, the mask read from cache by every workgroup of its list.  Lane
+// t of a workgroup stores words t, t + 256, ... of a chunk of kExpandChunk consecutive words of ONE row, so every wave
+// store is 64 consecutive 8-byte words (rows are n_c + 1 words long: every other row starts off a 16-byte boundary, so
+// 8 bytes is the widest store all rows can take) and the loads are consecutive too, with one break at e = d.
+// Grid: x = row, y = chunk of the row.  No LDS.
+constexpr uint32_t kExpandThreads = 256, kExpandWordsPerThread = 4, kExpandChunk = kExpandThreads * kExpandWordsPerThread;
+__global__ void __launch_bounds__(kExpandThreads) lwe_expand_kernel(uint64_t *__restrict__ out,
+                                                                    const uint64_t *__restrict__ in,
+                                                                    const ExpandJob *__restrict__ jobs, uint32_t n_c) {
+  const ExpandJob job = jobs[blockIdx.x];
+  const uint64_t *mask = in + job.mask_offset;
+  uint64_t *row = out + (size_t)blockIdx.x * ((size_t)n_c + 1);
+  const uint32_t d = job.rotation, first = blockIdx.y * kExpandChunk + threadIdx.x;
+  uint64_t v[kExpandWordsPerThread];
+  HX_UNROLL
+  for (uint32_t u = 0; u < kExpandWordsPerThread; ++u) {
+    const uint32_t e = first + u * kExpandThreads;
+    v[u] = 0;
+    if (e < n_c) {
+      const uint64_t m = mask[e < d ? e + n_c - d : e - d];
+      v[u] = e < d ? (uint64_t)0 - m : m;
+    } else if (e == n_c) {
+      v[u] = mask[(size_t)n_c + d];
+    }
+  }
+  HX_UNROLL
+  for (uint32_t u = 0; u < kExpandWordsPerThread; ++u) {
+    const uint32_t e = first + u * kExpandThreads;
+    if (e <= n_c) row[e] = v[u];
+  }
+}
+void launch_lwe_expand(hipStream_t st, uint64_t *lwe_out, const uint64_t *flattened_in, const ExpandJob *jobs,
+                       uint32_t n_c, uint32_t num_lwes) {
+  if (!num_lwes) return;
+  HX_LAUNCH(lwe_expand_kernel, dim3(num_lwes, (n_c + kExpandChunk) / kExpandChunk), dim3(kExpandThreads), 0, st, lwe_out,
+            flattened_in, jobs, n_c);
+}
+
 __global__ void iota_u64_kernel(uint64_t *out, uint32_t count) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) out[i] = i;

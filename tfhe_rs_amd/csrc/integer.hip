@@ -229,6 +229,8 @@ static uint32_t num_inputs_on_gpu(uint32_t total, uint32_t gpu, uint32_t gpus) {
 struct LutDriver {
   Params p{};
   uint32_t cap = 0, num_luts = 0, many_max = 1;
+  uint32_t in_n = 0;  // LWE dimension of a round's inputs, the keyswitch key's input dimension: p.big_n, unless the key
+                      // casts from another key (compact-list expansion)
   struct PerGpu {
     uint32_t gpu = 0;
     uint64_t *d_ks = nullptr, *d_luts = nullptr, *d_trivial = nullptr;  // d_trivial = 0, 1, ..., cap - 1
@@ -253,13 +255,14 @@ struct LutDriver {
 
   // max_many: the most functions one round extracts per bootstrap (sizes the dense output buffers)
   void init(const CudaStreamsFFI &s, const Params &params, uint32_t capacity,
-            const std::vector<std::vector<uint64_t>> &luts, uint32_t max_many = 1) {
+            const std::vector<std::vector<uint64_t>> &luts, uint32_t max_many = 1, uint32_t input_n = 0) {
     HX_PANIC_IF_FALSE(s.gpu_count >= 1 && s.streams != nullptr, "radix layer: empty stream set");
     p = params;
     cap = capacity;
     many_max = std::max(1u, max_many);
     num_luts = (uint32_t)luts.size();
-    const size_t lw = (size_t)(p.k + 1) * p.N, w = (size_t)p.big_n + 1;
+    in_n = input_n ? input_n : p.big_n;
+    const size_t lw = (size_t)(p.k + 1) * p.N, w = (size_t)p.big_n + 1, wi = (size_t)in_n + 1;
     std::vector<uint64_t> triv(cap);
     for (uint32_t i = 0; i < cap; ++i) triv[i] = i;
     gpus.resize(s.gpu_count);
@@ -275,13 +278,13 @@ struct LutDriver {
       g.d_trivial = dev_upload(st, triv);
       if (i == 0 && many_max > 1) radix_alloc((void **)&g.d_many, (size_t)many_max * cap * w * sizeof(uint64_t));
       if (i > 0) {
-        radix_alloc((void **)&g.d_in, (size_t)cap * w * sizeof(uint64_t));
+        radix_alloc((void **)&g.d_in, (size_t)cap * wi * sizeof(uint64_t));
         radix_alloc((void **)&g.d_out, (size_t)many_max * cap * w * sizeof(uint64_t));
         radix_alloc((void **)&g.d_lut_idx, (size_t)cap * sizeof(uint64_t));
         // An event is recorded on a stream of ITS device only (hipEventRecord rejects a foreign stream): `staged` and
         // `copied` are recorded on the first GPU's stream, `done` on this GPU's; waiting across devices is allowed.
         HX_CHECK(hipSetDevice((int)gpus[0].gpu));
-        radix_alloc((void **)&g.d0_in, (size_t)cap * w * sizeof(uint64_t));
+        radix_alloc((void **)&g.d0_in, (size_t)cap * wi * sizeof(uint64_t));
         radix_alloc((void **)&g.d0_out, (size_t)many_max * cap * w * sizeof(uint64_t));
         if (!t_dry) {
           HX_CHECK(hipEventCreateWithFlags(&g.staged, hipEventDisableTiming));
@@ -294,7 +297,7 @@ struct LutDriver {
           g.direct = peer_direct((int)g.gpu, (int)gpus[0].gpu) && peer_direct((int)gpus[0].gpu, (int)g.gpu);
           // host-staged copies: three pinned regions — shard in, its LUT indexes, results out — so that each leg of a copy
           // runs on the stream of the device whose memory it touches and no region is rewritten before its reader is done
-          if (!g.direct) HX_CHECK(hipHostMalloc((void **)&g.h_stage, ((size_t)cap * w + cap + (size_t)many_max * cap * w) * sizeof(uint64_t), 0));
+          if (!g.direct) HX_CHECK(hipHostMalloc((void **)&g.h_stage, ((size_t)cap * wi + cap + (size_t)many_max * cap * w) * sizeof(uint64_t), 0));
         }
       }
       HX_CHECK(hipStreamSynchronize(st));  // the LUT sources may be temporaries
@@ -308,7 +311,7 @@ struct LutDriver {
               uint32_t many = 1, uint32_t stride = 0) const {
     {
       HX_RANGE("keyswitch (%u blocks, gpu %u)", c, g.gpu);
-      cuda_keyswitch_lwe_ciphertext_vector_64_64_async(st, g.gpu, g.d_ks, g.d_trivial, in, in_idx, ksk, p.big_n, p.small_n,
+      cuda_keyswitch_lwe_ciphertext_vector_64_64_async(st, g.gpu, g.d_ks, g.d_trivial, in, in_idx, ksk, in_n, p.small_n,
                                                        p.ks_base_log, p.ks_level, c);
     }
     HX_RANGE("bootstrap (%u blocks, %u functions, gpu %u)", c, many, g.gpu);
@@ -339,7 +342,7 @@ struct LutDriver {
   // device's memory.  Not reachable on an MI355X node (every pair of GPUs is an xGMI peer): exercised on the
   // CPU tier's device model only.
   uint64_t *h_in(const PerGpu &g) const { return g.h_stage; }
-  uint64_t *h_idx(const PerGpu &g) const { return g.h_stage + (size_t)cap * ((size_t)p.big_n + 1); }
+  uint64_t *h_idx(const PerGpu &g) const { return g.h_stage + (size_t)cap * ((size_t)in_n + 1); }
   uint64_t *h_out(const PerGpu &g) const { return h_idx(g) + cap; }
 
   // one round, split into launches of at most `cap` blocks; a null in_idx / out_idx means "block s".
@@ -349,7 +352,7 @@ struct LutDriver {
   void round(const CudaStreamsFFI &s, uint64_t *out, const uint64_t *out_idx, const uint64_t *in, const uint64_t *in_idx,
              const uint64_t *lut_idx, uint32_t count, void *const *ksks, void *const *bsks, uint32_t many = 1,
              uint32_t stride = 0) const {
-    const size_t w = (size_t)p.big_n + 1;
+    const size_t w = (size_t)p.big_n + 1, wi = (size_t)in_n + 1;
     HX_PANIC_IF_FALSE(many >= 1 && many <= many_max && (many == 1 || out_idx != nullptr),
                       "radix layer: a round of %u functions per bootstrap on a driver created for %u", many, many_max);
     const uint32_t avail = std::min<uint32_t>(s.gpu_count, (uint32_t)gpus.size());
@@ -361,7 +364,7 @@ struct LutDriver {
       const uint32_t min_blocks = multi_gpu_threshold(p, gpus[0].gpu);
       const uint32_t active = std::max(1u, std::min(avail, (c + min_blocks - 1) / min_blocks));
       const uint64_t *ii = in_idx ? in_idx + off : nullptr, *oi = out_idx ? out_idx + off : nullptr;
-      const uint64_t *in0 = in_idx ? in : in + off * w;
+      const uint64_t *in0 = in_idx ? in : in + off * wi;
       uint64_t *out0 = out_idx ? out : out + off * w;
       uint32_t first = num_inputs_on_gpu(c, 0, active);
       // shards of the other GPUs: gather on the first GPU, ship, compute, ship back (all asynchronous)
@@ -374,11 +377,11 @@ struct LutDriver {
         HX_RANGE("scatter %u blocks to gpu %u", ci, g.gpu);  // integer.cuh:958 (the range covers the shard's launches too)
         HX_CHECK(hipSetDevice((int)gpus[0].gpu));
         if (ii)
-          axpy(st0, g.d0_in, nullptr, in0, ii + begin, 1, nullptr, nullptr, (uint32_t)w, ci);
+          axpy(st0, g.d0_in, nullptr, in0, ii + begin, 1, nullptr, nullptr, (uint32_t)wi, ci);
         else  // trivial input indexing: the shard starts at block `begin`
-          HX_CHECK(hipMemcpyAsync(g.d0_in, in0 + (size_t)begin * w, (size_t)ci * w * sizeof(uint64_t),
+          HX_CHECK(hipMemcpyAsync(g.d0_in, in0 + (size_t)begin * wi, (size_t)ci * wi * sizeof(uint64_t),
                                   hipMemcpyDeviceToDevice, st0));
-        const size_t in_bytes = (size_t)ci * w * sizeof(uint64_t), idx_bytes = (size_t)ci * sizeof(uint64_t),
+        const size_t in_bytes = (size_t)ci * wi * sizeof(uint64_t), idx_bytes = (size_t)ci * sizeof(uint64_t),
                      out_bytes = (size_t)many * ci * w * sizeof(uint64_t);
         if (!g.direct) {  // first legs on the first GPU's stream, which owns the sources
           HX_CHECK(hipMemcpyAsync(h_in(g), g.d0_in, in_bytes, hipMemcpyDeviceToHost, st0));
@@ -1611,6 +1614,26 @@ struct NoiseSquashMem : ScratchHeader {
     if (pbs_buf && grouping) hip_cleanup_multi_bit_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
     else if (pbs_buf) hip_cleanup_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
     for (void *d : {(void *)d_packed, (void *)d_after_ks, (void *)d_trivial, (void *)d_lo, (void *)d_hi, (void *)d_lut})
+      if (d) scratch_free(d);
+  }
+};
+
+// Expansion of compact ciphertext lists (cuda/include/zk/zk_utilities.h zk_expand_mem, cuda/src/zk/zk.cuh): the shared
+// mask of a list rotated once per body (launch_lwe_expand, ciphertext.hip), cast to the compute key, every packed body
+// split into its message and carry block by ONE round of the driver over 2 * num_lwes blocks.
+struct ExpandMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x58504E44;  // "XPND"
+  uint32_t kind = 0, ks_type = 0;  // EXPAND_KIND, KS_TYPE
+  uint32_t n_c = 0;                // the casting key's input dimension: the compact lists' mask length
+  uint32_t cast_out_n = 0, cast_base_log = 0, cast_level = 0;  // SMALL_TO_BIG: the casting keyswitch of its own
+  uint32_t num_lwes = 0, gpu = 0;
+  bool has_drv = false;
+  LutDriver drv;
+  ExpandJob *d_jobs = nullptr;  // per output row: where its list's mask starts, which body it takes (built once, here)
+  uint64_t *d_expanded = nullptr, *d_cast = nullptr, *d_in_idx = nullptr, *d_out_idx = nullptr, *d_lut_idx = nullptr;
+  void release(const CudaStreamsFFI &s) {
+    if (has_drv) drv.release(s);
+    for (void *d : {(void *)d_jobs, (void *)d_expanded, (void *)d_cast, (void *)d_in_idx, (void *)d_out_idx, (void *)d_lut_idx})
       if (d) scratch_free(d);
   }
 };
@@ -3131,6 +3154,143 @@ void hip_integer_apply_noise_squashing_64_async(CudaStreamsFFI streams, CudaRadi
 
 void hip_cleanup_integer_apply_noise_squashing_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
   scratch_destroy<NoiseSquashMem>(streams, mem_ptr_void, "cleanup apply_noise_squashing");
+}
+
+// ---- cuda/include/zk/zk.h:10-27, under hip_ names (the reference-named symbols stay link stubs) -----------------------
+// n_c = casting_ksk_params.input_lwe_dimension.  Outputs of every kind but NO_CASTING have dimension glwe_dimension *
+// polynomial_size (the reference sizes them by the casting key's larger dimension, the same number in its sets).
+uint64_t hip_scratch_expand_without_verification_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, uint32_t glwe_dimension, uint32_t polynomial_size,
+    CudaLweKeyswitchKeyParamsFFI computing_ksk_params, CudaLweKeyswitchKeyParamsFFI casting_ksk_params, uint32_t pbs_level,
+    uint32_t pbs_base_log, uint32_t grouping_factor, const uint32_t *num_lwes_per_compact_list, const bool *is_boolean_array,
+    const uint32_t is_boolean_array_len, uint32_t num_compact_lists, uint32_t message_modulus, uint32_t carry_modulus,
+    enum PBS_TYPE pbs_type, enum KS_TYPE casting_key_type, bool allocate_gpu_memory, enum EXPAND_KIND expand_kind,
+    enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const char *who = "expand_without_verification";
+  const uint32_t kind = (uint32_t)expand_kind, ks_type = (uint32_t)casting_key_type;
+  const uint32_t n_c = casting_ksk_params.input_lwe_dimension;
+  HX_PANIC_IF_FALSE(kind == NO_CASTING || kind == CASTING || kind == SANITY_CHECK, "%s: unknown expand kind %u", who, kind);
+  HX_PANIC_IF_FALSE(ks_type == BIG_TO_SMALL || ks_type == SMALL_TO_BIG, "%s: unknown casting key type %u", who, ks_type);
+  HX_PANIC_IF_FALSE(num_compact_lists >= 1 && num_lwes_per_compact_list != nullptr, "%s: no compact list to expand", who);
+  HX_PANIC_IF_FALSE(n_c >= 1 && n_c <= kExpandMaxDimension, "%s: unsupported compact list dimension %u", who, n_c);
+  uint64_t total = 0;
+  for (uint32_t l = 0; l < num_compact_lists; ++l) {
+    const uint32_t c = num_lwes_per_compact_list[l];
+    HX_PANIC_IF_FALSE(c >= 1 && c <= n_c,
+                      "%s: compact list %u holds %u bodies, a list holds 1 .. %u (the casting key's input dimension)", who, l,
+                      c, n_c);
+    total += c;
+  }
+  HX_PANIC_IF_FALSE(total >= 1 && 2 * total <= 0xFFFFFFFFull, "%s: %llu bodies in all", who, (unsigned long long)total);
+  const uint32_t num_lwes = (uint32_t)total;
+  Params p{};
+  if (kind != NO_CASTING) {
+    HX_PANIC_IF_FALSE(kind != SANITY_CHECK || ks_type == BIG_TO_SMALL, "%s: SANITY_CHECK not supported for SMALL_TO_BIG casting",
+                      who);
+    HX_PANIC_IF_FALSE(kind != CASTING || carry_modulus == message_modulus,
+                      "%s: GPU backend requires carry_modulus equal to message_modulus (got %u, %u)", who, carry_modulus,
+                      message_modulus);
+    HX_PANIC_IF_FALSE(is_boolean_array != nullptr && is_boolean_array_len >= 2 * num_lwes,
+                      "%s: is_boolean_array holds %u entries, 2 * %u bodies need %u (pad it with false)", who,
+                      is_boolean_array_len, num_lwes, 2 * num_lwes);
+    const uint32_t big_n = glwe_dimension * polynomial_size;
+    // BIG_TO_SMALL: the casting key IS the round's keyswitch key; SMALL_TO_BIG: a keyswitch of its own, then the computing key
+    const CudaLweKeyswitchKeyParamsFFI round_ksk = ks_type == BIG_TO_SMALL ? casting_ksk_params : computing_ksk_params;
+    HX_PANIC_IF_FALSE(ks_type == BIG_TO_SMALL || (casting_ksk_params.output_lwe_dimension == big_n &&
+                                                  computing_ksk_params.input_lwe_dimension == big_n),
+                      "%s: a SMALL_TO_BIG casting key ends on the big compute key (%u), where the computing keyswitch key starts",
+                      who, big_n);
+    CudaLweBootstrapKeyParamsFFI b{round_ksk.output_lwe_dimension, glwe_dimension, polynomial_size, pbs_base_log, pbs_level,
+                                   big_n, (uint32_t)pbs_type, grouping_factor};
+    // (make_params ties the keyswitch key's INPUT to the big key; here the round's input dimension is the driver's in_n)
+    CudaLweKeyswitchKeyParamsFFI k{big_n, round_ksk.output_lwe_dimension, round_ksk.base_log, round_ksk.level_count};
+    p = make_params(b, k, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  }
+  return scratch_create<ExpandMem>(streams, mem_ptr, allocate_gpu_memory, who, [&](ExpandMem &m) {
+    const hipStream_t st = S0(streams);
+    m.kind = kind, m.ks_type = ks_type, m.n_c = n_c, m.num_lwes = num_lwes, m.gpu = G0(streams);
+    std::vector<ExpandJob> jobs;
+    jobs.reserve(num_lwes);
+    uint64_t at = 0;
+    for (uint32_t l = 0; l < num_compact_lists; ++l) {
+      for (uint32_t d = 0; d < num_lwes_per_compact_list[l]; ++d) jobs.push_back(ExpandJob{at, d, 0});
+      at += (uint64_t)n_c + num_lwes_per_compact_list[l];
+    }
+    m.d_jobs = dev_upload(st, jobs);
+    if (kind == NO_CASTING) return;
+    // zk_utilities.h:190-230,283-300: per list of c bodies first the c message extractions, then the c carry extractions;
+    // output 2i is the message block of body i, 2i + 1 its carry block; a boolean output takes the sanitising table
+    const uint32_t blocks = 2 * num_lwes;
+    std::vector<uint64_t> in_idx(blocks), out_idx(blocks), lut_idx(blocks);
+    uint32_t offset = 0;
+    for (uint32_t l = 0; l < num_compact_lists; ++l) {
+      const uint32_t c = num_lwes_per_compact_list[l];
+      for (uint32_t i = 0; i < 2 * c; ++i) {
+        const uint32_t q = i + 2 * offset, half = i / c;
+        in_idx[q] = i % c + offset;
+        out_idx[q] = 2 * in_idx[q] + half;
+        lut_idx[q] = kind == SANITY_CHECK ? 0 : half + (is_boolean_array[out_idx[q]] ? 2 : 0);
+      }
+      offset += c;
+    }
+    m.d_in_idx = dev_upload(st, in_idx);
+    m.d_out_idx = dev_upload(st, out_idx);
+    m.d_lut_idx = dev_upload(st, lut_idx);
+    const uint64_t msg = p.msg, carry = p.carry;
+    std::vector<std::function<uint64_t(uint64_t)>> fs;
+    if (kind == SANITY_CHECK) {
+      fs = {[](uint64_t x) { return x; }};
+    } else {  // (x / carry_modulus only splits the packed value because carry == message, as the reference has it)
+      fs = {[=](uint64_t x) { return x % msg; }, [=](uint64_t x) { return (x / carry) % msg; },
+            [=](uint64_t x) { return (uint64_t)(x % msg != 0); }, [=](uint64_t x) { return (uint64_t)((x / carry) % msg != 0); }};
+    }
+    std::vector<std::vector<uint64_t>> luts(fs.size(), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
+    for (size_t t = 0; t < fs.size(); ++t) generate_lut(p, luts[t].data(), fs[t]);
+    radix_alloc((void **)&m.d_expanded, (size_t)num_lwes * ((size_t)n_c + 1) * sizeof(uint64_t));
+    if (ks_type == SMALL_TO_BIG) {
+      m.cast_out_n = casting_ksk_params.output_lwe_dimension;
+      m.cast_base_log = casting_ksk_params.base_log, m.cast_level = casting_ksk_params.level_count;
+      radix_alloc((void **)&m.d_cast, (size_t)num_lwes * ((size_t)m.cast_out_n + 1) * sizeof(uint64_t));
+    }
+    m.has_drv = true;
+    m.drv.init(streams, p, blocks, luts, 1, ks_type == BIG_TO_SMALL ? n_c : 0);
+  });
+}
+
+void hip_expand_without_verification_64_async(CudaStreamsFFI streams, void *lwe_array_out,
+                                              const void *lwe_flattened_compact_array_in, int8_t *mem_ptr, void *const *bsks,
+                                              void *const *computing_ksks, void *const *casting_keys) {
+  first_gpu(streams);
+  auto *m = scratch_use<ExpandMem>(mem_ptr, "expand_without_verification");
+  HX_PANIC_IF_FALSE(lwe_array_out != nullptr && lwe_flattened_compact_array_in != nullptr,
+                    "expand_without_verification: null pointer");
+  const hipStream_t st = S0(streams);
+  const uint64_t *in = (const uint64_t *)lwe_flattened_compact_array_in;
+  if (m->kind == NO_CASTING) {
+    HX_RANGE("expand (%u lwes)", m->num_lwes);
+    launch_lwe_expand(st, (uint64_t *)lwe_array_out, in, m->d_jobs, m->n_c, m->num_lwes);
+    return;
+  }
+  const bool to_big = m->ks_type == SMALL_TO_BIG;
+  HX_PANIC_IF_FALSE(bsks && casting_keys && casting_keys[0] && (!to_big || computing_ksks),
+                    "expand_without_verification: null key pointer");
+  {
+    HX_RANGE("expand (%u lwes)", m->num_lwes);
+    launch_lwe_expand(st, m->d_expanded, in, m->d_jobs, m->n_c, m->num_lwes);
+  }
+  if (to_big) {
+    HX_RANGE("casting keyswitch (%u lwes)", m->num_lwes);
+    const uint64_t *triv = m->drv.gpus[0].d_trivial;  // 0 .. 2 * num_lwes - 1
+    cuda_keyswitch_lwe_ciphertext_vector_64_64_async(st, m->gpu, m->d_cast, triv, m->d_expanded, triv, casting_keys[0], m->n_c,
+                                                     m->cast_out_n, m->cast_base_log, m->cast_level, m->num_lwes);
+  }
+  HX_RANGE("message and carry extraction (%u blocks)", 2 * m->num_lwes);
+  m->drv.round(streams, (uint64_t *)lwe_array_out, m->d_out_idx, to_big ? m->d_cast : m->d_expanded, m->d_in_idx, m->d_lut_idx,
+               2 * m->num_lwes, to_big ? computing_ksks : casting_keys, bsks);
+}
+
+void hip_cleanup_expand_without_verification_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<ExpandMem>(streams, mem_ptr_void, "cleanup expand_without_verification");
 }
 
 }  // extern "C"

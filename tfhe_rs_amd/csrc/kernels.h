@@ -111,6 +111,16 @@ void launch_unpack_extract(hipStream_t st, uint64_t *lwe_out, const uint64_t *pa
 void launch_unpack_glwe(hipStream_t st, uint64_t *glwe_out, const uint64_t *words, uint32_t k, uint32_t N, uint32_t bodies,
                         uint32_t bits);
 
+// compact LWE lists: output row o = the mask at word mask_offset of the flattened input times X^rotation, then body
+// `rotation` of that list (the word at mask_offset + n_c + rotation); rotation < n_c.  One launch, nothing else.
+struct ExpandJob {
+  uint64_t mask_offset;
+  uint32_t rotation, unused;
+};
+constexpr uint32_t kExpandMaxDimension = 1u << 25;  // the 1024-word row chunks of the largest n_c fit the grid's y extent
+void launch_lwe_expand(hipStream_t st, uint64_t *lwe_out, const uint64_t *flattened_in, const ExpandJob *jobs,
+                       uint32_t n_c, uint32_t num_lwes);
+
 // multi-bit — multibit.hip
 struct MultiBitArgs {
   PbsArgs pbs;             // bsk = Fourier-domain multi-bit key on the device ([group][subset][level][row][col][slot])

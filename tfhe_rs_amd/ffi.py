@@ -237,6 +237,12 @@ SIGNATURES = {
     "hip_integer_scratch_batch": (None, [_u32]),
     "hip_integer_mult_pbs_count": (_u64, [_v]),
     "hip_integer_propagate_pbs_count": (_u64, [_u32]),
+    # expansion of compact ciphertext lists
+    "hip_scratch_expand_without_verification_64_async":
+        (_u64, [_S, _i8pp, _u32, _u32, _KK, _KK, _u32, _u32, _u32, C.POINTER(C.c_uint32), C.POINTER(C.c_bool), _u32, _u32,
+                _u32, _u32, _u32, _u32, _b, _u32, _u32]),
+    "hip_expand_without_verification_64_async": (None, [_S, _v, _v, _v, _i8pp, _i8pp, _i8pp]),
+    "hip_cleanup_expand_without_verification_64": (None, [_S, _i8pp]),
     # 128-bit PBS and noise squashing
     "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
     "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),

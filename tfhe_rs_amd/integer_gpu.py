@@ -15,11 +15,14 @@ import ctypes as C
 import numpy as np
 
 from . import ffi
-from .core_crypto_gpu import CudaLweBootstrapKey, CudaLweKeyswitchKey, CudaLweMultiBitBootstrapKey128, CudaVec, _lib
+from .core_crypto_gpu import (CudaLweBootstrapKey, CudaLweCompactCiphertextList, CudaLweKeyswitchKey,
+                              CudaLweMultiBitBootstrapKey128, CudaVec, _lib)
 
 U64 = np.uint64
 PBS_TYPE_MULTI_BIT, PBS_TYPE_CLASSICAL = 0, 1          # pbs/pbs_enums.h:4
 OUTPUT_FLAG_NONE, OUTPUT_FLAG_OVERFLOW, OUTPUT_FLAG_CARRY = 0, 1, 2   # integer/integer.h:39
+KS_TYPE_BIG_TO_SMALL, KS_TYPE_SMALL_TO_BIG = 0, 1                      # keyswitch/ks_enums.h
+EXPAND_KIND = {"no_casting": 0, "casting": 1, "sanity_check": 2}       # zk/zk_enums.h
 
 
 class CudaServerKey:
@@ -794,3 +797,134 @@ class CudaCompressedSquashedNoiseCiphertextList:
         return cls(CudaVec.from_cpu_async(words, streams, elem_words=2), m["block_counts"], m["original_block_counts"],
                    m["glwe_dimension"], m["polynomial_size"], m["lwe_per_glwe"], m["storage_log_modulus"],
                    m["message_modulus"], m["carry_modulus"])
+
+
+# ---------------------------------------------------------------------------------------------- compact list expansion
+# integer/gpu/key_switching_key.rs (CudaKeySwitchingKey) and integer/gpu/ciphertext/compact_list.rs
+# (CudaFlattenedVecCompactCiphertextList, CudaCompactCiphertextListExpander), over the hip_ entry points of
+# include/tfhe_hip_backend.h, "expansion of compact ciphertext lists".
+class CudaKeySwitchingKey:
+    """key_switching_key.rs: the casting key from the public-key encryption key to a key of the destination server key
+    ("small": its bootstrap key's input key, "big": its GLWE key), with its decomposition, and the destination server key."""
+
+    def __init__(self, lwe_keyswitch_key: CudaLweKeyswitchKey, destination_key, dest_server_key: CudaServerKey):
+        assert destination_key in ("small", "big"), "destination_key: 'small' or 'big'"
+        want = (dest_server_key.bootstrapping_key.input_lwe_dimension if destination_key == "small"
+                else dest_server_key.bootstrapping_key.output_lwe_dimension)
+        assert lwe_keyswitch_key.output_key_lwe_dimension == want, "the casting key does not end on the destination key"
+        self.lwe_keyswitch_key, self.destination_key, self.dest_server_key = lwe_keyswitch_key, destination_key, dest_server_key
+
+    def _params(self):
+        k = self.lwe_keyswitch_key
+        return ffi.CudaLweKeyswitchKeyParamsFFI(k.input_key_lwe_dimension, k.output_key_lwe_dimension, k.decomp_base_log,
+                                                k.decomp_level_count)
+
+    def _ks_type(self):
+        return KS_TYPE_BIG_TO_SMALL if self.destination_key == "small" else KS_TYPE_SMALL_TO_BIG
+
+
+class CudaFlattenedVecCompactCiphertextList:
+    """compact_list.rs: compact lists end to end on the device and what they hold.  `data_info`: one entry per encrypted
+    value, ("unsigned", blocks) or ("boolean",); the blocks of all values, in order, are packed two per body (block 2j +
+    message_modulus * block 2j + 1 in body j), so ceil(blocks / 2) bodies in all."""
+
+    def __init__(self, d_list: CudaLweCompactCiphertextList, data_info, message_modulus, carry_modulus):
+        self.d_list = d_list
+        self.data_info = [tuple(e) for e in data_info]
+        for e in self.data_info:
+            assert e[0] in ("unsigned", "boolean"), f"data kind {e[0]!r} is not supported"
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+        total = self.total_blocks
+        assert d_list.lwe_ciphertext_count == (total + 1) // 2, \
+            "the lists do not hold one body per pair of blocks of the data they are said to hold"
+        # which expanded block is a boolean; padded with False to the two blocks every body expands to
+        flags = [e[0] == "boolean" for e in self.data_info for _ in range(self._blocks(e))]
+        self.is_boolean = flags + [False] * (2 * d_list.lwe_ciphertext_count - len(flags))
+
+    @staticmethod
+    def _blocks(entry):
+        return 1 if entry[0] == "boolean" else int(entry[1])
+
+    @property
+    def total_blocks(self):
+        return sum(self._blocks(e) for e in self.data_info)
+
+    @property
+    def num_lwe_per_compact_list(self):
+        return self.d_list.num_lwe_per_compact_list
+
+    @classmethod
+    def from_flat_words(cls, words, n_c, num_lwe_per_compact_list, data_info, message_modulus, carry_modulus, streams):
+        return cls(CudaLweCompactCiphertextList.from_flat_words(words, n_c, num_lwe_per_compact_list, streams), data_info,
+                   message_modulus, carry_modulus)
+
+    def __len__(self):
+        return len(self.data_info)
+
+    def get_kind_of(self, i):
+        return self.data_info[i] if 0 <= i < len(self.data_info) else None
+
+    def expand(self, key: CudaKeySwitchingKey, streams, kind="casting"):
+        """compact_list.rs expand: every body rotated out of its list's mask, cast with `key` and split into its two
+        blocks by one bootstrap round of the destination server key.  kind "sanity_check": the identity table instead
+        of the split; "no_casting": the expanded LWEs under the encryption key, returned as a CudaLweCiphertextList."""
+        from .core_crypto_gpu import CudaLweCiphertextList
+        sks, casting, d = key.dest_server_key, key.lwe_keyswitch_key, self.d_list
+        assert casting.input_key_lwe_dimension == d.n_c, "the casting key does not start on the lists' encryption key"
+        assert (sks.message_modulus, sks.carry_modulus) == (self.message_modulus, self.carry_modulus)
+        bsk = sks.bootstrapping_key
+        bk = sks._bsk_params()
+        n = d.lwe_ciphertext_count
+        s, keep = CudaServerKey._streams(streams)
+        counts = (C.c_uint32 * len(d.num_lwe_per_compact_list))(*d.num_lwe_per_compact_list)
+        flags = (C.c_bool * len(self.is_boolean))(*self.is_boolean)
+        out_dim = d.n_c if kind == "no_casting" else bsk.output_lwe_dimension
+        out_count = n if kind == "no_casting" else 2 * n
+        d_out = CudaLweCiphertextList.new(out_dim, out_count, streams)
+        ksks, bsks = sks._key_ptrs(streams)
+        nk = len(streams) if key.destination_key == "small" else 1
+        assert len(casting.d_vecs) >= nk, "casting key has fewer GPU replicas than the stream set has streams"
+        casts = (C.c_void_p * nk)(*[v.ptr for v in casting.d_vecs[:nk]])
+        mem = C.c_void_p()
+        _lib().hip_scratch_expand_without_verification_64_async(
+            s, C.byref(mem), bsk.glwe_dimension, bsk.polynomial_size, sks._ksk_params(), key._params(),
+            bsk.decomp_level_count, bsk.decomp_base_log, bk.grouping_factor, counts, flags, len(self.is_boolean),
+            len(d.num_lwe_per_compact_list), self.message_modulus, self.carry_modulus, bk.pbs_type, key._ks_type(), True,
+            EXPAND_KIND[kind], sks._noise_reduction())
+        _lib().hip_expand_without_verification_64_async(s, d_out.d_vec.ptr, d.d_vec.ptr, mem, bsks, ksks, casts)
+        _lib().hip_cleanup_expand_without_verification_64(s, C.byref(mem))
+        if kind == "no_casting":
+            return d_out
+        return CudaCompactCiphertextListExpander(d_out, self.data_info, self.message_modulus, self.carry_modulus)
+
+
+class CudaCompactCiphertextListExpander:
+    """compact_list.rs: the expanded blocks (one LWE per block of the data, in order, under the big compute key) and
+    what they hold."""
+
+    def __init__(self, expanded_blocks, data_info, message_modulus, carry_modulus):
+        self.expanded_blocks = expanded_blocks
+        self.data_info = list(data_info)
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+
+    def __len__(self):
+        return len(self.data_info)
+
+    def get_kind_of(self, i):
+        return self.data_info[i] if 0 <= i < len(self.data_info) else None
+
+    def get(self, i, streams):
+        """Entry i: an unsigned integer as a CudaUnsignedRadixCiphertext of its blocks (degree message_modulus - 1), a
+        boolean as one of a single block (degree 1); noise level nominal.  None past the end, as the reference."""
+        if not 0 <= i < len(self.data_info):
+            return None
+        blocks = CudaFlattenedVecCompactCiphertextList._blocks
+        start, count = sum(blocks(e) for e in self.data_info[:i]), blocks(self.data_info[i])
+        dim = self.expanded_blocks.lwe_dimension
+        w = (dim + 1) * 8
+        out = CudaUnsignedRadixCiphertext(CudaVec(count * (dim + 1), streams), 1, count, dim)
+        _lib().cuda_memcpy_async_gpu_to_gpu(out.d_blocks.ptr, self.expanded_blocks.d_vec.ptr + start * w, count * w,
+                                            streams.ptr[0], streams.gpu_indexes[0])
+        out.set_degrees(1 if self.data_info[i][0] == "boolean" else self.message_modulus - 1)
+        out.is_boolean = self.data_info[i][0] == "boolean"
+        return out
