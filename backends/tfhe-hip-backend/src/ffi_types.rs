@@ -42,6 +42,9 @@ pub const EXPAND_KIND_NO_CASTING: EXPAND_KIND = 0;
 pub const EXPAND_KIND_CASTING: EXPAND_KIND = 1;
 pub const EXPAND_KIND_SANITY_CHECK: EXPAND_KIND = 2;
 pub type EXPAND_KIND = ffi::c_uint;
+pub const RERAND_MODE_RERAND_WITH_KS: RERAND_MODE = 0;
+pub const RERAND_MODE_RERAND_WITHOUT_KS: RERAND_MODE = 1;
+pub type RERAND_MODE = ffi::c_uint;
 
 #[repr(C)]
 #[derive(Debug, Copy, Clone)]

@@ -50,6 +50,8 @@ enum COMPARISON_TYPE { EQ = 0, NE = 1, GT = 2, GE = 3, LT = 4, LE = 5, MAX = 6, 
 /* cuda/include/keyswitch/ks_enums.h, cuda/include/zk/zk_enums.h */
 enum KS_TYPE { BIG_TO_SMALL = 0, SMALL_TO_BIG = 1 };
 enum EXPAND_KIND { NO_CASTING = 0, CASTING = 1, SANITY_CHECK = 2 };
+/* cuda/include/integer/integer.h:45-48 */
+enum RERAND_MODE { RERAND_WITH_KS = 0, RERAND_WITHOUT_KS = 1 };
 
 /* ------------------------------------------------------------------ device runtime
  * backends/tfhe-cuda-common/cuda/include/device.h:58-92 (cuda_bind.rs:5-150) */
@@ -797,6 +799,65 @@ void hip_expand_without_verification_64_async(
     CudaStreamsFFI streams, void *lwe_array_out, const void *lwe_flattened_compact_array_in, int8_t *mem_ptr,
     void *const *bsks, void *const *computing_ksks, void *const *casting_keys);
 void hip_cleanup_expand_without_verification_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+
+/* ------------------------------------------------------------------ re-randomisation (extensions)
+ * cuda/include/integer/rerand.h:6-19 (scratch_cuda_rerand_64_async, cuda_rerand_64_async, cleanup_cuda_rerand_64; caller:
+ * tfhe/src/integer/gpu/ciphertext/re_randomization.rs), under hip_ names with the reference's parameter lists.  The
+ * reference-named symbols remain link stubs.
+ *
+ * Block o < lwe_ciphertext_count of lwe_array gains, in place, a fresh encryption of zero: body o of ONE compact list
+ * (n mask words, then at least lwe_ciphertext_count body words, on the device; n = ksk_params.input_lwe_dimension, any
+ * n >= 1), expanded to (mask * X^o in Z[X]/(X^n + 1), body o).
+ *   RERAND_WITHOUT_KS: the blocks are under the list's key (rows of n + 1 words).  One kernel rotates the mask and adds
+ *                      in place: no temporary, every row read once and written once.  The other three fields of
+ *                      ksk_params are not read; ksk may be null; the scratch holds nothing on the device.
+ *   RERAND_WITH_KS:    the blocks are under ksk_params.output_lwe_dimension (the reference files this dimension as the
+ *                      "small" one of its radix parameters, cuda/src/integer/rerand.cu:12-16, although it is the compute
+ *                      key's).  The zeros are expanded into the scratch, keyswitched with ksk[0] and added.
+ * Everything runs on the first stream of the set; a launch copies nothing to the device, allocates nothing and does not
+ * synchronise.  message_modulus and carry_modulus are part of the reference's list and only validated.
+ * Panics: lwe_ciphertext_count 0 or above n (one list has one mask), an unknown mode, a launch on a scratch created with
+ * allocate_gpu_memory = false or on a scratch of another kind, RERAND_WITH_KS with a null ksk. */
+uint64_t hip_scratch_rerand_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                     CudaLweKeyswitchKeyParamsFFI ksk_params,
+                                     uint32_t lwe_ciphertext_count,
+                                     uint32_t message_modulus,
+                                     uint32_t carry_modulus,
+                                     bool allocate_gpu_memory,
+                                     enum RERAND_MODE rerand_type);
+void hip_rerand_64_async(
+    CudaStreamsFFI streams, void *lwe_array,
+    const void *lwe_flattened_encryptions_of_zero_compact_array_in,
+    int8_t *mem_ptr, void *const *ksk);
+void hip_cleanup_rerand_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+
+/* ------------------------------------------------------------------ oblivious pseudo-random bits (extensions)
+ * cuda/include/integer/integer.h:664-678 (scratch_cuda_integer_grouped_oprf_64_async, cuda_integer_grouped_oprf_64_async,
+ * cleanup_cuda_integer_grouped_oprf_64; tfhe/src/shortint/oprf.rs), under hip_ names with the reference's parameter lists.
+ * The reference-named symbols remain link stubs, and so do the custom-range OPRF and the bitonic shuffle.
+ *
+ * seeded_lwe_input: num_blocks_to_process LWEs of dimension bsk_params.input_lwe_dimension on the device, their words
+ * derived from a seed by the caller and already multiples of 2^64 / (2 * polynomial_size).  They are bootstrapped as they
+ * are — no keyswitch; ksk_params takes no part, as in the reference — with the table of their bit count b (coefficient x
+ * holds (2 * (x / (2N / 2^b)) + 1) * delta / 2, delta = 2^(63 - log2 carry - log2 message), no input encoding), and
+ * (2^b - 1) * delta / 2 is added to the body: block i of radix_lwe_out then holds b uniform bits, b = log2 message_modulus
+ * for every block but the last, which takes what remains of total_random_bits.  Degrees are set to 2^b - 1, noise levels
+ * to nominal.  Classic and multi-bit keys; the bootstrap is a round of the radix layer and shards over the stream set.
+ * Panics: num_blocks_to_process != ceil(total_random_bits / log2 message_modulus), moduli that are no powers of two, a
+ * launch with another block count than the scratch's, on a size-only scratch or on a scratch of another kind. */
+uint64_t hip_scratch_integer_grouped_oprf_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks_to_process,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    uint32_t total_random_bits, enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_grouped_oprf_64_async(CudaStreamsFFI streams,
+                                       CudaRadixCiphertextFFI *radix_lwe_out,
+                                       const void *seeded_lwe_input,
+                                       uint32_t num_blocks_to_process,
+                                       int8_t *mem, void *const *bsks);
+void hip_cleanup_integer_grouped_oprf_64(CudaStreamsFFI streams,
+                                         int8_t **mem_ptr_void);
 
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's

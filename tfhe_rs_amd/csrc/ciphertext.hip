@@ -241,6 +241,52 @@ void launch_lwe_expand(hipStream_t st, uint64_t *lwe_out, const uint64_t *flatte
             flattened_in, jobs, n_c);
 }
 
+// ------------------------------------------------------------------ re-randomisation: rotate and add in place
+// Block o of lwe_array gains body o of ONE compact list of encryptions of zero, expanded on the fly (rerand.cuh expands
+// into a temporary, then adds: the row moves four times; here it is read once and written once):
+//   row[e] += zeros[e - o]          for o <= e < n
+//   row[e] -= zeros[e - o + n]      for e < o
+//   row[n] += zeros[n + o]
+// A re-randomisation reads one list and block o takes rotation o, so there is no job table.  Grid and lane layout of
+// lwe_expand_kernel: x = row, y = chunk of kExpandChunk words, 8-byte accesses (rows start off a 16-byte boundary every
+// other row), the loads of a lane's four words, row and mask, issued before its stores.  No LDS.
+__global__ void __launch_bounds__(kExpandThreads) lwe_rerand_add_kernel(uint64_t *__restrict__ lwe_array,
+                                                                        const uint64_t *__restrict__ zeros, uint32_t n) {
+  const uint32_t d = blockIdx.x, first = blockIdx.y * kExpandChunk + threadIdx.x;
+  uint64_t *row = lwe_array + (size_t)blockIdx.x * ((size_t)n + 1);
+  // Every lane loads: a lane past the row's end reads the body word again (index clamped to n) and stores nothing, so the
+  // eight loads carry no branch and are all in flight before the first add.
+  uint64_t r[kExpandWordsPerThread], z[kExpandWordsPerThread];
+  HX_UNROLL
+  for (uint32_t u = 0; u < kExpandWordsPerThread; ++u) {
+    const uint32_t e = first + u * kExpandThreads, ec = e < n ? e : n;
+    r[u] = row[ec];
+    z[u] = zeros[ec == n ? (size_t)n + d : (size_t)(ec < d ? ec + n - d : ec - d)];
+  }
+  HX_UNROLL
+  for (uint32_t u = 0; u < kExpandWordsPerThread; ++u) {
+    const uint32_t e = first + u * kExpandThreads;
+    if (e <= n) row[e] = r[u] + (e < d ? (uint64_t)0 - z[u] : z[u]);
+  }
+}
+void launch_lwe_rerand_add(hipStream_t st, uint64_t *lwe_array, const uint64_t *zeros, uint32_t n, uint32_t count) {
+  if (!count) return;
+  HX_LAUNCH(lwe_rerand_add_kernel, dim3(count, (n + kExpandChunk) / kExpandChunk), dim3(kExpandThreads), 0, st, lwe_array,
+            zeros, n);
+}
+
+// out[i] += in[i] over `words` words (the row add behind the keyswitch of a re-randomisation: rows of both sides are
+// dense and equally long, so the rows need not be told apart)
+__global__ void __launch_bounds__(256) lwe_add_rows_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ in,
+                                                           size_t words) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < words) out[i] += in[i];
+}
+void launch_lwe_add_rows(hipStream_t st, uint64_t *out, const uint64_t *in, uint32_t words_per_row, uint32_t count) {
+  const size_t words = (size_t)words_per_row * count;
+  if (words) HX_LAUNCH(lwe_add_rows_kernel, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, st, out, in, words);
+}
+
 __global__ void iota_u64_kernel(uint64_t *out, uint32_t count) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) out[i] = i;

@@ -231,6 +231,8 @@ struct LutDriver {
   uint32_t cap = 0, num_luts = 0, many_max = 1;
   uint32_t in_n = 0;  // LWE dimension of a round's inputs, the keyswitch key's input dimension: p.big_n, unless the key
                       // casts from another key (compact-list expansion)
+  bool no_ks = false;  // the round bootstraps its inputs as they are (dimension in_n = p.small_n): no keyswitch, no
+                       // keyswitch key (oblivious random bits)
   struct PerGpu {
     uint32_t gpu = 0;
     uint64_t *d_ks = nullptr, *d_luts = nullptr, *d_trivial = nullptr;  // d_trivial = 0, 1, ..., cap - 1
@@ -255,13 +257,15 @@ struct LutDriver {
 
   // max_many: the most functions one round extracts per bootstrap (sizes the dense output buffers)
   void init(const CudaStreamsFFI &s, const Params &params, uint32_t capacity,
-            const std::vector<std::vector<uint64_t>> &luts, uint32_t max_many = 1, uint32_t input_n = 0) {
+            const std::vector<std::vector<uint64_t>> &luts, uint32_t max_many = 1, uint32_t input_n = 0,
+            bool skip_keyswitch = false) {
     HX_PANIC_IF_FALSE(s.gpu_count >= 1 && s.streams != nullptr, "radix layer: empty stream set");
     p = params;
     cap = capacity;
     many_max = std::max(1u, max_many);
     num_luts = (uint32_t)luts.size();
-    in_n = input_n ? input_n : p.big_n;
+    no_ks = skip_keyswitch;
+    in_n = no_ks ? p.small_n : input_n ? input_n : p.big_n;
     const size_t lw = (size_t)(p.k + 1) * p.N, w = (size_t)p.big_n + 1, wi = (size_t)in_n + 1;
     std::vector<uint64_t> triv(cap);
     for (uint32_t i = 0; i < cap; ++i) triv[i] = i;
@@ -271,7 +275,7 @@ struct LutDriver {
       g.gpu = s.gpu_indexes ? s.gpu_indexes[i] : 0;
       const hipStream_t st = (hipStream_t)s.streams[i];
       HX_CHECK(hipSetDevice((int)g.gpu));
-      radix_alloc((void **)&g.d_ks, (size_t)cap * (p.small_n + 1) * sizeof(uint64_t));
+      if (!no_ks) radix_alloc((void **)&g.d_ks, (size_t)cap * (p.small_n + 1) * sizeof(uint64_t));
       radix_alloc((void **)&g.d_luts, std::max<size_t>(1, num_luts) * lw * sizeof(uint64_t));
       for (uint32_t t = 0; t < num_luts && !t_dry; ++t)
         HX_CHECK(hipMemcpyAsync(g.d_luts + t * lw, luts[t].data(), lw * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -309,18 +313,21 @@ struct LutDriver {
   void ks_pbs(hipStream_t st, const PerGpu &g, uint64_t *out, const uint64_t *out_idx, const uint64_t *in,
               const uint64_t *in_idx, const uint64_t *lut_idx, uint32_t c, const void *ksk, const void *bsk,
               uint32_t many = 1, uint32_t stride = 0) const {
-    {
+    const uint64_t *small = g.d_ks, *small_idx = g.d_trivial;
+    if (no_ks) {
+      small = in, small_idx = in_idx;
+    } else {
       HX_RANGE("keyswitch (%u blocks, gpu %u)", c, g.gpu);
       cuda_keyswitch_lwe_ciphertext_vector_64_64_async(st, g.gpu, g.d_ks, g.d_trivial, in, in_idx, ksk, in_n, p.small_n,
                                                        p.ks_base_log, p.ks_level, c);
     }
     HX_RANGE("bootstrap (%u blocks, %u functions, gpu %u)", c, many, g.gpu);
     if (p.grouping)
-      cuda_multi_bit_programmable_bootstrap_64_async(st, g.gpu, out, out_idx, g.d_luts, lut_idx, g.d_ks, g.d_trivial, bsk,
+      cuda_multi_bit_programmable_bootstrap_64_async(st, g.gpu, out, out_idx, g.d_luts, lut_idx, small, small_idx, bsk,
                                                      g.pbs_buf, p.small_n, p.k, p.N, p.grouping, p.pbs_base_log,
                                                      p.pbs_level, c, many, stride);
     else
-      cuda_programmable_bootstrap_64_async(st, g.gpu, out, out_idx, g.d_luts, lut_idx, g.d_ks, g.d_trivial, bsk, g.pbs_buf,
+      cuda_programmable_bootstrap_64_async(st, g.gpu, out, out_idx, g.d_luts, lut_idx, small, small_idx, bsk, g.pbs_buf,
                                            p.small_n, p.k, p.N, p.pbs_base_log, p.pbs_level, c, many, stride);
   }
 
@@ -357,6 +364,8 @@ struct LutDriver {
                       "radix layer: a round of %u functions per bootstrap on a driver created for %u", many, many_max);
     const uint32_t avail = std::min<uint32_t>(s.gpu_count, (uint32_t)gpus.size());
     const hipStream_t st0 = (hipStream_t)s.streams[0];
+    HX_PANIC_IF_FALSE(no_ks || ksks != nullptr, "radix layer: null keyswitch key array");
+    const auto ksk_of = [&](uint32_t i) -> const void * { return no_ks ? nullptr : ksks[i]; };
     HX_RANGE("apply lut round (%u blocks)", count);  // integer.cuh:874
     for (uint32_t off = 0; off < count; off += cap) {
       const uint32_t c = std::min(cap, count - off);
@@ -397,7 +406,7 @@ struct LutDriver {
           HX_CHECK(hipMemcpyAsync(g.d_in, h_in(g), in_bytes, hipMemcpyHostToDevice, sti));
           HX_CHECK(hipMemcpyAsync(g.d_lut_idx, h_idx(g), idx_bytes, hipMemcpyHostToDevice, sti));
         }
-        ks_pbs(sti, g, g.d_out, g.d_trivial, g.d_in, g.d_trivial, g.d_lut_idx, ci, ksks[i], bsks[i], many, stride);
+        ks_pbs(sti, g, g.d_out, g.d_trivial, g.d_in, g.d_trivial, g.d_lut_idx, ci, ksk_of(i), bsks[i], many, stride);
         if (g.direct) HX_CHECK(hipMemcpyPeerAsync(g.d0_out, (int)gpus[0].gpu, g.d_out, (int)g.gpu, out_bytes, sti));
         else HX_CHECK(hipMemcpyAsync(h_out(g), g.d_out, out_bytes, hipMemcpyDeviceToHost, sti));  // second leg below, on st0
         HX_CHECK(hipEventRecord(g.done, sti));
@@ -407,10 +416,10 @@ struct LutDriver {
       HX_CHECK(hipSetDevice((int)gpus[0].gpu));
       if (many == 1) {
         ks_pbs(st0, gpus[0], out0, oi ? oi : gpus[0].d_trivial, in0, ii ? ii : gpus[0].d_trivial, lut_idx + off, first,
-               ksks[0], bsks[0]);
+               ksk_of(0), bsks[0]);
       } else {
         ks_pbs(st0, gpus[0], gpus[0].d_many, gpus[0].d_trivial, in0, ii ? ii : gpus[0].d_trivial, lut_idx + off, first,
-               ksks[0], bsks[0], many, stride);
+               ksk_of(0), bsks[0], many, stride);
         for (uint32_t t = 0; t < many; ++t)
           axpy(st0, out, out_idx + (size_t)t * count + off, gpus[0].d_many + (size_t)t * first * w, nullptr, 1, nullptr,
                nullptr, (uint32_t)w, first);
@@ -1634,6 +1643,40 @@ struct ExpandMem : ScratchHeader {
   void release(const CudaStreamsFFI &s) {
     if (has_drv) drv.release(s);
     for (void *d : {(void *)d_jobs, (void *)d_expanded, (void *)d_cast, (void *)d_in_idx, (void *)d_out_idx, (void *)d_lut_idx})
+      if (d) scratch_free(d);
+  }
+};
+
+// Re-randomisation (cuda/include/integer/rerand_utilities.h int_rerand_mem, cuda/src/integer/rerand.cuh): every block
+// gains a fresh encryption of zero out of ONE compact list.  Without keyswitch the list is under the blocks' own key and
+// the scratch holds nothing on the device: launch_lwe_rerand_add rotates and adds in place.  With keyswitch the zeros are
+// expanded (launch_lwe_expand with the identity job table built here), keyswitched to the blocks' key and added.
+struct RerandMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x52524E44;  // "RRND"
+  uint32_t mode = 0;                               // RERAND_MODE
+  uint32_t n_in = 0, n_out = 0, base_log = 0, level = 0;  // zeros' dimension; with keyswitch: the blocks' and the key's shape
+  uint32_t count = 0, gpu = 0;
+  ExpandJob *d_jobs = nullptr;  // row o: the list's mask (offset 0) times X^o
+  uint64_t *d_expanded = nullptr, *d_switched = nullptr, *d_trivial = nullptr;
+  void release(const CudaStreamsFFI &) {
+    for (void *d : {(void *)d_jobs, (void *)d_expanded, (void *)d_switched, (void *)d_trivial})
+      if (d) scratch_free(d);
+  }
+};
+
+// Oblivious pseudo-random bits (cuda/include/integer/oprf.h int_grouped_oprf_memory, cuda/src/integer/oprf.cuh;
+// tfhe/src/shortint/oprf.rs generate_oprf_lut): seeded LWEs under the small key are bootstrapped as they are — no
+// keyswitch — with the table of their bit count, and a plaintext correction lands on the bodies.
+struct OprfMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x4F505246;  // "OPRF"
+  uint32_t num_blocks = 0, gpu = 0;
+  LutDriver drv;                      // no_ks: one table per bit count b = 1 .. message bits, table b - 1
+  std::vector<uint32_t> bits;         // per block: the random bits it takes
+  uint64_t *d_lut_idx = nullptr;      // per block: bits - 1
+  uint64_t *d_corrections = nullptr;  // per block: (2^bits - 1) * delta / 2, added to the body
+  void release(const CudaStreamsFFI &s) {
+    drv.release(s);
+    for (uint64_t *d : {d_lut_idx, d_corrections})
       if (d) scratch_free(d);
   }
 };
@@ -3291,6 +3334,155 @@ void hip_expand_without_verification_64_async(CudaStreamsFFI streams, void *lwe_
 
 void hip_cleanup_expand_without_verification_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
   scratch_destroy<ExpandMem>(streams, mem_ptr_void, "cleanup expand_without_verification");
+}
+
+// ---- cuda/include/integer/rerand.h:6-19, under hip_ names (the reference-named symbols stay link stubs) --------------
+// The zeros are ONE compact list under a key of dimension ksk_params.input_lwe_dimension.  RERAND_WITHOUT_KS: the blocks
+// are under that key too; the other three fields of ksk_params are not read (the reference's caller passes zeros).
+// RERAND_WITH_KS: the blocks are under ksk_params.output_lwe_dimension — the reference files the two dimensions as
+// "big" and "small" of its radix parameters (rerand.cu:12-16), whatever their order: "small" here is the compute key's
+// dimension, usually the larger one.
+uint64_t hip_scratch_rerand_64_async(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweKeyswitchKeyParamsFFI ksk_params,
+                                     uint32_t lwe_ciphertext_count, uint32_t message_modulus, uint32_t carry_modulus,
+                                     bool allocate_gpu_memory, enum RERAND_MODE rerand_type) {
+  const char *who = "rerand";
+  const uint32_t mode = (uint32_t)rerand_type, n_in = ksk_params.input_lwe_dimension, count = lwe_ciphertext_count;
+  HX_PANIC_IF_FALSE(mode == RERAND_WITH_KS || mode == RERAND_WITHOUT_KS, "%s: unknown re-randomisation mode %u", who, mode);
+  HX_PANIC_IF_FALSE(message_modulus >= 2 && carry_modulus >= 1, "%s: unsupported message/carry moduli (%u, %u)", who,
+                    message_modulus, carry_modulus);
+  HX_PANIC_IF_FALSE(n_in >= 1 && n_in <= kExpandMaxDimension, "%s: unsupported dimension %u of the encryptions of zero", who,
+                    n_in);
+  HX_PANIC_IF_FALSE(count >= 1, "%s: no ciphertext to re-randomise (lwe_ciphertext_count is 0)", who);
+  HX_PANIC_IF_FALSE(count <= n_in,
+                    "%s: %u ciphertexts, one compact list of encryptions of zero holds 1 .. %u bodies (its dimension)", who,
+                    count, n_in);
+  if (mode == RERAND_WITH_KS)
+    HX_PANIC_IF_FALSE(ksk_params.output_lwe_dimension >= 1 && ksk_params.level_count >= 1 && ksk_params.base_log >= 1,
+                      "%s: RERAND_WITH_KS needs the keyswitch key's output dimension and decomposition", who);
+  return scratch_create<RerandMem>(streams, mem_ptr, allocate_gpu_memory, who, [&](RerandMem &m) {
+    m.mode = mode, m.n_in = n_in, m.count = count, m.gpu = G0(streams);
+    if (mode == RERAND_WITHOUT_KS) return;  // rotate and add in place: nothing on the device
+    const hipStream_t st = S0(streams);
+    m.n_out = ksk_params.output_lwe_dimension, m.base_log = ksk_params.base_log, m.level = ksk_params.level_count;
+    std::vector<ExpandJob> jobs(count);
+    std::vector<uint64_t> triv(count);
+    for (uint32_t o = 0; o < count; ++o) jobs[o] = ExpandJob{0, o, 0}, triv[o] = o;
+    m.d_jobs = dev_upload(st, jobs);
+    m.d_trivial = dev_upload(st, triv);
+    radix_alloc((void **)&m.d_expanded, (size_t)count * ((size_t)n_in + 1) * sizeof(uint64_t));
+    radix_alloc((void **)&m.d_switched, (size_t)count * ((size_t)m.n_out + 1) * sizeof(uint64_t));
+  });
+}
+
+void hip_rerand_64_async(CudaStreamsFFI streams, void *lwe_array,
+                         const void *lwe_flattened_encryptions_of_zero_compact_array_in, int8_t *mem_ptr,
+                         void *const *ksk) {
+  first_gpu(streams);
+  auto *m = scratch_use<RerandMem>(mem_ptr, "rerand");
+  HX_PANIC_IF_FALSE(lwe_array != nullptr && lwe_flattened_encryptions_of_zero_compact_array_in != nullptr,
+                    "rerand: null pointer");
+  const hipStream_t st = S0(streams);
+  const uint64_t *zeros = (const uint64_t *)lwe_flattened_encryptions_of_zero_compact_array_in;
+  if (m->mode == RERAND_WITHOUT_KS) {
+    HX_RANGE("rerand: rotate and add (%u blocks)", m->count);
+    launch_lwe_rerand_add(st, (uint64_t *)lwe_array, zeros, m->n_in, m->count);
+    return;
+  }
+  HX_PANIC_IF_FALSE(ksk != nullptr && ksk[0] != nullptr, "rerand: RERAND_WITH_KS without a keyswitch key (null pointer)");
+  {
+    HX_RANGE("rerand: expand (%u zeros)", m->count);
+    launch_lwe_expand(st, m->d_expanded, zeros, m->d_jobs, m->n_in, m->count);
+  }
+  {
+    HX_RANGE("rerand: keyswitch (%u zeros)", m->count);
+    cuda_keyswitch_lwe_ciphertext_vector_64_64_async(st, m->gpu, m->d_switched, m->d_trivial, m->d_expanded, m->d_trivial,
+                                                     ksk[0], m->n_in, m->n_out, m->base_log, m->level, m->count);
+  }
+  HX_RANGE("rerand: add (%u blocks)", m->count);
+  launch_lwe_add_rows(st, (uint64_t *)lwe_array, m->d_switched, m->n_out + 1, m->count);
+}
+
+void hip_cleanup_rerand_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<RerandMem>(streams, mem_ptr_void, "cleanup rerand");
+}
+
+// ---- cuda/include/integer/integer.h:664-678, under hip_ names (the reference-named symbols stay link stubs) ----------
+// ksk_params is part of the reference's parameter list and, as there, takes no part: no keyswitch runs.
+uint64_t hip_scratch_integer_grouped_oprf_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                                   CudaLweBootstrapKeyParamsFFI bsk_params,
+                                                   CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks_to_process,
+                                                   uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+                                                   uint32_t total_random_bits, enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const char *who = "integer_grouped_oprf";
+  (void)ksk_params;
+  HX_PANIC_IF_FALSE(message_modulus >= 2 && (message_modulus & (message_modulus - 1)) == 0 && carry_modulus >= 1 &&
+                        (carry_modulus & (carry_modulus - 1)) == 0,
+                    "%s: message and carry moduli must be powers of two (got %u, %u)", who, message_modulus, carry_modulus);
+  uint32_t message_bits = 0, carry_bits = 0;
+  while ((1u << (message_bits + 1)) <= message_modulus) ++message_bits;
+  while ((1u << (carry_bits + 1)) <= carry_modulus) ++carry_bits;
+  // oprf.h:27-34
+  const uint32_t wanted = (total_random_bits + message_bits - 1) / message_bits;
+  HX_PANIC_IF_FALSE(num_blocks_to_process >= 1 && num_blocks_to_process == wanted,
+                    "%s: num_blocks_to_process (%u) should be equal to ceil(total_random_bits / message bits) = ceil(%u / %u) "
+                    "= %u",
+                    who, num_blocks_to_process, total_random_bits, message_bits, wanted);
+  // no keyswitch in front of this bootstrap: the key parameters below only restate the bootstrap's own dimensions
+  const CudaLweKeyswitchKeyParamsFFI no_ks{bsk_params.glwe_dimension * bsk_params.polynomial_size,
+                                           bsk_params.input_lwe_dimension, 1, 1};
+  const Params p = make_params(bsk_params, no_ks, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  HX_PANIC_IF_FALSE(2ull * p.N >= message_modulus, "%s: 2 * polynomial_size should not be smaller than the message modulus", who);
+  const uint64_t delta = (uint64_t)1 << (64 - 1 - carry_bits - message_bits);
+  return scratch_create<OprfMem>(streams, mem_ptr, allocate_gpu_memory, who, [&](OprfMem &m) {
+    const hipStream_t st = S0(streams);
+    m.num_blocks = num_blocks_to_process, m.gpu = G0(streams);
+    // oprf.rs generate_oprf_lut, integer.cuh generate_lookup_table_no_encoding: coefficient x of the body holds f(x)
+    std::vector<std::vector<uint64_t>> luts(message_bits, std::vector<uint64_t>((size_t)(p.k + 1) * p.N, 0));
+    for (uint32_t b = 1; b <= message_bits; ++b) {
+      const uint64_t poly_delta = 2ull * p.N >> b;
+      uint64_t *body = luts[b - 1].data() + (size_t)p.k * p.N;
+      for (uint32_t x = 0; x < p.N; ++x) body[x] = (2 * (x / poly_delta) + 1) * delta / 2;
+    }
+    std::vector<uint64_t> lut_idx(m.num_blocks), corrections(m.num_blocks);
+    m.bits.resize(m.num_blocks);
+    uint32_t processed = 0;
+    for (uint32_t i = 0; i < m.num_blocks; ++i) {
+      m.bits[i] = std::min(message_bits, total_random_bits - processed);
+      lut_idx[i] = m.bits[i] - 1;
+      corrections[i] = (((uint64_t)1 << m.bits[i]) - 1) * delta / 2;
+      processed += m.bits[i];
+    }
+    m.d_lut_idx = dev_upload(st, lut_idx);
+    m.d_corrections = dev_upload(st, corrections);
+    m.drv.init(streams, p, m.num_blocks, luts, 1, 0, true);
+  });
+}
+
+void hip_integer_grouped_oprf_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *radix_lwe_out,
+                                       const void *seeded_lwe_input, uint32_t num_blocks_to_process, int8_t *mem,
+                                       void *const *bsks) {
+  first_gpu(streams);
+  auto *m = scratch_use<OprfMem>(mem, "integer_grouped_oprf");
+  HX_PANIC_IF_FALSE(radix_lwe_out && radix_lwe_out->ptr && seeded_lwe_input && bsks && bsks[0],
+                    "integer_grouped_oprf: null pointer");
+  const Params &p = m->drv.p;
+  HX_PANIC_IF_FALSE(num_blocks_to_process == m->num_blocks,
+                    "integer_grouped_oprf: %u blocks to process on a scratch created for %u", num_blocks_to_process,
+                    m->num_blocks);
+  HX_PANIC_IF_FALSE(radix_lwe_out->lwe_dimension == p.big_n && radix_lwe_out->num_radix_blocks >= m->num_blocks,
+                    "integer_grouped_oprf: output of %u blocks of lwe dimension %u, the bootstrap writes %u blocks of %u",
+                    radix_lwe_out->num_radix_blocks, radix_lwe_out->lwe_dimension, m->num_blocks, p.big_n);
+  uint64_t *out = (uint64_t *)radix_lwe_out->ptr;
+  m->drv.round(streams, out, nullptr, (const uint64_t *)seeded_lwe_input, nullptr, m->d_lut_idx, m->num_blocks, nullptr,
+               bsks);
+  HX_LAUNCH(lwe_body_add_scalars_kernel, dim3((m->num_blocks + 255) / 256), dim3(256), 0, S0(streams), out, m->d_corrections,
+            p.big_n + 1, m->num_blocks, (uint64_t)1);
+  // oprf.cuh:82-86: the degree is p - 1, not the table's
+  for (uint32_t i = 0; i < m->num_blocks; ++i) set_block_info(radix_lwe_out, i, 1, ((uint64_t)1 << m->bits[i]) - 1, 1);
+}
+
+void hip_cleanup_integer_grouped_oprf_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<OprfMem>(streams, mem_ptr_void, "cleanup integer_grouped_oprf");
 }
 
 }  // extern "C"

@@ -120,6 +120,11 @@ struct ExpandJob {
 constexpr uint32_t kExpandMaxDimension = 1u << 25;  // the 1024-word row chunks of the largest n_c fit the grid's y extent
 void launch_lwe_expand(hipStream_t st, uint64_t *lwe_out, const uint64_t *flattened_in, const ExpandJob *jobs,
                        uint32_t n_c, uint32_t num_lwes);
+// re-randomisation, in place: block o < count of lwe_array (rows of n + 1 words) += the expansion of body o of ONE
+// compact list `zeros` (n mask words, then at least `count` bodies; count <= n); no temporary, no table
+void launch_lwe_rerand_add(hipStream_t st, uint64_t *lwe_array, const uint64_t *zeros, uint32_t n, uint32_t count);
+// out[i] += in[i] over count rows of words_per_row words, both dense
+void launch_lwe_add_rows(hipStream_t st, uint64_t *out, const uint64_t *in, uint32_t words_per_row, uint32_t count);
 
 // multi-bit — multibit.hip
 struct MultiBitArgs {

@@ -243,6 +243,13 @@ SIGNATURES = {
                 _u32, _u32, _u32, _u32, _b, _u32, _u32]),
     "hip_expand_without_verification_64_async": (None, [_S, _v, _v, _v, _i8pp, _i8pp, _i8pp]),
     "hip_cleanup_expand_without_verification_64": (None, [_S, _i8pp]),
+    # re-randomisation; oblivious pseudo-random bits
+    "hip_scratch_rerand_64_async": (_u64, [_S, _i8pp, _KK, _u32, _u32, _u32, _b, _u32]),
+    "hip_rerand_64_async": (None, [_S, _v, _v, _v, _i8pp]),
+    "hip_cleanup_rerand_64": (None, [_S, _i8pp]),
+    "hip_scratch_integer_grouped_oprf_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _b, _u32, _u32]),
+    "hip_integer_grouped_oprf_64_async": (None, [_S, _R, _v, _u32, _v, _i8pp]),
+    "hip_cleanup_integer_grouped_oprf_64": (None, [_S, _i8pp]),
     # 128-bit PBS and noise squashing
     "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
     "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),

@@ -23,6 +23,7 @@ PBS_TYPE_MULTI_BIT, PBS_TYPE_CLASSICAL = 0, 1          # pbs/pbs_enums.h:4
 OUTPUT_FLAG_NONE, OUTPUT_FLAG_OVERFLOW, OUTPUT_FLAG_CARRY = 0, 1, 2   # integer/integer.h:39
 KS_TYPE_BIG_TO_SMALL, KS_TYPE_SMALL_TO_BIG = 0, 1                      # keyswitch/ks_enums.h
 EXPAND_KIND = {"no_casting": 0, "casting": 1, "sanity_check": 2}       # zk/zk_enums.h
+RERAND_WITH_KS, RERAND_WITHOUT_KS = 0, 1                               # integer/integer.h:45
 
 
 class CudaServerKey:
@@ -434,6 +435,33 @@ class CudaUnsignedRadixCiphertext:
         return ffi.CudaRadixCiphertextFFI(self.d_blocks.ptr, deg.ctypes.data_as(C.POINTER(C.c_uint64)),
                                           noise.ctypes.data_as(C.POINTER(C.c_uint64)), self.total_blocks,
                                           self.total_blocks, self.lwe_dimension)
+
+    def re_randomize(self, zeros, key, streams):
+        """integer/gpu/ciphertext/re_randomization.rs re_randomize: every block gains, in place, a fresh encryption of
+        zero.  `zeros`: ONE compact list (CudaLweCompactCiphertextList) of at least total_blocks encryptions of zero under
+        the compact public key `key` (a CudaReRandomizationKey) stands for; deriving its words from a seed is the
+        caller's.  Blocks must be at nominal noise and stay there; degrees do not change."""
+        ksk = key.checked_rerand_ksk(self.lwe_dimension)
+        if len(zeros.num_lwe_per_compact_list) != 1 or zeros.n_c != key.zeros_dimension:
+            raise ValueError("Mismatched LweDimension between the encryptions of zero and the provided re-randomization "
+                             "key: one compact list under its compact public key is expected.")
+        if zeros.lwe_ciphertext_count < self.total_blocks:
+            raise ValueError("Not enough encryptions of zero to re-randomize every block.")
+        if int(self._info[1].max(initial=0)) > 1:
+            raise ValueError("Tried to re-randomize a Ciphertext with non-nominal NoiseLevel.")
+        s, keep = CudaServerKey._streams(streams)
+        if ksk is None:
+            params, mode, keys = ffi.CudaLweKeyswitchKeyParamsFFI(key.zeros_dimension, 0, 0, 0), RERAND_WITHOUT_KS, None
+        else:
+            params = ffi.CudaLweKeyswitchKeyParamsFFI(ksk.input_key_lwe_dimension, ksk.output_key_lwe_dimension,
+                                                      ksk.decomp_base_log, ksk.decomp_level_count)
+            mode, keys = RERAND_WITH_KS, (C.c_void_p * 1)(ksk.d_vecs[0].ptr)
+        mem = C.c_void_p()
+        _lib().hip_scratch_rerand_64_async(s, C.byref(mem), params, self.total_blocks, key.message_modulus,
+                                           key.carry_modulus, True, mode)
+        _lib().hip_rerand_64_async(s, self.d_blocks.ptr, zeros.d_vec.ptr, mem, keys)
+        _lib().hip_cleanup_rerand_64(s, C.byref(mem))
+        self._info[1][:] = 1
 
 
 # ---------------------------------------------------------------------------------------------- ciphertext compression
@@ -927,4 +955,74 @@ class CudaCompactCiphertextListExpander:
                                             streams.ptr[0], streams.gpu_indexes[0])
         out.set_degrees(1 if self.data_info[i][0] == "boolean" else self.message_modulus - 1)
         out.is_boolean = self.data_info[i][0] == "boolean"
+        return out
+
+
+# ---------------------------------------------------------------------------------------------- re-randomisation, OPRF
+# integer/gpu/ciphertext/re_randomization.rs (CudaReRandomizationKey) and integer/gpu/server_key/radix/oprf.rs
+# (CudaOprfServerKey), over the hip_ entry points of include/tfhe_hip_backend.h, "re-randomisation" and "oblivious
+# pseudo-random bits".  Deriving words from a seed (the XOF) is host work in the reference too: callers pass the words.
+class CudaReRandomizationKey:
+    """re_randomization.rs CudaReRandomizationKey: `zeros_dimension` is the LWE dimension of the compact public key the
+    encryptions of zero are made with.  With `ksk` (a CudaLweKeyswitchKey from that key to the blocks' key):
+    LegacyDedicatedCPK; without: DerivedCPKWithoutKeySwitch, the public key is derived from the compute key itself."""
+
+    def __init__(self, zeros_dimension, ksk=None, message_modulus=4, carry_modulus=4):
+        self.zeros_dimension, self.ksk = int(zeros_dimension), ksk
+        self.message_modulus, self.carry_modulus = int(message_modulus), int(carry_modulus)
+        if ksk is not None and ksk.input_key_lwe_dimension != self.zeros_dimension:
+            raise ValueError("Mismatched LweDimension between the provided CompactPublicKey and the re-randomization "
+                             "keyswitch key input.")
+
+    def checked_rerand_ksk(self, radix_block_lwe_dimension):
+        """re_randomization.rs:36-86: the keyswitch key (or None) once the dimensions are known to match; the backend
+        expands the zeros at that dimension, a mismatch would read out of bounds."""
+        if self.ksk is not None:
+            if self.ksk.output_key_lwe_dimension != radix_block_lwe_dimension:
+                raise ValueError("Mismatched LweSize between the ciphertext being re-randomized and the provided "
+                                 "re-randomization keyswitch key output.")
+            return self.ksk
+        if self.zeros_dimension != radix_block_lwe_dimension:
+            raise ValueError("Mismatched LweSize between the ciphertext being re-randomized and the provided "
+                             "CompactPublicKey.")
+        return None
+
+
+class CudaOprfServerKey:
+    """oprf.rs: the bootstrap key of the oblivious pseudo-random function, from the key the seeded LWEs are read under
+    (the small compute key) to the big compute key — a CudaLweBootstrapKey or CudaLweMultiBitBootstrapKey."""
+
+    def __init__(self, bsk):
+        self.bootstrapping_key = bsk
+
+    def generate_oblivious_pseudo_random_bits(self, seeded_lwes, total_random_bits, server_key, streams, rerand=None):
+        """`seeded_lwes`: [blocks][input dimension + 1] words derived from a seed, multiples of 2^64 / 2N, blocks =
+        ceil(total_random_bits / message bits).  Returns one radix integer whose blocks hold the random bits (the last
+        block what remains), degrees 2^bits - 1, nominal noise.  `rerand`: (zeros, CudaReRandomizationKey) to
+        re-randomise the fresh blocks, as the reference's OPRF can."""
+        b = self.bootstrapping_key
+        g = getattr(b, "grouping_factor", 0)
+        seeded = np.ascontiguousarray(seeded_lwes, dtype=U64)
+        assert seeded.ndim == 2 and seeded.shape[1] == b.input_lwe_dimension + 1, \
+            "seeded LWEs do not have the OPRF key's input dimension"
+        blocks = seeded.shape[0]
+        bk = ffi.CudaLweBootstrapKeyParamsFFI(b.input_lwe_dimension, b.glwe_dimension, b.polynomial_size, b.decomp_base_log,
+                                              b.decomp_level_count, b.output_lwe_dimension,
+                                              PBS_TYPE_MULTI_BIT if g else PBS_TYPE_CLASSICAL, g)
+        s, keep = CudaServerKey._streams(streams)
+        n = len(streams)
+        assert len(b.d_vecs) >= n, "OPRF key has fewer GPU replicas than the stream set has streams"
+        bsks = (C.c_void_p * n)(*[v.ptr for v in b.d_vecs[:n]])
+        d_in = CudaVec.from_cpu_async(seeded.reshape(-1), streams)
+        out = CudaUnsignedRadixCiphertext(CudaVec(blocks * (b.output_lwe_dimension + 1), streams), 1, blocks,
+                                          b.output_lwe_dimension)
+        mem = C.c_void_p()
+        _lib().hip_scratch_integer_grouped_oprf_64_async(
+            s, C.byref(mem), bk, server_key._ksk_params(), blocks, server_key.message_modulus, server_key.carry_modulus,
+            True, int(total_random_bits), 1 if getattr(b, "ms_noise_reduction", False) else 0)
+        _lib().hip_integer_grouped_oprf_64_async(s, C.byref(out._ffi()), d_in.ptr, blocks, mem, bsks)
+        _lib().hip_cleanup_integer_grouped_oprf_64(s, C.byref(mem))
+        if rerand is not None:
+            zeros, key = rerand
+            out.re_randomize(zeros, key, streams)
         return out
