@@ -16,7 +16,7 @@ BACKENDS = [pytest.param("emu", id="emu"), pytest.param("hip", id="hip", marks=p
 MSG = 4  # message_modulus = carry_modulus = 4
 
 
-def setup(kind, p=None, gpu_indexes=(0,), msg=MSG):
+def setup(kind, p=None, gpu_indexes=(0,), msg=MSG, carry=None):
     from tfhe_rs_amd import core_crypto_gpu as gpu
     from tfhe_rs_amd import integer_gpu as igpu
     use_backend(kind)
@@ -30,7 +30,7 @@ def setup(kind, p=None, gpu_indexes=(0,), msg=MSG):
     else:
         bsk = gpu.CudaLweBootstrapKey.from_lwe_bootstrap_key(keys.bsk, p.n, p.k, p.N, p.pbs_base_log, p.pbs_level, st,
                                                              ms_noise_reduction=bool(p.ms_type))
-    return p, keys, st, igpu.CudaServerKey(ksk, bsk, msg, msg), igpu
+    return p, keys, st, igpu.CudaServerKey(ksk, bsk, msg, msg if carry is None else carry), igpu
 
 
 def encrypt_radix(p, keys, values, num_blocks, seed, msg=MSG):
