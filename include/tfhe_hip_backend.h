@@ -1023,6 +1023,15 @@ uint32_t hip_backend_last_keyswitch_path(void);
 /* small-batch keyswitch (<= 32 LWEs): workgroups per column tile that share the K dimension (default 8; 1 = one
  * workgroup per column tile, no atomics).  Identical bits. */
 void hip_backend_set_keyswitch_kparts(uint32_t parts);
+/* the kernel form the last keyswitch (64- or 32-bit key) launched, for tests: out[0] the path above (the 64->32 entry point
+ * records it too), out[1] the scalar kernel (1 small-base, 2 int32 digits, 3 int64 digits, 4 the 64->32 kernel; 0 on the
+ * matrix-core paths), out[2] the compile-time level count of the one-launch or the digit kernel (1, 2, 4, 8, 16; 0: neither
+ * ran), out[3] 1 when that form pads the level count, out[4] the key width in bits, out[5] the one-launch kernel's split of
+ * K over the waves of a workgroup (4 or 1; 0: it did not run), out[6] the workgroups per column tile it ran with,
+ * out[7] the GEMM's steps per barrier (1, 2, 4; 0: no GEMM ran) + 256 * the column tiles of the matrix-core launch */
+void hip_backend_last_keyswitch_instantiation(uint32_t *out8);
+/* keys whose matrix-core layout is cached at the moment (at most 32: the least recently used one goes), for tests */
+uint32_t hip_backend_keyswitch_cache_entries(void);
 const char *hip_backend_version(void);
 
 /* HIP events recorded on a backend stream (used by bench.py to time launches) */

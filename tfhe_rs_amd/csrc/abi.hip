@@ -1100,6 +1100,8 @@ void hip_backend_last_pbs_instantiation(uint32_t *out8) {
 }
 uint32_t hip_backend_last_keyswitch_path(void) { return keyswitch_last_path(); }
 void hip_backend_set_keyswitch_kparts(uint32_t parts) { keyswitch_set_kparts(parts); }
+void hip_backend_last_keyswitch_instantiation(uint32_t *out8) { keyswitch_last_instantiation(out8); }
+uint32_t hip_backend_keyswitch_cache_entries(void) { return (uint32_t)ksm_cache_entries(); }
 const char *hip_backend_version(void) {
 #if defined(TFHE_HIPEMU)
   return "tfhe-hip-backend 0.1 (HOST EMULATION - test build, not a product)";

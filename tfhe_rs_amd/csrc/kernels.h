@@ -68,6 +68,8 @@ size_t ksm_cache_entries();
 void keyswitch_select_kernel(uint32_t which);
 uint32_t keyswitch_last_path();  // 0 scalar kernels, 1 one-launch matrix-core kernel, 2 digit pass + GEMM, 3 GEMM on emitted digits
 void keyswitch_set_kparts(uint32_t parts);
+// the kernel form the last keyswitch launched, as hip_backend_last_keyswitch_instantiation documents it
+void keyswitch_last_instantiation(uint32_t out8[8]);
 bool keyswitch_batch_takes_gemm(uint32_t num_samples);  // a batch of this size takes the GEMM path (emitted digits pay off)
 void ksd_release_stream(int device, hipStream_t st);  // the large-batch keyswitch's per-stream scratch
 extern bool g_ntt_kernel_serial;

@@ -609,15 +609,49 @@ __global__ void __launch_bounds__(256, 2) ks_gemm_kernel(OutT *lwe_out, const ui
   ksm_epilogue(acc, [suma](int, uint32_t so) { return (int64_t)suma[so]; }, 0u, 1u, lane_e, lwe_out, out_idx, lwe_in, in_idx,
                colsum, n_in, n_out, base_log, num_samples, ct, stile);
 }
+
+// test hook behind hip_backend_last_keyswitch_instantiation: which kernel form the last keyswitch launched.  The host launch
+// code notes it as it launches (an entry point clears the record, the launchers fill in their words); nothing of it reaches
+// a kernel
+enum KsInstWord : int {
+  KS_INST_SCALAR = 1,  // the scalar kernel: KsScalarKernel, 0 on the matrix-core paths
+  KS_INST_LEVEL = 2,   // compile-time LEVEL of ks_mfma_kernel / ks_digits_kernel (0: neither ran)
+  KS_INST_PADDED = 3,  // its PADDED
+  KS_INST_BITS = 4,    // key (and output) width in bits
+  KS_INST_KSPLIT = 5,  // ks_mfma_kernel's KSPLIT, 1 or 4 (0: it did not run)
+  KS_INST_KPARTS = 6,  // the workgroups per column tile it was launched with
+  KS_INST_GEMM = 7,    // ks_gemm_kernel's SPB (0: no GEMM ran) + 256 * column tiles of the matrix-core launch
+};
+enum KsScalarKernel : uint32_t { KS_SCALAR_SMALL_BASE = 1, KS_SCALAR_DIGITS32 = 2, KS_SCALAR_DIGITS64 = 3, KS_SCALAR_64_32 = 4 };
+static std::mutex g_ks_inst_mutex;
+static uint32_t g_ks_inst[8];
+static void ks_note(int word, uint32_t value) {
+  std::lock_guard<std::mutex> lock(g_ks_inst_mutex);
+  g_ks_inst[word] = value;
+}
+static void ks_note_begin(uint32_t key_bits) {
+  std::lock_guard<std::mutex> lock(g_ks_inst_mutex);
+  for (uint32_t &w : g_ks_inst) w = 0;
+  g_ks_inst[KS_INST_BITS] = key_bits;
+}
+
 // the widest supported step count per barrier that divides `steps`.  Steps of 32 k between two workgroup barriers, by key
 // word size: measured per 4096 LWEs on one box, u64 keys 0.373 / 0.307 / 0.325 ms with 1 / 2 / 4 (4 fills the 64 KB of
 // static LDS), u32 keys 0.279 / 0.216 / 0.203 ms
 template <typename OutT, typename... Args>
 static void launch_ks_gemm(dim3 grid, hipStream_t st, uint32_t steps, Args... args) {
   constexpr int WANT = sizeof(OutT) == 8 ? 2 : 4;
-  if (WANT >= 4 && steps % 4 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 4>), grid, dim3(256), 0, st, args...);
-  else if (WANT >= 2 && steps % 2 == 0) HX_LAUNCH((ks_gemm_kernel<OutT, 2>), grid, dim3(256), 0, st, args...);
-  else HX_LAUNCH((ks_gemm_kernel<OutT, 1>), grid, dim3(256), 0, st, args...);
+  uint32_t spb = 1;  // noted as it is chosen: KS_INST_GEMM
+  if (WANT >= 4 && steps % 4 == 0) {
+    spb = 4;
+    HX_LAUNCH((ks_gemm_kernel<OutT, 4>), grid, dim3(256), 0, st, args...);
+  } else if (WANT >= 2 && steps % 2 == 0) {
+    spb = 2;
+    HX_LAUNCH((ks_gemm_kernel<OutT, 2>), grid, dim3(256), 0, st, args...);
+  } else {
+    HX_LAUNCH((ks_gemm_kernel<OutT, 1>), grid, dim3(256), 0, st, args...);
+  }
+  ks_note(KS_INST_GEMM, spb + 256u * grid.x);
 }
 
 // A operands + digit sums of the large-batch path: buffers per (device, stream) — the keyswitch entry points of the
@@ -762,6 +796,12 @@ void keyswitch_select_kernel(uint32_t which) {
 }
 uint32_t keyswitch_last_path() { return g_last_path.load(); }
 void keyswitch_set_kparts(uint32_t parts) { g_kparts.store(parts ? parts : 1); }
+
+void keyswitch_last_instantiation(uint32_t out8[8]) {
+  std::lock_guard<std::mutex> lock(g_ks_inst_mutex);
+  for (int i = 1; i < 8; ++i) out8[i] = g_ks_inst[i];
+  out8[0] = g_last_path.load();
+}
 bool keyswitch_batch_takes_gemm(uint32_t num_samples) { return num_samples >= g_gemm_min.load() && g_split_digits.load(); }
 
 // ------------------------------------------------------------------ launching the matrix-core paths
@@ -898,6 +938,8 @@ static bool ksm_launch_digits_gemm(const KsCall<OutT> &c, const KsmShape &sh, co
   int32_t *suma = (int32_t *)(scr + a_bytes);
   HX_CHECK(hipMemsetAsync(suma, 0, (size_t)tiles * 32 * sizeof(int32_t), c.st));
   ksm_with_level(sh.level_pad, c.level, [&](auto L, auto P) {
+    ks_note(KS_INST_LEVEL, (uint32_t)decltype(L)::value);
+    ks_note(KS_INST_PADDED, (uint32_t)decltype(P)::value);
     HX_LAUNCH((ks_digits_kernel<decltype(L)::value, decltype(P)::value>), dim3(tiles, KSD_SPLIT), dim3(256), 0, c.st, scr, suma,
               c.lwe_in, c.in_idx, c.n_in, c.base_log, c.level, c.num_samples);
   });
@@ -926,6 +968,11 @@ static void ksm_launch_one(const KsCall<OutT> &c, const KsmShape &sh, const int8
   ksm_with_level(sh.level_pad, c.level, [&](auto L, auto P) {
     constexpr int LEVEL = decltype(L)::value;
     constexpr bool PADDED = decltype(P)::value;
+    ks_note(KS_INST_LEVEL, (uint32_t)LEVEL);
+    ks_note(KS_INST_PADDED, (uint32_t)PADDED);
+    ks_note(KS_INST_KSPLIT, split ? 4u : 1u);
+    ks_note(KS_INST_KPARTS, kparts);
+    ks_note(KS_INST_GEMM, 256u * sh.col_tiles);
     if (split)
       HX_LAUNCH((ks_mfma_kernel<LEVEL, PADDED, OutT, 4>), grid, dim3(256), 0, c.st, c.lwe_out, c.out_idx, c.lwe_in, c.in_idx,
                 planes, colsum, c.n_in, c.n_out, c.base_log, c.num_samples, sh.col_tiles, c.level, c.ksk, c.key_words());
@@ -981,6 +1028,7 @@ static bool keyswitch_front(const char *name, uint32_t max_bits, const KsCall<Ou
   HX_PANIC_IF_FALSE(c.base_log >= 1 && c.level >= 1 && c.base_log * c.level <= max_bits,
                     "%s: unsupported decomposition (base_log=%u, level=%u)", name, c.base_log, c.level);
   if (c.num_samples == 0) return true;
+  ks_note_begin(8 * (uint32_t)sizeof(OutT));
   return g_use_mfma.load() && keyswitch_mfma(c, ready);
 }
 
@@ -998,14 +1046,17 @@ void launch_keyswitch(hipStream_t st, uint64_t *lwe_out, const uint64_t *out_idx
   while (((uint64_t)1 << log_terms) < (uint64_t)n_in * level) ++log_terms;
   if (base_log + 33 + log_terms <= 64) {  // d' <= 2^base_log, so one spare bit
     const size_t smem = sizeof(uint32_t) * KS_IC * level * KS_TB;
+    ks_note(KS_INST_SCALAR, KS_SCALAR_SMALL_BASE);
     HX_LAUNCH(keyswitch_small_base_kernel, grid, dim3(KS_TPB), smem, st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in,
               n_out, base_log, level, num_samples);
   } else if (base_log <= 31) {
     const size_t smem = sizeof(int32_t) * KS_IC * level * KS_TB;
+    ks_note(KS_INST_SCALAR, KS_SCALAR_DIGITS32);
     HX_LAUNCH((keyswitch_kernel<int32_t>), grid, dim3(KS_TPB), smem, st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in,
               n_out, base_log, level, num_samples);
   } else {
     const size_t smem = sizeof(int64_t) * KS_IC * level * KS_TB;
+    ks_note(KS_INST_SCALAR, KS_SCALAR_DIGITS64);
     HX_LAUNCH((keyswitch_kernel<int64_t>), grid, dim3(KS_TPB), smem, st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in,
               n_out, base_log, level, num_samples);
   }
@@ -1017,10 +1068,12 @@ void launch_keyswitch_64_32(hipStream_t st, uint32_t *lwe_out, const uint64_t *o
   const KsCall<uint32_t> c{st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out, base_log, level, num_samples};
   // lwe_keyswitch.rs:353-359: the decomposition must fit the OUTPUT width
   if (keyswitch_front("keyswitch 64->32", 32, c, nullptr)) return;
+  g_last_path.store(0);
   HX_PANIC_IF_FALSE(level <= KS_MAXL, "keyswitch 64->32: level_count %u > %d is only supported by the matrix-core kernel",
                     level, KS_MAXL);
   const dim3 grid((n_out + 1 + KS_TPB - 1) / KS_TPB, (num_samples + KS_TB - 1) / KS_TB);
   const size_t smem = sizeof(uint32_t) * KS_IC * level * KS_TB;
+  ks_note(KS_INST_SCALAR, KS_SCALAR_64_32);
   HX_LAUNCH(keyswitch_64_32_kernel, grid, dim3(KS_TPB), smem, st, lwe_out, out_idx, lwe_in, in_idx, ksk, n_in, n_out,
             base_log, level, num_samples);
 }

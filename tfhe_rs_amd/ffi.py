@@ -141,6 +141,8 @@ SIGNATURES = {
     "hip_backend_set_keyswitch_kernel": (None, [_u32]),
     "hip_backend_last_keyswitch_path": (_u32, []),
     "hip_backend_set_keyswitch_kparts": (None, [_u32]),
+    "hip_backend_last_keyswitch_instantiation": (None, [C.POINTER(C.c_uint32)]),
+    "hip_backend_keyswitch_cache_entries": (_u32, []),
     "hip_integer_set_multi_gpu_threshold": (None, [_u32]),
     "hip_integer_active_gpu_count": (_u32, [_u32, _u32, _u32, _u32]),
     "hip_backend_set_ntt_kernel": (None, [_u32]),
