@@ -859,6 +859,58 @@ void hip_integer_grouped_oprf_64_async(CudaStreamsFFI streams,
 void hip_cleanup_integer_grouped_oprf_64(CudaStreamsFFI streams,
                                          int8_t **mem_ptr_void);
 
+/* ------------------------------------------------------------------ sum of ciphertexts, scalar multiplication (extensions)
+ * cuda/include/integer/integer.h:433-463 and :862-864 under hip_ names with the reference's parameter lists; the
+ * reference-named symbols remain link stubs.
+ * partial_sum_ciphertexts_vec: radix_lwe_vec holds V integers of num_blocks_in_radix blocks, [v][block]; degrees are
+ * read from radix_lwe_vec->degrees when given (otherwise every block counts as message_modulus - 1), blocks of degree 0
+ * are left out.  radix_lwe_out may be the first integer of the vector.  V = 1 copies, V = 2 adds.  With
+ * reduce_degrees_for_single_carry_propagation every output block ends at a degree of 2 message_modulus - 2 at most
+ * (what propagate_single_carry accepts), without it at message_modulus * carry_modulus - 1 at most.  Degrees and noise
+ * levels of the output are written back.  The plan of a sum depends on the degrees: it is made by the call and kept until
+ * a call brings other degrees.  hip_partial_sum_ciphertexts_vec_pbs_count: bootstraps the last call issued.
+ * integer_scalar_mul: in place on clean blocks; lwe_array may hold a batch of integers (hip_integer_scratch_batch before
+ * the scratch call), all multiplied by the same scalar.  decomposed_scalar (num_scalars bits, least significant first)
+ * and has_at_least_one_set (message bits entries) are host arrays; bits at or above the integer's width are ignored.
+ * hip_integer_scalar_mul_pbs_count: bootstraps per integer for that scalar (shifted blocks, column sums, propagation). */
+uint64_t hip_scratch_partial_sum_ciphertexts_vec_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks_in_radix,
+    uint32_t max_num_radix_in_vec, uint32_t message_modulus,
+    uint32_t carry_modulus, bool reduce_degrees_for_single_carry_propagation,
+    bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_partial_sum_ciphertexts_vec_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *radix_lwe_out,
+    CudaRadixCiphertextFFI *radix_lwe_vec, int8_t *mem_ptr, void *const *bsks,
+    void *const *ksks);
+void hip_cleanup_partial_sum_ciphertexts_vec_64(CudaStreamsFFI streams,
+                                                int8_t **mem_ptr_void);
+uint64_t hip_partial_sum_ciphertexts_vec_pbs_count(int8_t *mem_ptr);
+uint64_t hip_scratch_integer_scalar_mul_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, uint32_t num_scalar_bits,
+    bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_scalar_mul_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array,
+    uint64_t const *decomposed_scalar, uint64_t const *has_at_least_one_set,
+    int8_t *mem_ptr, void *const *bsks, void *const *ksks,
+    uint32_t polynomial_size, uint32_t message_modulus, uint32_t num_scalars);
+void hip_cleanup_integer_scalar_mul_64(CudaStreamsFFI streams,
+                                       int8_t **mem_ptr_void);
+uint64_t hip_integer_scalar_mul_pbs_count(int8_t *mem_ptr,
+                                          uint64_t const *decomposed_scalar,
+                                          uint32_t num_scalars);
+void hip_small_scalar_multiplication_integer_64_inplace_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array, uint64_t scalar,
+    const uint32_t message_modulus, const uint32_t carry_modulus);
+/* benches: out[g] = sum of the pool rows members[offsets[g] .. offsets[g + 1]) by the column-sum kernel of the
+ * multiplication (which = 0) or by the two-base gather-sum kernel of the sum and the scalar multiplication (which = 1) */
+void hip_test_group_sum_async(void *stream, uint32_t gpu_index, uint32_t which, void *out, void const *pool,
+                              void const *offsets, void const *members, uint32_t words, uint32_t groups);
+
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's
  * cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103 and cuda/include/fft/fft128.h), under hip_ names

@@ -21,6 +21,7 @@
 #include "arena.h"
 #include "profile.h"
 #include "scratch.h"
+#include "radix_sum.h"
 #include "../../include/tfhe_hip_backend.h"
 
 #include <algorithm>
@@ -929,120 +930,42 @@ struct MulMem : ScratchHeader {
   uint32_t slots = 0;                          // pool slots per integer
   uint64_t *d_pool = nullptr, *d_pack = nullptr, *d_sum = nullptr;
 
-  struct Step {  // one reduction step, ciphertext-relative
-    std::vector<uint64_t> offsets, members;      // CSR of groups (pool slots)
-    std::vector<uint64_t> msg_slot, carry_slot;  // output slots per group (carry_slot = ~0 when dropped)
-  };
+  using Step = SumStep;  // one reduction step, ciphertext-relative: groups of pool slots, the slots they become
   std::vector<uint64_t> prod_lhs, prod_rhs, prod_slot, prod_lut;  // products
   std::vector<Step> steps;
   std::vector<std::vector<uint64_t>> final_cols;  // what is left of every column: degrees adding up to 2 msg - 2 at most
 
-  // The column sums are planned on the largest value every term can take (its degree): a low half of a block
-  // product is at most msg - 1, a high half at most (msg - 1)^2 / msg (2 for msg = 4), the carry of a sum S at most
-  // S / msg.  A group holds at most max_terms = (msg carry - 1) / (msg - 1) = 5 terms — every term is a fresh
-  // bootstrap output, and that count is the noise level the parameter sets are made for (shortint MaxNoiseLevel;
-  // it is also the reference's fixed chunk in sum_ciphertexts) — whose degrees add up to msg * carry - 1 at most;
-  // a group whose degrees stay below msg emits no carry, and a column is finished once it has at most max_terms
-  // terms whose degrees add up to 2 msg - 2, what one carry propagation accepts.
+  // The first terms of the column sums (radix_sum.h plans the rest): a low half of a block product is at most msg - 1, a
+  // high half at most (msg - 1)^2 / msg (2 for msg = 4).  Every column ends at degrees adding up to 2 msg - 2 at most,
+  // what one carry propagation accepts.  Many integers per call: 1,762 PBS per 32-block multiplication; few: 1,804 in
+  // three rounds less.
   void plan() {
     const uint32_t L = blocks, m = drv.p.msg;
-    const uint32_t cap = drv.p.msg * drv.p.carry - 1, final_cap = 2 * m - 2, max_terms = cap / (m - 1);
     std::vector<std::vector<uint64_t>> cols(L);
     std::vector<uint32_t> deg;  // by pool slot
-    uint64_t next = 0;
     auto new_slot = [&](uint32_t d) {
       deg.push_back(d);
-      return next++;
+      return (uint64_t)deg.size() - 1;
     };
     for (uint32_t i = 0; i < L; ++i)
       for (uint32_t j = 0; i + j < L; ++j) {
         prod_lhs.push_back(j);
         prod_rhs.push_back(i);
         prod_lut.push_back(0);
-        prod_slot.push_back(next);
+        prod_slot.push_back(deg.size());
         cols[i + j].push_back(new_slot(m - 1));
         if (i + j + 1 < L) {
           prod_lhs.push_back(j);
           prod_rhs.push_back(i);
           prod_lut.push_back(1);
-          prod_slot.push_back(next);
+          prod_slot.push_back(deg.size());
           cols[i + j + 1].push_back(new_slot((m - 1) * (m - 1) / m));
         }
       }
-    auto total = [&](const std::vector<uint64_t> &c) {
-      uint32_t t = 0;
-      for (uint64_t x : c) t += deg[x];
-      return t;
-    };
-    auto finished = [&](const std::vector<uint64_t> &c) { return total(c) <= final_cap && c.size() <= max_terms; };
-    auto unfinished = [&]() {
-      for (auto &c : cols)
-        if (!finished(c)) return true;
-      return false;
-    };
-    // Many integers per call (throughput): a group costs two PBS whatever it holds, so only well-filled groups
-    // (max_terms terms, or four with degrees adding up to cap - 2 at least) are summed while any column can form one —
-    // what is left of a column waits for the next step (1,762 PBS per 32-block multiplication, three more but small
-    // rounds).  Few integers (latency): every term is grouped at once, which needs the fewest rounds (1,804).
-    const bool wide = max_cts >= 8;
-    while (unfinished()) {
-      // first-fit decreasing: the terms of an unfinished column, largest degree first, into groups of capacity cap
-      std::vector<std::vector<std::vector<uint64_t>>> groups(L);
-      bool any_good = false;
-      auto good = [&](const std::vector<uint64_t> &g) {
-        return g.size() >= max_terms || (g.size() >= 4 && total(g) + 2 >= cap);
-      };
-      for (uint32_t c = 0; c < L; ++c) {
-        if (finished(cols[c])) continue;
-        std::vector<uint64_t> sorted = cols[c];
-        std::stable_sort(sorted.begin(), sorted.end(), [&](uint64_t x, uint64_t y) { return deg[x] > deg[y]; });
-        for (uint64_t x : sorted) {
-          bool placed = false;
-          for (auto &g : groups[c])
-            if (g.size() < max_terms && total(g) + deg[x] <= cap) {
-              g.push_back(x);
-              placed = true;
-              break;
-            }
-          if (!placed) groups[c].push_back({x});
-        }
-        for (auto &g : groups[c]) any_good = any_good || good(g);
-      }
-      Step s;
-      s.offsets.push_back(0);
-      std::vector<std::vector<uint64_t>> nc(L);
-      for (uint32_t c = 0; c < L; ++c) {
-        if (groups[c].empty()) {  // finished column: stays as it is
-          nc[c].insert(nc[c].end(), cols[c].begin(), cols[c].end());
-          continue;
-        }
-        for (auto &g : groups[c]) {
-          const bool emit = g.size() >= 2 && (!wide || (any_good ? good(g) : g.size() >= 3));
-          if (!emit) {
-            nc[c].insert(nc[c].end(), g.begin(), g.end());
-            continue;
-          }
-          const uint32_t sum = total(g);
-          s.members.insert(s.members.end(), g.begin(), g.end());
-          s.offsets.push_back(s.members.size());
-          const uint64_t ms = new_slot(std::min(m - 1, sum));
-          s.msg_slot.push_back(ms);
-          nc[c].push_back(ms);
-          if (c + 1 < L && sum >= m) {
-            const uint64_t cs = new_slot(sum / m);
-            s.carry_slot.push_back(cs);
-            nc[c + 1].push_back(cs);
-          } else {
-            s.carry_slot.push_back(~(uint64_t)0);
-          }
-        }
-      }
-      HX_PANIC_IF_FALSE(!s.msg_slot.empty(), "multiplication plan: no progress");
-      cols.swap(nc);
-      steps.push_back(std::move(s));
-    }
-    final_cols = cols;
-    slots = (uint32_t)next;
+    SumPlan plan = plan_column_sums(std::move(cols), deg, m, drv.p.carry, max_cts >= 8, 2 * m - 2);
+    steps = std::move(plan.steps);
+    final_cols = std::move(plan.final_cols);
+    slots = (uint32_t)deg.size();
   }
 
   void init(const CudaStreamsFFI &ss, const Params &p, uint32_t num_blocks, uint32_t cts) {
@@ -1476,6 +1399,15 @@ struct CmuxMem : ScratchHeader {
   }
 };
 
+// the shift by r bits inside a block, on the packing msg * current + neighbour (lower neighbour for a left shift, upper
+// for a right one): the table of the logical scalar shift and of the scalar multiplication's shifted copies
+static std::function<uint64_t(uint64_t)> shift_in_block(uint32_t msg, uint32_t bits, uint32_t r, bool left) {
+  return [msg, bits, r, left](uint64_t x) -> uint64_t {
+    const uint64_t cur = x / msg, nb = x % msg;
+    return (left ? ((cur << r) | (nb >> (bits - r))) : ((cur >> r) | (nb << (bits - r)))) % msg;
+  };
+}
+
 // scalar_shifts.cuh / integer.h:200-228: logical shift of an unsigned integer by a clear amount = a move by whole blocks
 // and, when bits remain, ONE bivariate round over (block, its lower / upper neighbour)
 struct ScalarShiftMem : ScratchHeader {
@@ -1521,6 +1453,307 @@ static void check_clean(std::initializer_list<const CudaRadixCiphertextFFI *> op
         HX_PANIC_IF_FALSE(op->degrees[i] <= msg - 1, "%s: block %u has degree %llu, %s", who, i,
                           (unsigned long long)op->degrees[i], tail);
 }
+
+// ------------------------------------------------------------------ column sums read in place
+// The device side of a SumPlan (radix_sum.h) whose first terms are not in a pool: term ids below n_caller are rows of the
+// caller's memory (integer c of a batch owns rows c * caller_rows ...), the ids from n_caller on are rows of d_pool
+// (integer c owns rows c * slots ...).  Every step is one gather-sum launch into d_sum and one KS -> PBS round (message
+// and carry of every group) into the pool; what is left of every column is summed into the output.
+struct ColumnSum {
+  SumPlan plan;
+  uint32_t L = 0, n_caller = 0, caller_rows = 0, slots = 0;
+  bool final_reads_caller = false;
+  uint32_t nb = 0;  // integers the device arrays were built for (0: none)
+  struct StepIdx {
+    uint64_t *off = nullptr, *mem = nullptr, *in = nullptr, *out = nullptr, *lut = nullptr;
+    uint32_t groups = 0, count = 0;
+  };
+  std::vector<StepIdx> steps;
+  uint64_t *foff = nullptr, *fmem = nullptr;
+  std::vector<uint64_t *> owned;
+  uint64_t *d_pool = nullptr, *d_sum = nullptr;
+  size_t pool_rows = 0, sum_rows = 0;
+
+  // takes the plan of columns `cols` over the degrees `deg` (deg.size() first terms, the first n_caller_ in caller rows)
+  void set_plan(SumPlan &&pl, uint32_t L_, uint32_t n_caller_, uint32_t caller_rows_, size_t terms) {
+    plan = std::move(pl);
+    L = L_, n_caller = n_caller_, caller_rows = caller_rows_;
+    slots = (uint32_t)(terms - n_caller_);
+    final_reads_caller = false;
+    for (auto &c : plan.final_cols)
+      for (uint64_t x : c) final_reads_caller = final_reads_caller || x < n_caller;
+    nb = 0;
+  }
+  uint64_t row(uint64_t id, uint32_t c) const {
+    return id < n_caller ? kCallerRow | ((uint64_t)c * caller_rows + id) : (uint64_t)c * slots + (id - n_caller);
+  }
+  // rows of the pool and of the dense sums for `cts` integers of the present plan (both only ever grow)
+  void reserve(hipStream_t st, uint32_t cts, size_t w) {
+    const size_t pr = (size_t)cts * slots, sr = (size_t)cts * std::max<size_t>(plan.max_groups(), L);
+    auto grow = [&](uint64_t *&d, size_t &have, size_t want) {
+      if (want <= have) return;
+      if (d) {
+        HX_CHECK(hipStreamSynchronize(st));  // launches may still use the smaller buffer
+        scratch_free(d);
+      }
+      radix_alloc((void **)&d, want * w * sizeof(uint64_t));
+      have = want;
+    };
+    grow(d_pool, pool_rows, pr);
+    grow(d_sum, sum_rows, sr);
+  }
+  void free_indexes(hipStream_t st) {
+    if (!owned.empty()) HX_CHECK(hipStreamSynchronize(st));  // launches of the previous plan may still read them
+    for (auto *d : owned) scratch_free(d);
+    owned.clear();
+    steps.clear();
+    foff = fmem = nullptr;
+    nb = 0;
+  }
+  // index arrays of the plan for cts integers (build_pass of the multiplication is the model)
+  void upload(hipStream_t st, uint32_t cts, uint64_t lut_msg, uint64_t lut_carry) {
+    free_indexes(st);
+    auto up = [&](const std::vector<uint64_t> &h) {
+      uint64_t *d = dev_upload(st, h);
+      if (d) owned.push_back(d);
+      return d;
+    };
+    for (const SumStep &s : plan.steps) {
+      StepIdx si;
+      const size_t G = s.msg_slot.size(), M = s.members.size();
+      std::vector<uint64_t> off(cts * G + 1), mem(cts * M), in, out, lut;
+      for (uint32_t c = 0; c < cts; ++c) {
+        for (size_t g = 0; g < G; ++g) {
+          off[c * G + g] = c * M + s.offsets[g];
+          in.push_back(c * G + g);
+          out.push_back(row(s.msg_slot[g], c));
+          lut.push_back(lut_msg);
+          if (s.carry_slot[g] != ~(uint64_t)0) {
+            in.push_back(c * G + g);
+            out.push_back(row(s.carry_slot[g], c));
+            lut.push_back(lut_carry);
+          }
+        }
+        for (size_t m = 0; m < M; ++m) mem[c * M + m] = row(s.members[m], c);
+      }
+      off[cts * G] = cts * M;
+      si.off = up(off), si.mem = up(mem), si.in = up(in), si.out = up(out), si.lut = up(lut);
+      si.groups = (uint32_t)(cts * G);
+      si.count = (uint32_t)in.size();
+      steps.push_back(si);
+    }
+    std::vector<uint64_t> off{0}, mem;
+    for (uint32_t c = 0; c < cts; ++c)
+      for (uint32_t col = 0; col < L; ++col) {
+        for (uint64_t x : plan.final_cols[col]) mem.push_back(row(x, c));
+        off.push_back(mem.size());
+      }
+    foff = up(off), fmem = up(mem);
+    nb = cts;
+  }
+  void reduce(const CudaStreamsFFI &ss, const LutDriver &drv, const uint64_t *caller, uint32_t w, void *const *ksks,
+              void *const *bsks) const {
+    for (const StepIdx &si : steps) {
+      if (si.groups == 0) continue;
+      HX_RANGE("column sums (%u groups)", si.groups);
+      launch_gather_sum2(S0(ss), d_sum, d_pool, caller, si.off, si.mem, w, si.groups);
+      drv.round(ss, d_pool, si.out, d_sum, si.in, si.lut, si.count, ksks, bsks);
+    }
+  }
+  // out[c * L + col] = what is left of column col of integer c.  in_place: `out` holds caller rows and every output row is
+  // read by its own group only; otherwise output rows that other groups read go through the dense buffer.
+  void finish(hipStream_t st, uint64_t *out, const uint64_t *caller, uint32_t w, bool in_place) const {
+    if (!final_reads_caller || in_place) {
+      launch_gather_sum2(st, out, d_pool, caller, foff, fmem, w, nb * L);
+      return;
+    }
+    launch_gather_sum2(st, d_sum, d_pool, caller, foff, fmem, w, nb * L);
+    HX_CHECK(hipMemcpyAsync(out, d_sum, (size_t)nb * L * w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  }
+  void release(hipStream_t st) {
+    free_indexes(st);
+    for (uint64_t *d : {d_pool, d_sum})
+      if (d) scratch_free(d);
+    d_pool = d_sum = nullptr;
+  }
+};
+
+// ------------------------------------------------------------------ sum of a vector of ciphertexts
+// multiplication.cuh:286-485 (host_integer_partial_sum_ciphertexts_vec): V integers of `blocks` blocks, [v][block]; column
+// c holds block c of every integer whose degree there is not 0.  The plan depends on the degrees: it is made by the call
+// and kept, with its device arrays, until a call brings other degrees.
+struct SumMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x53554D31;  // "SUM1"
+  LutDriver drv;  // LUTs: 0 message, 1 carry
+  uint32_t blocks = 0, max_vec = 0;
+  bool reduce = false;
+  ColumnSum cs;
+  std::vector<uint64_t> key;  // the degrees the present plan was made for
+  std::vector<uint32_t> deg;  // degree by term id of the present plan
+  uint64_t last_pbs = 0;      // bootstraps of the last call
+
+  void init(const CudaStreamsFFI &ss, const Params &p, uint32_t num_blocks, uint32_t max_num_radix_in_vec,
+            bool reduce_degrees) {
+    HX_PANIC_IF_FALSE(num_blocks >= 1, "partial_sum_ciphertexts_vec: no blocks");
+    HX_PANIC_IF_FALSE(p.msg >= 3, "partial_sum_ciphertexts_vec: message_modulus %u < 3 is not supported", p.msg);
+    blocks = num_blocks, max_vec = max_num_radix_in_vec, reduce = reduce_degrees;
+    const uint64_t m = p.msg;
+    std::vector<std::vector<uint64_t>> luts(2, std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
+    generate_lut(p, luts[0].data(), [m](uint64_t x) -> uint64_t { return x % m; });
+    generate_lut(p, luts[1].data(), [m](uint64_t x) -> uint64_t { return x / m; });
+    drv.init(ss, p, std::max<uint32_t>(1, std::min<uint64_t>((uint64_t)max_vec * blocks, 1u << 16)), luts);
+    // sized for a full vector of clean integers; a call whose degrees need more grows it
+    make_plan(std::vector<uint64_t>((size_t)max_vec * blocks, m - 1), max_vec);
+    cs.reserve(S0(ss), 1, (size_t)p.big_n + 1);
+  }
+  void make_plan(const std::vector<uint64_t> &d, uint32_t V) {
+    const Params &p = drv.p;
+    std::vector<std::vector<uint64_t>> cols(blocks);
+    deg.assign(d.begin(), d.end());
+    for (uint32_t v = 0; v < V; ++v)
+      for (uint32_t c = 0; c < blocks; ++c)
+        if (d[(size_t)v * blocks + c] != 0) cols[c].push_back((uint64_t)v * blocks + c);
+    SumPlan pl = plan_column_sums(std::move(cols), deg, p.msg, p.carry, false,
+                                  reduce ? 2 * p.msg - 2 : p.msg * p.carry - 1);
+    cs.set_plan(std::move(pl), blocks, V * blocks, V * blocks, deg.size());
+    key = d;
+  }
+  void release(const CudaStreamsFFI &ss) {
+    HX_CHECK(hipStreamSynchronize(S0(ss)));
+    cs.release(S0(ss));
+    drv.release(ss);
+  }
+};
+
+// ------------------------------------------------------------------ multiplication by a clear scalar
+// scalar_mul.cuh:47-136 takes one logical shift per set residue of the bit position (msg_bits rounds of one copy each),
+// one rotated copy of the whole integer per set bit, a copy of that vector into the sum's work buffer, the sum and a carry
+// propagation.  Here: ONE round bootstraps every in-block shift some set bit uses (plane r, r = 1 .. msg_bits - 1: block j
+// becomes the shift-left table on msg * b[j] + b[j - 1]; plane 0 is the operand itself), bit i then contributes block j
+// of plane i % msg_bits to column j + i / msg_bits as an index entry of the gather-sum kernel, the shared planner reduces
+// the columns and one carry propagation finishes.  Term ids: j (plane 0, caller rows), blocks + (r - 1) blocks + j (pool).
+struct ScalarMulMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x534D554C;  // "SMUL"
+  LutDriver drv;  // LUTs: 0 message, 1 carry, 2 + (r - 1): shift left by r bits inside a block
+  PropagateMem prop;
+  uint32_t blocks = 0, max_cts = 0, bits = 0, scalar_bits = 0;
+  ColumnSum cs;
+  uint64_t *d_pack = nullptr;   // msg * b[j] + b[j - 1] of every block of every integer
+  std::vector<uint8_t> key;     // the bits (below bits * blocks) the present plan was made for
+  bool planned = false, propagate = false, any_bit = false;
+  std::vector<uint64_t> pre_j, pre_r;  // the shifted blocks some set bit uses, per integer
+  // device arrays of the preshift round for cs.nb integers
+  uint64_t *pk0 = nullptr, *pkj = nullptr, *pkm = nullptr, *pre_in = nullptr, *pre_out = nullptr, *pre_lut = nullptr;
+  std::vector<uint64_t *> owned;
+
+  static std::vector<uint8_t> scalar_key(const uint64_t *decomposed, uint32_t n, uint32_t limit) {
+    std::vector<uint8_t> k(std::min(n, limit));
+    for (size_t i = 0; i < k.size(); ++i) k[i] = decomposed[i] == 1;
+    while (!k.empty() && !k.back()) k.pop_back();
+    return k;
+  }
+  void make_plan(const std::vector<uint8_t> &k) {
+    const Params &p = drv.p;
+    const uint32_t L = blocks, m = p.msg;
+    std::vector<std::vector<uint64_t>> cols(L);
+    std::vector<uint32_t> deg((size_t)L * bits, m - 1);
+    std::vector<uint32_t> used(bits, 0);  // blocks of plane r some set bit uses: j < used[r]
+    any_bit = false;
+    for (size_t i = 0; i < k.size(); ++i) {
+      if (!k[i]) continue;
+      any_bit = true;
+      const uint32_t r = (uint32_t)(i % bits), q = (uint32_t)(i / bits);
+      used[r] = std::max(used[r], L - q);
+      for (uint32_t j = 0; j + q < L; ++j) cols[j + q].push_back(r == 0 ? j : (uint64_t)L + (uint64_t)(r - 1) * L + j);
+    }
+    pre_j.clear(), pre_r.clear();
+    for (uint32_t r = 1; r < bits; ++r)
+      for (uint32_t j = 0; j < used[r]; ++j) pre_j.push_back(j), pre_r.push_back(r);
+    SumPlan pl = plan_column_sums(std::move(cols), deg, m, p.carry, max_cts >= 8, 2 * m - 2);
+    propagate = false;  // every column a single clean term or nothing (a power of two): nothing to propagate
+    for (auto &c : pl.final_cols) propagate = propagate || c.size() > 1;
+    cs.set_plan(std::move(pl), L, L, L, deg.size());
+    key = k;
+    planned = true;
+  }
+  uint64_t pbs_count() const {
+    return pre_j.size() + cs.plan.bootstraps() + (propagate ? PropagateMem::pbs_count(blocks) : 0);
+  }
+
+  void init(const CudaStreamsFFI &ss, const Params &p, uint32_t num_blocks, uint32_t cts, uint32_t num_scalar_bits) {
+    HX_PANIC_IF_FALSE(num_blocks >= 1, "integer_scalar_mul: no blocks");
+    HX_PANIC_IF_FALSE((p.msg & (p.msg - 1)) == 0, "integer_scalar_mul: the message modulus must be a power of two");
+    blocks = num_blocks, max_cts = cts;
+    bits = (uint32_t)__builtin_ctz(p.msg);
+    scalar_bits = std::min(num_scalar_bits, bits * blocks);
+    const uint64_t m = p.msg;
+    std::vector<std::vector<uint64_t>> luts(1 + bits, std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
+    generate_lut(p, luts[0].data(), [m](uint64_t x) -> uint64_t { return x % m; });
+    generate_lut(p, luts[1].data(), [m](uint64_t x) -> uint64_t { return x / m; });
+    for (uint32_t r = 1; r < bits; ++r) generate_lut(p, luts[1 + r].data(), shift_in_block(p.msg, bits, r, true));
+    const uint64_t widest = (uint64_t)cts * blocks * std::max(bits, scalar_bits);  // no round holds more blocks
+    drv.init(ss, p, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(widest, 1u << 16)), luts);
+    const size_t w = (size_t)p.big_n + 1;
+    radix_alloc((void **)&d_pack, (size_t)cts * blocks * w * sizeof(uint64_t));
+    prop.init(ss, p, num_blocks, cts);
+    // sized for the scalar with every bit set; a wider plan (there is none among the scalars tried) grows it
+    make_plan(std::vector<uint8_t>(scalar_bits, 1));
+    cs.reserve(S0(ss), cts, w);
+    planned = false;
+  }
+
+  void upload(hipStream_t st, uint32_t cts) {
+    cs.upload(st, cts, 0, 1);
+    for (auto *d : owned) scratch_free(d);  // (cs.upload waited for the stream)
+    owned.clear();
+    auto up = [&](const std::vector<uint64_t> &h) {
+      uint64_t *d = dev_upload(st, h);
+      if (d) owned.push_back(d);
+      return d;
+    };
+    const uint32_t L = blocks;
+    std::vector<uint64_t> r0, rj, rm, in, out, lut;
+    for (uint32_t c = 0; c < cts; ++c) {
+      r0.push_back((uint64_t)c * L);
+      for (uint32_t j = 1; j < L; ++j) rj.push_back((uint64_t)c * L + j), rm.push_back((uint64_t)c * L + j - 1);
+      for (size_t s = 0; s < pre_j.size(); ++s) {
+        in.push_back((uint64_t)c * L + pre_j[s]);
+        out.push_back((uint64_t)c * cs.slots + (pre_r[s] - 1) * L + pre_j[s]);
+        lut.push_back(1 + pre_r[s]);
+      }
+    }
+    pk0 = up(r0), pkj = up(rj), pkm = up(rm), pre_in = up(in), pre_out = up(out), pre_lut = up(lut);
+  }
+
+  // v <- v * scalar for `cts` integers (the plan of the scalar is in place)
+  void run(const CudaStreamsFFI &ss, uint64_t *v, uint32_t cts, void *const *ksks, void *const *bsks) {
+    const hipStream_t st = S0(ss);
+    const Params &p = drv.p;
+    const uint32_t L = blocks, w = p.big_n + 1;
+    cs.reserve(st, cts, w);
+    if (cs.nb != cts) upload(st, cts);
+    HX_RANGE("integer scalar mul: %u integers of %u blocks", cts, L);
+    if (!pre_j.empty()) {
+      HX_RANGE("shifted blocks");
+      axpy(st, d_pack, pk0, v, pk0, p.msg, nullptr, nullptr, w, cts);
+      axpy(st, d_pack, pkj, v, pkj, p.msg, v, pkm, w, cts * (L - 1));
+      drv.round(ss, cs.d_pool, pre_out, d_pack, pre_in, pre_lut, (uint32_t)(cts * pre_j.size()), ksks, bsks);
+    }
+    cs.reduce(ss, drv, v, w, ksks, bsks);
+    cs.finish(st, v, v, w, false);
+    if (propagate) prop.run(ss, v, cts, ksks, bsks);
+  }
+
+  void release(const CudaStreamsFFI &ss) {
+    HX_CHECK(hipStreamSynchronize(S0(ss)));
+    cs.release(S0(ss));
+    for (auto *d : owned) scratch_free(d);
+    owned.clear();
+    drv.release(ss);
+    prop.release(ss);
+    if (d_pack) scratch_free(d_pack);
+  }
+};
 
 // ------------------------------------------------------------------ ciphertext compression
 // tfhe/src/shortint/list_compression/compression.rs:17-133 (compress), :137-254 (decompress); the reference's GPU flow is
@@ -2545,11 +2778,7 @@ uint64_t scratch_cuda_logical_scalar_shift_64_inplace_async(CudaStreamsFFI strea
     const uint32_t msg = p.msg, bits = m.bits;
     const bool left = m.left != 0;
     std::vector<std::vector<uint64_t>> luts(std::max(1u, bits - 1), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
-    for (uint32_t r = 1; r < bits; ++r)  // packed msg * current + neighbour (lower neighbour for a left shift, upper for a right one)
-      generate_lut(p, luts[r - 1].data(), [msg, bits, r, left](uint64_t x) -> uint64_t {
-        const uint64_t cur = x / msg, nb = x % msg;
-        return (left ? ((cur << r) | (nb >> (bits - r))) : ((cur >> r) | (nb << (bits - r)))) % msg;
-      });
+    for (uint32_t r = 1; r < bits; ++r) generate_lut(p, luts[r - 1].data(), shift_in_block(msg, bits, r, left));
     m.drv.init(streams, p, num_blocks, luts);
     radix_alloc((void **)&m.d_pack, (size_t)num_blocks * (p.big_n + 1) * sizeof(uint64_t));
     std::vector<uint64_t> li((size_t)std::max(1u, bits - 1) * num_blocks);
@@ -2625,6 +2854,193 @@ uint64_t hip_integer_mult_pbs_count(int8_t *mem_ptr) {
   for (auto &s : m->steps)
     for (size_t g = 0; g < s.msg_slot.size(); ++g) n += 1 + (s.carry_slot[g] != ~(uint64_t)0);
   return n + PropagateMem::pbs_count(m->blocks);
+}
+
+// ---- sum of a vector of ciphertexts, multiplication by a clear scalar (hip_ names with the parameter lists of
+// cuda/include/integer/integer.h:433-463, :862-864: the reference-named symbols stay link stubs) ----------------------
+uint64_t hip_scratch_partial_sum_ciphertexts_vec_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                                          CudaLweBootstrapKeyParamsFFI bsk_params,
+                                                          CudaLweKeyswitchKeyParamsFFI ksk_params,
+                                                          uint32_t num_blocks_in_radix, uint32_t max_num_radix_in_vec,
+                                                          uint32_t message_modulus, uint32_t carry_modulus,
+                                                          bool reduce_degrees_for_single_carry_propagation,
+                                                          bool allocate_gpu_memory,
+                                                          enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<SumMem>(streams, mem_ptr, allocate_gpu_memory, "partial_sum_ciphertexts_vec", [&](SumMem &m) {
+    m.init(streams, p, num_blocks_in_radix, max_num_radix_in_vec, reduce_degrees_for_single_carry_propagation);
+  });
+}
+
+void hip_partial_sum_ciphertexts_vec_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *radix_lwe_out,
+                                              CudaRadixCiphertextFFI *radix_lwe_vec, int8_t *mem_ptr, void *const *bsks,
+                                              void *const *ksks) {
+  first_gpu(streams);
+  auto *m = scratch_use<SumMem>(mem_ptr, "partial_sum_ciphertexts_vec");
+  HX_PANIC_IF_FALSE(radix_lwe_out && radix_lwe_vec && bsks && ksks, "partial_sum_ciphertexts_vec: null pointer");
+  const Params &p = m->drv.p;
+  const uint32_t L = m->blocks, w = p.big_n + 1;
+  HX_PANIC_IF_FALSE(radix_lwe_out->lwe_dimension == p.big_n && radix_lwe_vec->lwe_dimension == p.big_n,
+                    "partial_sum_ciphertexts_vec: input and output lwe dimensions should be %u", p.big_n);
+  HX_PANIC_IF_FALSE(radix_lwe_vec->num_radix_blocks % L == 0,
+                    "partial_sum_ciphertexts_vec: input vector length should be a multiple of the scratch's number of "
+                    "radix blocks (%u)", L);
+  const uint32_t V = radix_lwe_vec->num_radix_blocks / L;
+  HX_PANIC_IF_FALSE(V <= m->max_vec, "partial_sum_ciphertexts_vec: %u integers exceed max_num_radix_in_vec %u", V,
+                    m->max_vec);
+  m->last_pbs = 0;
+  if (V == 0) return;
+  HX_PANIC_IF_FALSE(radix_lwe_out->ptr && radix_lwe_vec->ptr && radix_lwe_out->num_radix_blocks >= L,
+                    "partial_sum_ciphertexts_vec: output does not have enough blocks (%u needed)", L);
+  const uint32_t cap = p.msg * p.carry - 1;
+  std::vector<uint64_t> d((size_t)V * L, p.msg - 1), noise((size_t)V * L, 1);
+  for (size_t i = 0; i < d.size(); ++i) {
+    if (radix_lwe_vec->degrees) d[i] = radix_lwe_vec->degrees[i];
+    if (radix_lwe_vec->noise_levels) noise[i] = radix_lwe_vec->noise_levels[i];
+    HX_PANIC_IF_FALSE(d[i] <= cap, "partial_sum_ciphertexts_vec: block %zu has degree %llu, at most %u fits a block", i,
+                      (unsigned long long)d[i], cap);
+    HX_PANIC_IF_FALSE(noise[i] <= 1,
+                      "partial_sum_ciphertexts_vec: block %zu has noise level %llu, the terms of a sum are at nominal noise",
+                      i, (unsigned long long)noise[i]);
+  }
+  const hipStream_t st = S0(streams);
+  uint64_t *out = (uint64_t *)radix_lwe_out->ptr;
+  const uint64_t *vec = (const uint64_t *)radix_lwe_vec->ptr;
+  if (V == 1) {
+    if (out != vec) HX_CHECK(hipMemcpyAsync(out, vec, (size_t)L * w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    for (uint32_t c = 0; c < L; ++c) {
+      if (radix_lwe_out->degrees) radix_lwe_out->degrees[c] = d[c];
+      if (radix_lwe_out->noise_levels) radix_lwe_out->noise_levels[c] = noise[c];
+    }
+    return;
+  }
+  if (V == 2) {  // a plain addition (multiplication.cuh: host_addition)
+    axpy(st, out, nullptr, vec, nullptr, 1, vec + (size_t)L * w, nullptr, w, L);
+    for (uint32_t c = 0; c < L; ++c) {
+      if (radix_lwe_out->degrees) radix_lwe_out->degrees[c] = d[c] + d[L + c];
+      if (radix_lwe_out->noise_levels) radix_lwe_out->noise_levels[c] = noise[c] + noise[L + c];
+    }
+    return;
+  }
+  if (m->key != d) m->make_plan(d, V);
+  m->cs.reserve(st, 1, w);
+  if (m->cs.nb != 1) m->cs.upload(st, 1, 0, 1);
+  HX_RANGE("sum of %u integers of %u blocks", V, L);
+  m->cs.reduce(streams, m->drv, vec, w, ksks, bsks);
+  m->last_pbs = m->cs.plan.bootstraps();
+  // an output that is an integer of the vector is read by the groups of its own columns only: summed in place
+  const bool apart = out + (size_t)L * w <= vec || out >= vec + (size_t)V * L * w;
+  m->cs.finish(st, out, vec, w, apart || (out >= vec && (size_t)(out - vec) % ((size_t)L * w) == 0));
+  for (uint32_t c = 0; c < L; ++c) {
+    uint64_t dc = 0, nc = 0;
+    for (uint64_t x : m->cs.plan.final_cols[c]) dc += m->deg[x], nc += x < (uint64_t)V * L ? noise[x] : 1;
+    if (radix_lwe_out->degrees) radix_lwe_out->degrees[c] = dc;
+    if (radix_lwe_out->noise_levels) radix_lwe_out->noise_levels[c] = nc;
+  }
+}
+
+void hip_cleanup_partial_sum_ciphertexts_vec_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<SumMem>(streams, mem_ptr_void, "cleanup partial_sum_ciphertexts_vec");
+}
+// bootstraps the last sum of this scratch issued (0 before the first, and for up to two integers)
+uint64_t hip_partial_sum_ciphertexts_vec_pbs_count(int8_t *mem_ptr) {
+  return scratch_cast<SumMem>(mem_ptr, "hip_partial_sum_ciphertexts_vec_pbs_count")->last_pbs;
+}
+
+// A batch of integers per call takes the same scalar; capacity from hip_integer_scratch_batch, as for the multiplication.
+uint64_t hip_scratch_integer_scalar_mul_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                                 CudaLweBootstrapKeyParamsFFI bsk_params,
+                                                 CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+                                                 uint32_t message_modulus, uint32_t carry_modulus,
+                                                 uint32_t num_scalar_bits, bool allocate_gpu_memory,
+                                                 enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<ScalarMulMem>(streams, mem_ptr, allocate_gpu_memory, "integer_scalar_mul", [&](ScalarMulMem &m) {
+    m.init(streams, p, num_blocks, g_scratch_batch, num_scalar_bits);
+  });
+}
+
+// decomposed_scalar: num_scalars bits, least significant first; has_at_least_one_set[r]: some set bit sits at a position
+// i with i % msg_bits == r.  Both on the host.  Bits at or above msg_bits * num_blocks are ignored.
+void hip_integer_scalar_mul_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array,
+                                     uint64_t const *decomposed_scalar, uint64_t const *has_at_least_one_set,
+                                     int8_t *mem_ptr, void *const *bsks, void *const *ksks, uint32_t polynomial_size,
+                                     uint32_t message_modulus, uint32_t num_scalars) {
+  first_gpu(streams);
+  auto *m = scratch_use<ScalarMulMem>(mem_ptr, "integer_scalar_mul");
+  HX_PANIC_IF_FALSE(lwe_array && lwe_array->ptr && bsks && ksks && (num_scalars == 0 || decomposed_scalar) &&
+                        has_at_least_one_set,
+                    "integer_scalar_mul: null pointer");
+  const Params &p = m->drv.p;
+  HX_PANIC_IF_FALSE(polynomial_size == p.N && message_modulus == p.msg, "integer_scalar_mul: call does not match the scratch");
+  HX_PANIC_IF_FALSE(lwe_array->lwe_dimension == p.big_n, "integer_scalar_mul: the blocks' lwe dimension should be %u", p.big_n);
+  const uint32_t L = m->blocks, w = p.big_n + 1;
+  const uint32_t cts = batch_of(lwe_array, L, "integer_scalar_mul");
+  HX_PANIC_IF_FALSE(cts >= 1 && cts <= m->max_cts, "integer_scalar_mul: %u integers exceed the scratch capacity %u", cts,
+                    m->max_cts);
+  check_clean({lwe_array}, cts * L, p.msg, "integer_scalar_mul", "the scalar multiplication takes clean blocks");
+  const std::vector<uint8_t> k = ScalarMulMem::scalar_key(decomposed_scalar, num_scalars, m->bits * L);
+  HX_PANIC_IF_FALSE(k.size() <= m->scalar_bits, "integer_scalar_mul: %zu scalar bits on a scratch created for %u", k.size(),
+                    m->scalar_bits);
+  for (size_t i = 0; i < k.size(); ++i)
+    HX_PANIC_IF_FALSE(!k[i] || has_at_least_one_set[i % m->bits] == 1,
+                      "integer_scalar_mul: bit %zu is set, has_at_least_one_set[%zu] is not", i, i % m->bits);
+  if (!m->planned || m->key != k) m->make_plan(k);
+  if (!m->any_bit) {
+    HX_CHECK(hipMemsetAsync(lwe_array->ptr, 0, (size_t)cts * L * w * sizeof(uint64_t), S0(streams)));
+    set_block_info(lwe_array, 0, cts * L, 0, 0);
+    return;
+  }
+  m->run(streams, (uint64_t *)lwe_array->ptr, cts, ksks, bsks);
+  set_block_info(lwe_array, 0, cts * L, p.msg - 1, 1);
+}
+
+void hip_cleanup_integer_scalar_mul_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<ScalarMulMem>(streams, mem_ptr_void, "cleanup integer_scalar_mul");
+}
+
+// bootstraps per integer of a multiplication by this scalar: shifted blocks + column sums + carry propagation
+uint64_t hip_integer_scalar_mul_pbs_count(int8_t *mem_ptr, uint64_t const *decomposed_scalar, uint32_t num_scalars) {
+  auto *m = scratch_cast<ScalarMulMem>(mem_ptr, "hip_integer_scalar_mul_pbs_count");
+  const std::vector<uint8_t> k = ScalarMulMem::scalar_key(decomposed_scalar, num_scalars, m->bits * m->blocks);
+  if (!m->planned || m->key != k) m->make_plan(k);
+  return m->any_bit ? m->pbs_count() : 0;
+}
+
+// the two column-sum kernels on the same CSR over one pool, for timing one against the other (tools/bench_scalar_mul.py):
+// which = 0 lwe_group_sum_kernel, 1 lwe_gather_sum2_kernel (every member a pool row)
+void hip_test_group_sum_async(void *stream, uint32_t gpu_index, uint32_t which, void *out, void const *pool,
+                              void const *offsets, void const *members, uint32_t words, uint32_t groups) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(which <= 1 && groups >= 1 && words >= 1, "hip_test_group_sum: unknown kernel or empty launch");
+  if (which == 0)
+    HX_LAUNCH(lwe_group_sum_kernel, dim3(groups), dim3(256), 0, (hipStream_t)stream, (uint64_t *)out,
+              (const uint64_t *)pool, (const uint64_t *)offsets, (const uint64_t *)members, words, groups);
+  else
+    launch_gather_sum2((hipStream_t)stream, (uint64_t *)out, (const uint64_t *)pool, (const uint64_t *)pool,
+                       (const uint64_t *)offsets, (const uint64_t *)members, words, groups);
+}
+
+// scalar_mul.cuh:139-177 (host_integer_small_scalar_mul_radix): every word times a small scalar; degrees and noise levels
+// scale, and a noise level above what the parameter set is made for, (msg carry - 1) / (msg - 1), is refused
+void hip_small_scalar_multiplication_integer_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array,
+                                                              uint64_t scalar, const uint32_t message_modulus,
+                                                              const uint32_t carry_modulus) {
+  first_gpu(streams);
+  HX_PANIC_IF_FALSE(lwe_array && lwe_array->ptr, "small_scalar_multiplication_integer: null radix ciphertext");
+  HX_PANIC_IF_FALSE(message_modulus >= 2 && carry_modulus >= 1, "small_scalar_multiplication_integer: invalid message modulus or carry modulus");
+  const uint64_t max_noise = ((uint64_t)message_modulus * carry_modulus - 1) / (message_modulus - 1);
+  for (uint32_t i = 0; i < lwe_array->num_radix_blocks; ++i)
+    if (lwe_array->noise_levels)
+      HX_PANIC_IF_FALSE(lwe_array->noise_levels[i] * scalar <= max_noise,
+                        "small_scalar_multiplication_integer: noise %llu exceeds maximum authorized value %llu",
+                        (unsigned long long)(lwe_array->noise_levels[i] * scalar), (unsigned long long)max_noise);
+  axpy(S0(streams), (uint64_t *)lwe_array->ptr, nullptr, (const uint64_t *)lwe_array->ptr, nullptr, scalar, nullptr, nullptr,
+       lwe_array->lwe_dimension + 1, lwe_array->num_radix_blocks);
+  for (uint32_t i = 0; i < lwe_array->num_radix_blocks; ++i) {
+    if (lwe_array->degrees) lwe_array->degrees[i] *= scalar;
+    if (lwe_array->noise_levels) lwe_array->noise_levels[i] *= scalar;
+  }
 }
 
 // ---- ciphertext compression (hip_ names: the reference-named compression symbols stay link stubs) ---------------------

@@ -252,6 +252,17 @@ SIGNATURES = {
     "hip_scratch_integer_grouped_oprf_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _b, _u32, _u32]),
     "hip_integer_grouped_oprf_64_async": (None, [_S, _R, _v, _u32, _v, _i8pp]),
     "hip_cleanup_integer_grouped_oprf_64": (None, [_S, _i8pp]),
+    # sum of a vector of ciphertexts; multiplication by a clear scalar
+    "hip_scratch_partial_sum_ciphertexts_vec_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _b, _b, _u32]),
+    "hip_partial_sum_ciphertexts_vec_64_async": (None, [_S, _R, _R, _v, _i8pp, _i8pp]),
+    "hip_cleanup_partial_sum_ciphertexts_vec_64": (None, [_S, _i8pp]),
+    "hip_partial_sum_ciphertexts_vec_pbs_count": (_u64, [_v]),
+    "hip_scratch_integer_scalar_mul_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_scalar_mul_64_async": (None, [_S, _R, _v, _v, _v, _i8pp, _i8pp, _u32, _u32, _u32]),
+    "hip_cleanup_integer_scalar_mul_64": (None, [_S, _i8pp]),
+    "hip_integer_scalar_mul_pbs_count": (_u64, [_v, _v, _u32]),
+    "hip_small_scalar_multiplication_integer_64_inplace_async": (None, [_S, _R, _u64, _u32, _u32]),
+    "hip_test_group_sum_async": (None, [_v, _u32, _u32, _v, _v, _v, _v, _u32, _u32]),
     # 128-bit PBS and noise squashing
     "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
     "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),

@@ -350,6 +350,68 @@ class CudaServerKey {
     cleanup_cuda_logical_scalar_shift_64_inplace(f.streams, &mem);
     return result;
   }
+  // scalar_mul.rs:67-110 `unchecked_scalar_mul_assign` behind the default form's propagation: 0 gives zero, 1 nothing, a power
+  // of two a left shift; otherwise the bit decomposition (least significant first) and the residues that hold a set bit
+  void scalar_mul_assign(CudaUnsignedRadixCiphertext &ct, uint64_t scalar, const CudaStreams &streams) const {
+    if (ct.num_blocks() == 0 || scalar == 1) return;
+    if (scalar == 0) {
+      cuda_memset_async(ct.d_blocks.as_mut_c_ptr(0), 0, ct.d_blocks.len * sizeof(uint64_t), streams.ptr[0], streams.gpu_indexes[0].get());
+      ct.degrees.assign(ct.num_blocks(), 0);
+      ct.noise_levels.assign(ct.num_blocks(), 0);
+      return;
+    }
+    if ((scalar & (scalar - 1)) == 0) {  // shifting costs one bivariate PBS per block, so it is always cheaper than multiplying
+      ct = scalar_shift(ct, (uint32_t)__builtin_ctzll(scalar), LEFT_SHIFT, streams);
+      return;
+    }
+    if (!ct.block_carries_are_empty()) propagate_single_carry_assign(ct, streams);
+    const uint32_t msg_bits = (uint32_t)__builtin_ctzll(message_modulus);
+    std::vector<uint64_t> decomposed, has_at_least_one_set(msg_bits, 0);
+    for (uint64_t s = scalar; s != 0; s >>= 1) {
+      if (s & 1) has_at_least_one_set[decomposed.size() % msg_bits] = 1;
+      decomposed.push_back(s & 1);
+    }
+    Ffi f(*this, streams);
+    const CudaLweBootstrapKeyParamsFFI b = bsk_params();
+    CudaRadixCiphertextFFI c = ct.ffi();
+    int8_t *mem = nullptr;
+    hip_scratch_integer_scalar_mul_64_async(f.streams, &mem, b, ksk_params(), (uint32_t)ct.num_blocks(), (uint32_t)message_modulus,
+                                            (uint32_t)carry_modulus, (uint32_t)decomposed.size(), true, noise_reduction());
+    hip_integer_scalar_mul_64_async(f.streams, &c, decomposed.data(), has_at_least_one_set.data(), mem, f.bsks.data(), f.ksks.data(),
+                                    b.polynomial_size, (uint32_t)message_modulus, (uint32_t)decomposed.size());
+    hip_cleanup_integer_scalar_mul_64(f.streams, &mem);
+  }
+  CudaUnsignedRadixCiphertext scalar_mul(const CudaUnsignedRadixCiphertext &ct, uint64_t scalar, const CudaStreams &streams) const {
+    CudaUnsignedRadixCiphertext result = ct.duplicate(streams);
+    scalar_mul_assign(result, scalar, streams);
+    return result;
+  }
+  // radix/mod.rs `unchecked_partial_sum_ciphertexts` / `sum_ciphertexts`: equal-width integers gathered [integer][block], summed
+  // column by column; with `reduce` the columns end at what one carry propagation accepts and the carries are propagated
+  std::optional<CudaUnsignedRadixCiphertext> sum_ciphertexts(const std::vector<CudaUnsignedRadixCiphertext> &cts, const CudaStreams &streams,
+                                                             bool reduce = true) const {
+    if (cts.empty()) return std::nullopt;
+    const size_t L = cts[0].num_blocks(), w = cts[0].lwe_dimension + 1;
+    CudaUnsignedRadixCiphertext vec = CudaUnsignedRadixCiphertext::zero(cts.size() * L, cts[0].lwe_dimension, message_modulus, carry_modulus, streams);
+    for (size_t i = 0; i < cts.size(); ++i) {
+      detail::assert_eq(cts[i].num_blocks(), L, "Mismatched number of blocks between the ciphertexts of a sum");
+      detail::assert_eq(cts[i].lwe_dimension, cts[0].lwe_dimension, "Mismatched lwe dimension between the ciphertexts of a sum");
+      cuda_memcpy_async_gpu_to_gpu((uint64_t *)vec.d_blocks.as_mut_c_ptr(0) + i * L * w, cts[i].d_blocks.as_c_ptr(0), L * w * sizeof(uint64_t),
+                                   streams.ptr[0], streams.gpu_indexes[0].get());
+      std::copy(cts[i].degrees.begin(), cts[i].degrees.end(), vec.degrees.begin() + (std::ptrdiff_t)(i * L));
+      std::copy(cts[i].noise_levels.begin(), cts[i].noise_levels.end(), vec.noise_levels.begin() + (std::ptrdiff_t)(i * L));
+    }
+    CudaUnsignedRadixCiphertext result = CudaUnsignedRadixCiphertext::zero(L, cts[0].lwe_dimension, message_modulus, carry_modulus, streams);
+    Ffi f(*this, streams);
+    CudaRadixCiphertextFFI o = result.ffi(), v = vec.ffi();
+    int8_t *mem = nullptr;
+    hip_scratch_partial_sum_ciphertexts_vec_64_async(f.streams, &mem, bsk_params(), ksk_params(), (uint32_t)L, (uint32_t)cts.size(),
+                                                     (uint32_t)message_modulus, (uint32_t)carry_modulus, reduce, true, noise_reduction());
+    hip_partial_sum_ciphertexts_vec_64_async(f.streams, &o, &v, mem, f.bsks.data(), f.ksks.data());
+    hip_cleanup_partial_sum_ciphertexts_vec_64(f.streams, &mem);
+    if (reduce && cts.size() > 1) propagate_single_carry_assign(result, streams);
+    return result;
+  }
 
   // radix/mod.rs apply_lookup_table: `lut` is the (k+1)*N accumulator of a shortint LookupTable, `degree` its maximum output
   CudaUnsignedRadixCiphertext apply_lookup_table(const CudaUnsignedRadixCiphertext &input, const std::vector<uint64_t> &lut, uint64_t degree,

@@ -360,6 +360,99 @@ class CudaServerKey:
         _lib().cleanup_cuda_integer_mult_inplace_64(s, C.byref(mem))
         return pbs if return_pbs_count else None
 
+    def scalar_mul_assign(self, ct, scalar, streams, return_pbs_count=False):
+        """ct *= scalar (mod 2^bits) on clean blocks, every integer of the batch by the same clear scalar
+        (radix/scalar_mul.rs:67-110 unchecked_scalar_mul_assign, with its shortcuts: 0 gives zero, 1 does nothing, a
+        power of two is a left shift).  Otherwise one round of shifted blocks, column sums, one carry propagation."""
+        scalar = int(scalar)
+        assert scalar >= 0
+        w = ct.lwe_dimension + 1
+        if scalar == 0:
+            _lib().cuda_memset_async(ct.d_blocks.ptr, 0, ct.total_blocks * w * 8, streams.ptr[0], streams.gpu_indexes[0])
+            ct._info[0][:] = 0
+            ct._info[1][:] = 0
+            return 0 if return_pbs_count else None
+        if scalar == 1 or ct.total_blocks == 0:
+            return 0 if return_pbs_count else None
+        msg_bits = self.message_modulus.bit_length() - 1
+        if scalar & (scalar - 1) == 0 and ct.num_integers == 1:
+            # shifting costs one bivariate PBS per block, so it is always cheaper than multiplying
+            shift = scalar.bit_length() - 1
+            self.scalar_shift_assign(ct, shift, streams, left=True)
+            survive = max(0, ct.num_blocks - shift // msg_bits)
+            return (survive if shift % msg_bits else 0) if return_pbs_count else None
+        bits = [(scalar >> i) & 1 for i in range(scalar.bit_length())]      # BlockDecomposer::with_early_stop_at_zero(scalar, 1)
+        has_at_least_one_set = np.zeros(msg_bits, dtype=U64)
+        for i, b in enumerate(bits):
+            if b:
+                has_at_least_one_set[i % msg_bits] = 1
+        decomposed = np.ascontiguousarray(bits, dtype=U64)
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        mem = C.c_void_p()
+        _lib().hip_integer_scratch_batch(ct.num_integers)
+        _lib().hip_scratch_integer_scalar_mul_64_async(
+            s, C.byref(mem), self._bsk_params(), self._ksk_params(), ct.num_blocks, self.message_modulus,
+            self.carry_modulus, len(bits), True, self._noise_reduction())
+        _lib().hip_integer_scratch_batch(1)
+        pbs = int(_lib().hip_integer_scalar_mul_pbs_count(mem, decomposed.ctypes.data_as(C.c_void_p), len(bits)))
+        _lib().hip_integer_scalar_mul_64_async(
+            s, C.byref(ct._ffi()), decomposed.ctypes.data_as(C.c_void_p), has_at_least_one_set.ctypes.data_as(C.c_void_p),
+            mem, bsks, ksks, self.bootstrapping_key.polynomial_size, self.message_modulus, len(bits))
+        _lib().hip_cleanup_integer_scalar_mul_64(s, C.byref(mem))
+        return pbs if return_pbs_count else None
+
+    def unchecked_scalar_mul(self, ct, scalar, streams):
+        """The copying form of scalar_mul_assign (scalar_mul.rs:50-65): `ct` is left as it is."""
+        out = ct.duplicate(streams)
+        out._info[0][:] = ct._info[0]
+        out._info[1][:] = ct._info[1]
+        self.scalar_mul_assign(out, scalar, streams)
+        return out
+
+    def unchecked_partial_sum_ciphertexts(self, vec, streams, reduce=False, out=None, max_num_radix_in_vec=None,
+                                          return_pbs_count=False):
+        """The raw call (integer/gpu/mod.rs cuda_backend_unchecked_partial_sum_ciphertexts_assign): `vec` holds V
+        integers, [v][block]; their blocks are added column by column, with message / carry rounds wherever a column
+        would outgrow a block.  Without `reduce` the output blocks may be as large as a block holds; with it they end at
+        what one carry propagation accepts.  `out` (one integer) may be a view of the first integer of `vec`.  Degrees
+        and noise levels of the result are written back."""
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        if out is None:
+            out = CudaUnsignedRadixCiphertext(CudaVec(vec.num_blocks * (vec.lwe_dimension + 1), streams), 1, vec.num_blocks,
+                                              vec.lwe_dimension)
+        mem = C.c_void_p()
+        cap = vec.num_integers if max_num_radix_in_vec is None else int(max_num_radix_in_vec)
+        _lib().hip_scratch_partial_sum_ciphertexts_vec_64_async(
+            s, C.byref(mem), self._bsk_params(), self._ksk_params(), vec.num_blocks, cap, self.message_modulus,
+            self.carry_modulus, bool(reduce), True, self._noise_reduction())
+        _lib().hip_partial_sum_ciphertexts_vec_64_async(s, C.byref(out._ffi()), C.byref(vec._ffi()), mem, bsks, ksks)
+        pbs = int(_lib().hip_partial_sum_ciphertexts_vec_pbs_count(mem))
+        _lib().hip_cleanup_partial_sum_ciphertexts_vec_64(s, C.byref(mem))
+        return (out, pbs) if return_pbs_count else out
+
+    def sum_ciphertexts(self, cts, streams, reduce=True):
+        """Sum of a list of one-integer ciphertexts of equal width (radix/mod.rs unchecked_sum_ciphertexts); with
+        `reduce` the carries are propagated and the result is clean.  None for an empty list."""
+        if not cts:
+            return None
+        L, n = cts[0].num_blocks, cts[0].lwe_dimension
+        assert all(c.num_integers == 1 and c.num_blocks == L and c.lwe_dimension == n for c in cts)
+        w = n + 1
+        vec = CudaUnsignedRadixCiphertext(CudaVec(len(cts) * L * w, streams), len(cts), L, n)
+        for i, c in enumerate(cts):
+            _lib().cuda_memcpy_async_gpu_to_gpu(vec.d_blocks.ptr + i * L * w * 8, c.d_blocks.ptr, L * w * 8, streams.ptr[0],
+                                                streams.gpu_indexes[0])
+            vec._info[0][i * L:(i + 1) * L] = c._info[0]
+            vec._info[1][i * L:(i + 1) * L] = c._info[1]
+        out = self.unchecked_partial_sum_ciphertexts(vec, streams, reduce=reduce)
+        if reduce and len(cts) > 1:
+            if len(cts) == 2:    # a plain addition: the blocks hold what the operands held
+                assert int(out.degrees.max(initial=0)) <= 2 * self.message_modulus - 2, "sum_ciphertexts: operands are not clean"
+            self.propagate_single_carry_assign(out, streams)
+        return out
+
 
     def mul_by_boolean_assign(self, ct, boolean, streams, boolean_is_left=False):
         """ct <- boolean ? ct : 0, block by block (integer_mult with is_boolean_right; with boolean_is_left the
@@ -1026,3 +1119,33 @@ class CudaOprfServerKey:
             zeros, key = rerand
             out.re_randomize(zeros, key, streams)
         return out
+
+    def generate_oblivious_pseudo_random_unsigned_custom_range(self, seeded_lwes, num_input_random_bits,
+                                                               excluded_upper_bound, num_blocks_output, server_key, streams,
+                                                               rerand=None):
+        """oprf.rs par_generate_oblivious_pseudo_random_unsigned_custom_range, the flow of cuda/src/integer/oprf.cuh:127-176
+        as a composition of this layer's operations: `num_input_random_bits` oblivious random bits r (re-randomised when
+        `rerand` is given), extended with zero blocks to ceil((num_input_random_bits + bit length of the bound) /
+        message bits) blocks, multiplied by the bound, shifted right by num_input_random_bits, then truncated or
+        zero-extended to `num_blocks_output` blocks: (r * bound) >> num_input_random_bits, a value below the bound."""
+        bound, nbits = int(excluded_upper_bound), int(num_input_random_bits)
+        assert bound >= 1 and nbits >= 1 and num_blocks_output >= 1
+        msg_bits = server_key.message_modulus.bit_length() - 1
+        ct = self.generate_oblivious_pseudo_random_bits(seeded_lwes, nbits, server_key, streams, rerand=rerand)
+        inter = -(-(nbits + bound.bit_length()) // msg_bits)
+        w = ct.lwe_dimension + 1
+
+        def resized(src, blocks):
+            """the first `blocks` blocks of src, zero blocks (degree 0) behind them"""
+            dst = CudaUnsignedRadixCiphertext(CudaVec(blocks * w, streams), 1, blocks, src.lwe_dimension)
+            keep = min(blocks, src.num_blocks)
+            _lib().cuda_memcpy_async_gpu_to_gpu(dst.d_blocks.ptr, src.d_blocks.ptr, keep * w * 8, streams.ptr[0],
+                                                streams.gpu_indexes[0])
+            dst._info[0][:], dst._info[1][:] = 0, 0
+            dst._info[0][:keep], dst._info[1][:keep] = src._info[0][:keep], src._info[1][:keep]
+            return dst
+
+        work = resized(ct, inter)
+        server_key.scalar_mul_assign(work, bound, streams)
+        server_key.scalar_shift_assign(work, nbits, streams, left=False)
+        return work if num_blocks_output == inter else resized(work, num_blocks_output)
