@@ -911,6 +911,78 @@ void hip_small_scalar_multiplication_integer_64_inplace_async(
 void hip_test_group_sum_async(void *stream, uint32_t gpu_index, uint32_t which, void *out, void const *pool,
                               void const *offsets, void const *members, uint32_t words, uint32_t groups);
 
+/* ------------------------------------------------------------------ shifts and rotations (extensions)
+ * cuda/include/integer/integer.h:212-228 (arithmetic shift by a clear amount), :367-381 (rotation by a clear amount) and
+ * :230-244 (shift / rotation by an encrypted amount) under hip_ names with the reference's parameter lists; the
+ * reference-named symbols remain link stubs.  All three work in place on clean blocks; lwe_array may hold a batch of
+ * integers of num_blocks blocks (hip_integer_scratch_batch before the scratch call), lwe_shift then holds as many.
+ * Signed values are two's complement in the same blocks.
+ * arithmetic_scalar_shift: RIGHT_SHIFT only (LEFT_SHIFT is refused: it is the logical shift).  A move by whole blocks and
+ *   one round; shift = 0 does nothing, shift >= bits turns every block into the sign's padding block, one bit per block
+ *   needs no bootstrap.
+ * scalar_rotate: LEFT_ROTATE / RIGHT_ROTATE by n mod bits; a rotation by whole blocks and, when bits remain, one round.
+ * shift_and_rotate: shift_type LEFT_SHIFT / RIGHT_SHIFT / LEFT_ROTATE / RIGHT_ROTATE, is_signed makes RIGHT_SHIFT
+ *   arithmetic.  Needs message_modulus * carry_modulus >= 8 and a power of two as message modulus; the shifts also what
+ *   the unsigned comparison needs (16 values per block).  A shift by bits or more gives 0 (all ones for a negative
+ *   arithmetic operand).  A rotation rotates by (amount mod 2^m) mod bits, m = ceil(log2 bits): when bits is no power of
+ *   two the m control bits capture amounts up to 2^m - 1, as in the reference's GPU code.  Outputs are clean (degree
+ *   message_modulus - 1, noise level 1); lwe_shift is not written.
+ * hip_integer_shift_and_rotate_pbs_count: bootstraps per integer of one call on that scratch. */
+uint64_t hip_scratch_integer_arithmetic_scalar_shift_64_inplace_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus,
+    enum SHIFT_OR_ROTATE_TYPE shift_type, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_arithmetic_scalar_shift_64_inplace_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array, uint32_t shift,
+    int8_t *mem_ptr, void *const *bsks, void *const *ksks);
+void hip_cleanup_integer_arithmetic_scalar_shift_64_inplace(CudaStreamsFFI streams,
+                                                            int8_t **mem_ptr_void);
+uint64_t hip_scratch_integer_scalar_rotate_64_inplace_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus,
+    enum SHIFT_OR_ROTATE_TYPE shift_type, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_scalar_rotate_64_inplace_async(CudaStreamsFFI streams,
+                                                CudaRadixCiphertextFFI *lwe_array,
+                                                uint32_t n, int8_t *mem_ptr,
+                                                void *const *bsks, void *const *ksks);
+void hip_cleanup_integer_scalar_rotate_64_inplace(CudaStreamsFFI streams,
+                                                  int8_t **mem_ptr_void);
+uint64_t hip_scratch_integer_shift_and_rotate_64_inplace_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus,
+    enum SHIFT_OR_ROTATE_TYPE shift_type, bool is_signed, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_shift_and_rotate_64_inplace_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array,
+    CudaRadixCiphertextFFI const *lwe_shift, int8_t *mem_ptr, void *const *bsks,
+    void *const *ksks);
+void hip_cleanup_integer_shift_and_rotate_64_inplace(CudaStreamsFFI streams,
+                                                     int8_t **mem_ptr_void);
+uint64_t hip_integer_shift_and_rotate_pbs_count(int8_t *mem_ptr);
+/* tests, benches: the fused rotate-and-pack kernel alone.  out[c rows + i] = s0 x[c rows + i] + s1 pick(i) + (ctrl ?
+ * ctrl[c ctrl_stride + ctrl_row] : 0) on u64 words; pick(i) is row i - r (dir = 0) or i + r (dir = 1) of integer c, a row
+ * outside the integer taken modulo rows (mode = 0), nothing (mode = 1) or pad[c pad_stride + pad_row] (mode = 2).
+ * 0 <= r < rows; out must not overlap x. */
+void hip_test_rotate_pack_async(void *stream, uint32_t gpu_index, void *out, void const *x, void const *pad,
+                                void const *ctrl, uint64_t s0, uint64_t s1, uint32_t words, uint32_t rows, uint32_t batch,
+                                uint32_t r, uint32_t dir, uint32_t mode, uint32_t pad_stride, uint32_t pad_row,
+                                uint32_t ctrl_stride, uint32_t ctrl_row);
+/* benches: the same rows for s0 = 1, composed from a device copy, block copies, a memset or single-row copies and two
+ * axpy launches (what a barrel stage took before the kernel).  tmp: 2 * batch * rows rows of scratch; ctrl_idx: batch * rows
+ * entries c * ctrl_stride + ctrl_row on the device (read when ctrl is given). */
+void hip_test_rotate_pack_baseline_async(void *stream, uint32_t gpu_index, void *out, void const *x, void const *pad,
+                                         void const *ctrl, void const *ctrl_idx, void *tmp, uint64_t s1, uint32_t words,
+                                         uint32_t rows, uint32_t batch, uint32_t r, uint32_t dir, uint32_t mode,
+                                         uint32_t pad_stride, uint32_t pad_row);
+
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's
  * cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103 and cuda/include/fft/fft128.h), under hip_ names

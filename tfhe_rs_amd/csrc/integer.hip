@@ -22,6 +22,7 @@
 #include "profile.h"
 #include "scratch.h"
 #include "radix_sum.h"
+#include "radix_rotate.h"
 #include "../../include/tfhe_hip_backend.h"
 
 #include <algorithm>
@@ -234,6 +235,7 @@ struct LutDriver {
                       // casts from another key (compact-list expansion)
   bool no_ks = false;  // the round bootstraps its inputs as they are (dimension in_n = p.small_n): no keyswitch, no
                        // keyswitch key (oblivious random bits)
+  mutable uint64_t issued = 0;  // bootstraps of all rounds so far (the operations that publish a count check it against this)
   struct PerGpu {
     uint32_t gpu = 0;
     uint64_t *d_ks = nullptr, *d_luts = nullptr, *d_trivial = nullptr;  // d_trivial = 0, 1, ..., cap - 1
@@ -339,6 +341,7 @@ struct LutDriver {
   void round_many(const CudaStreamsFFI &s, uint64_t *out, const uint64_t *in, const uint64_t *lut_idx, uint32_t count,
                   void *const *ksks, void *const *bsks, uint32_t many, uint32_t stride) const {
     HX_PANIC_IF_FALSE(count <= cap, "apply_many_univariate_lut: more blocks than the scratch was created for");
+    issued += count;
     HX_CHECK(hipSetDevice((int)gpus[0].gpu));
     ks_pbs((hipStream_t)s.streams[0], gpus[0], out, gpus[0].d_trivial, in, gpus[0].d_trivial, lut_idx, count, ksks[0],
            bsks[0], many, stride);
@@ -368,6 +371,7 @@ struct LutDriver {
     HX_PANIC_IF_FALSE(no_ks || ksks != nullptr, "radix layer: null keyswitch key array");
     const auto ksk_of = [&](uint32_t i) -> const void * { return no_ks ? nullptr : ksks[i]; };
     HX_RANGE("apply lut round (%u blocks)", count);  // integer.cuh:874
+    issued += count;
     for (uint32_t off = 0; off < count; off += cap) {
       const uint32_t c = std::min(cap, count - off);
       // helper_multi_gpu.cu:39-48 (get_active_gpu_count): as many GPUs as the round can keep busy
@@ -1453,6 +1457,313 @@ static void check_clean(std::initializer_list<const CudaRadixCiphertextFFI *> op
         HX_PANIC_IF_FALSE(op->degrees[i] <= msg - 1, "%s: block %u has degree %llu, %s", who, i,
                           (unsigned long long)op->degrees[i], tail);
 }
+
+// ------------------------------------------------------------------ shifts and rotations
+// uploads an index array of a call (kept alive by the scratch) in place of the one it held
+static void replace_upload(hipStream_t st, uint64_t *&d, const std::vector<uint64_t> &h) {
+  if (d) {
+    HX_CHECK(hipStreamSynchronize(st));  // an earlier call may still read it
+    scratch_free(d);
+  }
+  d = dev_upload(st, h);
+}
+
+// shift_and_rotate.cuh / integer.h:230-244: shift or rotation by an ENCRYPTED amount, a barrel shifter over the bits.
+// b = log2(msg) bits per block, L blocks, B = b L bits, m = ceil(log2 B) control bits.  Rounds of one call, every
+// integer of the batch in the same rounds:
+//   1. value bits: B rows per integer, bit i of block j -> {0, 1} (the driver's input index reads block j b times)
+//   2. control bits: the m low bits of the amount, each already at plaintext position 2 (value 4 bit)
+//   3. m stages: ONE lwe_rotate_pack_kernel launch forms ctrl_d + 2 src(i, 2^d) + cur(i) for every bit row — src wraps
+//      (rotations), is nothing (shifts) or the sign row as step 1 extracted it (arithmetic right shift) — and one round
+//      of B rows applies the mux table (x & 7 = 4 c + 2 p + a -> c ? p : a)
+//   4. shifts only: "amount >= B" from the unsigned comparison against the clear digits of B (one pass per integer), for
+//      the arithmetic shift 2 overshift + sign; one round of one row per integer moves it into the carry
+//   5. reassembly: from each block's top bit, b - 1 times block = 2 block + next lower bit and a cleaning round; the last
+//      one takes the packed condition on top and the overshift table instead.  b = 1: no loop, the cleanup (shifts only)
+//      is a round of its own.
+// A rotation rotates by (amount mod 2^m) mod B: when B is no power of two the m control bits capture amounts up to
+// 2^m - 1 >= B and the barrel stages compose to a rotation by that many positions, which is what the reference's GPU code
+// computes.
+// Bootstraps per integer: B + m + m B + (shifts: comparison + 1) + (b > 1 ? (b - 1) L : shifts ? L : 0).
+// Differences from the reference: at msg = 2 the amount's bit blocks are paired into base-4 digits before the comparison
+// (the carry look-ahead behind GE takes digits of two bits and more; the reference pairs blocks inside its comparison), and
+// the table that moves the condition into the carry keeps two bits, (x & 3) msg — at msg = 2 the reference's (x % msg) msg
+// drops the overshift bit of an arithmetic shift; from msg = 4 on the two tables are the same.
+struct ShiftRotateMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x53525431;  // "SRT1"
+  LutDriver drv;  // LUTs: i: bit i; b + i: bit i at position 2; 2 b: mux; + 1: x % msg; + 2: condition into the carry; + 3: cleanup
+  CompareMem cmp;
+  uint32_t blocks = 0, bits = 0, total = 0, ctrl = 0, max_cts = 0, type = 0;
+  bool arithmetic = false, overshift = false, pairs = false;
+  uint32_t cmp_blocks = 0;  // digits the comparison sees (paired at msg = 2, padded to an even count)
+  uint64_t *d_bits = nullptr, *d_cur = nullptr, *d_pack = nullptr, *d_ctrl = nullptr, *d_cond = nullptr,
+           *d_padded = nullptr, *d_triv = nullptr;
+  // index arrays, [integer][row] so that a call with fewer integers reads a prefix
+  uint64_t *i_bits_in = nullptr, *i_bits_lut = nullptr, *i_ctrl_in = nullptr, *i_ctrl_lut = nullptr, *i_const = nullptr,
+           *i_sign = nullptr, *i_top = nullptr, *i_bit = nullptr, *i_cond = nullptr, *i_hi = nullptr, *i_lo = nullptr;
+
+  bool shift() const { return type == LEFT_SHIFT || type == RIGHT_SHIFT; }
+  uint64_t compare_pbs() const {
+    if (!overshift) return 0;
+    return cmp_blocks == 1 ? 1 : PropagateMem::pbs_count(cmp_blocks) - cmp_blocks + 1;  // no result round, the flag
+  }
+  uint64_t pbs_count() const {
+    return (uint64_t)total + ctrl + (uint64_t)ctrl * total + (overshift ? compare_pbs() + 1 : 0) +
+           (bits > 1 ? (uint64_t)(bits - 1) * blocks : overshift ? blocks : 0);
+  }
+
+  void init(const CudaStreamsFFI &ss, const Params &p, uint32_t L, uint32_t cts, uint32_t shift_type, bool is_signed) {
+    HX_PANIC_IF_FALSE(L >= 1 && cts >= 1, "shift_and_rotate: no blocks");
+    HX_PANIC_IF_FALSE(shift_type <= RIGHT_ROTATE, "shift_and_rotate: unknown shift type %u", shift_type);
+    HX_PANIC_IF_FALSE((p.msg & (p.msg - 1)) == 0, "shift_and_rotate: the message modulus must be a power of two");
+    // the mux packs control | previous | current into one block: three bits
+    HX_PANIC_IF_FALSE(p.msg * p.carry >= 8, "shift_and_rotate: message_modulus * carry_modulus >= 8 is required (got %u)",
+                      p.msg * p.carry);
+    blocks = L, max_cts = cts, type = shift_type;
+    bits = (uint32_t)__builtin_ctz(p.msg);
+    total = bits * L;
+    ctrl = 0;
+    while ((1u << ctrl) < total) ++ctrl;
+    overshift = shift();
+    arithmetic = is_signed && shift_type == RIGHT_SHIFT;
+    const uint32_t b = bits, B = total, m = ctrl;
+    const uint64_t msg = p.msg;
+    const size_t lw = (size_t)(p.k + 1) * p.N, w = (size_t)p.big_n + 1;
+    std::vector<std::vector<uint64_t>> luts(2 * b + 4, std::vector<uint64_t>(lw));
+    for (uint32_t i = 0; i < b; ++i) {
+      generate_lut(p, luts[i].data(), [i](uint64_t x) -> uint64_t { return (x >> i) & 1; });
+      generate_lut(p, luts[b + i].data(), [i](uint64_t x) -> uint64_t { return ((x >> i) & 1) << 2; });
+    }
+    generate_lut(p, luts[2 * b].data(), [](uint64_t x) -> uint64_t { return (x & 4) ? (x >> 1) & 1 : x & 1; });
+    generate_lut(p, luts[2 * b + 1].data(), [msg](uint64_t x) -> uint64_t { return x % msg; });
+    generate_lut(p, luts[2 * b + 2].data(), [msg](uint64_t x) -> uint64_t { return (x & 3) * msg; });
+    const bool arith = arithmetic;
+    generate_lut(p, luts[2 * b + 3].data(), [msg, arith](uint64_t x) -> uint64_t {
+      const uint64_t c = x / msg, v = x % msg;
+      if (arith) return c == 3 ? msg - 1 : c == 2 ? 0 : v;
+      return c >= 1 ? 0 : v;
+    });
+    const uint32_t rows = cts * std::max(B, L);
+    drv.init(ss, p, std::min<uint32_t>(rows, 1u << 16), luts);
+    radix_alloc((void **)&d_bits, (size_t)cts * B * w * sizeof(uint64_t));
+    radix_alloc((void **)&d_cur, (size_t)cts * B * w * sizeof(uint64_t));
+    radix_alloc((void **)&d_pack, (size_t)cts * B * w * sizeof(uint64_t));
+    radix_alloc((void **)&d_ctrl, (size_t)cts * std::max(1u, m) * w * sizeof(uint64_t));
+    const hipStream_t st = S0(ss);
+    std::vector<uint64_t> bi((size_t)cts * B), bl((size_t)cts * B), ci((size_t)cts * m), cl((size_t)cts * m),
+        top((size_t)cts * L), bit((size_t)std::max(1u, b - 1) * cts * L), cond((size_t)cts * L), sign(cts);
+    for (uint32_t c = 0; c < cts; ++c) {
+      for (uint32_t j = 0; j < L; ++j) {
+        for (uint32_t i = 0; i < b; ++i) bi[(size_t)c * B + j * b + i] = (uint64_t)c * L + j, bl[(size_t)c * B + j * b + i] = i;
+        top[(size_t)c * L + j] = (uint64_t)c * B + j * b + b - 1;
+        for (uint32_t i = 0; i + 1 < b; ++i) bit[((size_t)i * cts + c) * L + j] = (uint64_t)c * B + j * b + i;
+        cond[(size_t)c * L + j] = c;
+      }
+      for (uint32_t d = 0; d < m; ++d) ci[(size_t)c * m + d] = (uint64_t)c * L + d / b, cl[(size_t)c * m + d] = b + d % b;
+      sign[c] = (uint64_t)c * B + B - 1;
+    }
+    i_bits_in = dev_upload(st, bi), i_bits_lut = dev_upload(st, bl);
+    i_ctrl_in = dev_upload(st, ci), i_ctrl_lut = dev_upload(st, cl);
+    i_top = dev_upload(st, top), i_bit = dev_upload(st, bit), i_cond = dev_upload(st, cond), i_sign = dev_upload(st, sign);
+    // constant LUT indexes: [2 b] * rows (mux), then + 1, + 2, + 3 on cts L rows each
+    std::vector<uint64_t> k((size_t)cts * B + 3 * (size_t)cts * L);
+    for (size_t i = 0; i < k.size(); ++i) k[i] = i < (size_t)cts * B ? 2 * b : 2 * b + 1 + (i - (size_t)cts * B) / ((size_t)cts * L);
+    i_const = dev_upload(st, k);
+    if (!overshift) return;
+    // "amount >= B" on the clear digits of B
+    pairs = p.msg == 2;
+    const uint32_t digits = pairs ? (L + 1) / 2 : L;
+    cmp_blocks = (digits > 1 && digits % 2) ? digits + 1 : digits;
+    Params pc = p;
+    if (pairs) pc.msg = 4, pc.carry = p.msg * p.carry / 4;  // the same plaintext space, read as digits of two bits
+    cmp.init(ss, pc, cmp_blocks, GE);
+    radix_alloc((void **)&d_cond, (size_t)cts * w * sizeof(uint64_t));
+    if (pairs || cmp_blocks != L) radix_alloc((void **)&d_padded, (size_t)cmp_blocks * w * sizeof(uint64_t));
+    std::vector<uint64_t> triv((size_t)cmp_blocks * w, 0);
+    uint64_t v = B;
+    for (uint32_t i = 0; i < cmp_blocks; ++i, v /= pc.msg) triv[(size_t)i * w + w - 1] = (v % pc.msg) * p.delta();
+    HX_PANIC_IF_FALSE(v == 0, "shift_and_rotate: the bit count %u does not fit %u digits", B, cmp_blocks);
+    d_triv = dev_upload(st, triv);
+    if (pairs) {
+      std::vector<uint64_t> hi(L / 2), lo(L / 2);
+      for (uint32_t i = 0; i < L / 2; ++i) hi[i] = 2 * i + 1, lo[i] = 2 * i;
+      i_hi = dev_upload(st, hi), i_lo = dev_upload(st, lo);
+    }
+  }
+
+  void run(const CudaStreamsFFI &ss, uint64_t *v, const uint64_t *amount, uint32_t cts, void *const *ksks,
+           void *const *bsks) {
+    const Params &p = drv.p;
+    const hipStream_t st = S0(ss);
+    const uint32_t L = blocks, b = bits, B = total, m = ctrl, w = p.big_n + 1;
+    const uint64_t before = drv.issued + (overshift ? cmp.prop.drv.issued : 0);
+    HX_RANGE("shift / rotate by an encrypted amount: %u integers of %u bits", cts, B);
+    drv.round(ss, d_bits, nullptr, v, i_bits_in, i_bits_lut, cts * B, ksks, bsks);
+    if (m) drv.round(ss, d_ctrl, nullptr, amount, i_ctrl_in, i_ctrl_lut, cts * m, ksks, bsks);
+    const uint64_t *cur = d_bits;
+    for (uint32_t d = 0; d < m; ++d) {
+      RotatePack a{};
+      a.out = d_pack, a.x = cur, a.pad = d_bits, a.ctrl = d_ctrl;
+      a.s0 = 1, a.s1 = 2, a.words = w, a.rows = B, a.r = 1u << d;
+      a.dir = (type == LEFT_SHIFT || type == LEFT_ROTATE) ? kTowardsHigher : kTowardsLower;
+      a.mode = !shift() ? kPickWrap : arithmetic ? kPickRow : kPickZero;
+      a.pad_stride = B, a.pad_row = B - 1, a.ctrl_stride = m, a.ctrl_row = d;
+      launch_rotate_pack(st, a, cts);
+      drv.round(ss, d_cur, nullptr, d_pack, nullptr, i_const, cts * B, ksks, bsks);
+      cur = d_cur;
+    }
+    if (overshift) {
+      for (uint32_t c = 0; c < cts; ++c) {
+        const uint64_t *am = amount + (size_t)c * L * w;
+        if (d_padded) {
+          HX_CHECK(hipMemsetAsync(d_padded, 0, (size_t)cmp_blocks * w * sizeof(uint64_t), st));
+          if (pairs) {
+            axpy(st, d_padded, nullptr, am, i_hi, 2, am, i_lo, w, L / 2);
+            if (L % 2)
+              HX_CHECK(hipMemcpyAsync(d_padded + (size_t)(L / 2) * w, am + (size_t)(L - 1) * w, w * sizeof(uint64_t),
+                                      hipMemcpyDeviceToDevice, st));
+          } else {
+            HX_CHECK(hipMemcpyAsync(d_padded, am, (size_t)L * w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+          }
+          am = d_padded;
+        }
+        cmp.run(ss, d_cond + (size_t)c * w, am, d_triv, ksks, bsks);
+      }
+      if (arithmetic) axpy(st, d_cond, nullptr, d_cond, nullptr, 2, d_bits, i_sign, w, cts);
+      drv.round(ss, d_cond, nullptr, d_cond, nullptr, i_const + (size_t)max_cts * B + 1 * (size_t)max_cts * L, cts, ksks, bsks);
+    }
+    const uint64_t *clean = i_const + (size_t)max_cts * B, *cleanup = clean + 2 * (size_t)max_cts * L;
+    if (b == 1) {
+      HX_CHECK(hipMemcpyAsync(v, cur, (size_t)cts * L * w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+      if (overshift) {
+        axpy(st, v, nullptr, v, nullptr, 1, d_cond, i_cond, w, cts * L);
+        drv.round(ss, v, nullptr, v, nullptr, cleanup, cts * L, ksks, bsks);
+      }
+    }
+    for (uint32_t i = b - 1; i-- > 0;) {
+      const uint64_t *low = i_bit + (size_t)i * max_cts * L;
+      if (i == b - 2) axpy(st, v, nullptr, cur, i_top, 2, cur, low, w, cts * L);
+      else axpy(st, v, nullptr, v, nullptr, 2, cur, low, w, cts * L);
+      const bool last = i == 0 && overshift;
+      if (last) axpy(st, v, nullptr, v, nullptr, 1, d_cond, i_cond, w, cts * L);
+      drv.round(ss, v, nullptr, v, nullptr, last ? cleanup : clean, cts * L, ksks, bsks);
+    }
+    const uint64_t after = drv.issued + (overshift ? cmp.prop.drv.issued : 0);
+    HX_PANIC_IF_FALSE(after - before == cts * pbs_count(), "shift_and_rotate: %llu bootstraps issued, %llu counted",
+                      (unsigned long long)(after - before), (unsigned long long)(cts * pbs_count()));
+  }
+
+  void release(const CudaStreamsFFI &ss) {
+    HX_CHECK(hipStreamSynchronize(S0(ss)));
+    drv.release(ss);
+    if (overshift) cmp.release(ss);
+    for (uint64_t *d : {d_bits, d_cur, d_pack, d_ctrl, d_cond, d_padded, d_triv, i_bits_in, i_bits_lut, i_ctrl_in,
+                        i_ctrl_lut, i_const, i_sign, i_top, i_bit, i_cond, i_hi, i_lo})
+      if (d) scratch_free(d);
+  }
+};
+
+// scalar_shifts.cuh / integer.h:212-228: arithmetic right shift of a two's complement integer by a clear amount.  A move
+// by q = shift / b whole blocks, then ONE round whose rows carry their own table (the reference runs them on three
+// streams): the n - 1 surviving (block, upper neighbour) pairs the in-block shift, the last surviving block the shift
+// with sign fill, one more row the padding block (msg - 1) sign, which is then written to the q vacated top blocks.
+// shift >= B: every block is the padding block.  b = 1: no bootstrap, the sign block is copied.
+struct ArithShiftMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x41534831;  // "ASH1"
+  LutDriver drv;  // LUTs: r - 1: in-block shift by r; (b - 1) + r - 1: the same with sign fill (univariate); 2 (b - 1): padding
+  uint32_t blocks = 0, bits = 0, max_cts = 0;
+  uint64_t *d_pack = nullptr;  // [integer][L + 1]: the rows of the round, row L the padding row's input
+  uint64_t *i_in = nullptr, *i_out = nullptr, *i_lut = nullptr, *i_from = nullptr, *i_to = nullptr;  // of the cached call
+  uint32_t key_shift = ~0u, key_cts = 0, round_rows = 0, fill_rows = 0;
+
+  void init(const CudaStreamsFFI &ss, const Params &p, uint32_t L, uint32_t cts) {
+    HX_PANIC_IF_FALSE(L >= 1 && cts >= 1, "arithmetic_scalar_shift: no blocks");
+    HX_PANIC_IF_FALSE((p.msg & (p.msg - 1)) == 0, "arithmetic_scalar_shift: the message modulus must be a power of two");
+    blocks = L, max_cts = cts;
+    bits = (uint32_t)__builtin_ctz(p.msg);
+    const uint32_t msg = p.msg, b = bits;
+    std::vector<std::vector<uint64_t>> luts(2 * (b - 1) + 1, std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
+    for (uint32_t r = 1; r < b; ++r) {
+      generate_lut(p, luts[r - 1].data(), shift_in_block(msg, b, r, false));
+      generate_lut(p, luts[b - 1 + r - 1].data(), [msg, b, r](uint64_t x) -> uint64_t {
+        const uint64_t v = x % msg, sign = v >> (b - 1);
+        return ((v >> r) | (sign ? (uint64_t)(msg - 1) << (b - r) : 0)) % msg;
+      });
+    }
+    generate_lut(p, luts[2 * (b - 1)].data(), [msg, b](uint64_t x) -> uint64_t { return (msg - 1) * ((x % msg) >> (b - 1)); });
+    drv.init(ss, p, cts * (L + 1), luts);
+    radix_alloc((void **)&d_pack, (size_t)cts * (L + 1) * (p.big_n + 1) * sizeof(uint64_t));
+  }
+
+  // the rows of the call's round and of the fill that follows it; n blocks survive, r bits remain
+  void plan(hipStream_t st, uint32_t shift, uint32_t cts, uint32_t n, uint32_t r) {
+    if (key_shift == shift && key_cts == cts) return;
+    const uint32_t L = blocks, b = bits;
+    std::vector<uint64_t> in, out, lut, from, to;
+    for (uint32_t c = 0; c < cts; ++c) {
+      if (b > 1) {
+        for (uint32_t j = 0; j < n && r; ++j) {
+          in.push_back((uint64_t)c * (L + 1) + j), out.push_back((uint64_t)c * L + j);
+          lut.push_back(j + 1 < n ? r - 1 : b - 1 + r - 1);
+        }
+        if (n < L) in.push_back((uint64_t)c * (L + 1) + L), out.push_back((uint64_t)c * L + n), lut.push_back(2 * (b - 1));
+        for (uint32_t t = n + 1; t < L; ++t) from.push_back((uint64_t)c * L + n), to.push_back((uint64_t)c * L + t);
+      } else {  // one bit per block: block t takes block t + q, the sign block beyond the end (rows of d_pack)
+        for (uint32_t t = 0; t < L; ++t)
+          from.push_back((uint64_t)c * (L + 1) + std::min(t + (L - n), L - 1)), to.push_back((uint64_t)c * L + t);
+      }
+    }
+    replace_upload(st, i_in, in), replace_upload(st, i_out, out), replace_upload(st, i_lut, lut);
+    replace_upload(st, i_from, from), replace_upload(st, i_to, to);
+    round_rows = (uint32_t)in.size(), fill_rows = (uint32_t)from.size();
+    key_shift = shift, key_cts = cts;
+  }
+
+  void release(const CudaStreamsFFI &ss) {
+    HX_CHECK(hipStreamSynchronize(S0(ss)));
+    drv.release(ss);
+    for (uint64_t *d : {d_pack, i_in, i_out, i_lut, i_from, i_to})
+      if (d) scratch_free(d);
+  }
+};
+
+// scalar_rotate.cuh / integer.h:367-381: rotation by a clear amount.  n mod B first; a rotation by q = n / b whole blocks,
+// which wraps, and when r = n mod b bits remain ONE bivariate round over all L blocks with the wrapping neighbour (the
+// tables of the logical shift).  lwe_rotate_pack_kernel builds msg block + neighbour in wrap mode from the blocks where
+// they are, and the round's output index performs the block rotation: no temporary rotation, no second copy.
+struct ScalarRotateMem : ScratchHeader {
+  static constexpr uint32_t kMagic = 0x53524F31;  // "SRO1"
+  LutDriver drv;  // LUT r - 1: the shift by r bits inside a block, this scratch's direction
+  uint32_t blocks = 0, bits = 0, left = 0, max_cts = 0;
+  uint64_t *d_pack = nullptr, *i_lut = nullptr, *i_out = nullptr;  // i_lut: [r - 1][integer][block]; i_out: [q][integer][block]
+
+  void init(const CudaStreamsFFI &ss, const Params &p, uint32_t L, uint32_t cts, bool is_left) {
+    HX_PANIC_IF_FALSE(L >= 1 && cts >= 1, "scalar_rotate: no blocks");
+    HX_PANIC_IF_FALSE((p.msg & (p.msg - 1)) == 0, "scalar_rotate: the message modulus must be a power of two");
+    blocks = L, max_cts = cts, left = is_left;
+    bits = (uint32_t)__builtin_ctz(p.msg);
+    const uint32_t b = bits;
+    std::vector<std::vector<uint64_t>> luts(std::max(1u, b - 1), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
+    for (uint32_t r = 1; r < b; ++r) generate_lut(p, luts[r - 1].data(), shift_in_block(p.msg, b, r, is_left));
+    drv.init(ss, p, cts * L, luts);
+    radix_alloc((void **)&d_pack, (size_t)cts * L * (p.big_n + 1) * sizeof(uint64_t));
+    if (b == 1) return;
+    const size_t T = (size_t)cts * L;
+    std::vector<uint64_t> li((size_t)(b - 1) * T), oi((size_t)L * T);
+    for (size_t i = 0; i < li.size(); ++i) li[i] = i / T;
+    for (uint32_t q = 0; q < L; ++q)
+      for (uint32_t c = 0; c < cts; ++c)
+        for (uint32_t i = 0; i < L; ++i)  // the packed pair of block i lands q blocks further in the rotation's direction
+          oi[(size_t)q * T + (size_t)c * L + i] = (uint64_t)c * L + (is_left ? (i + q) % L : (i + L - q) % L);
+    i_lut = dev_upload(S0(ss), li), i_out = dev_upload(S0(ss), oi);
+  }
+  void release(const CudaStreamsFFI &ss) {
+    HX_CHECK(hipStreamSynchronize(S0(ss)));
+    drv.release(ss);
+    for (uint64_t *d : {d_pack, i_lut, i_out})
+      if (d) scratch_free(d);
+  }
+};
 
 // ------------------------------------------------------------------ column sums read in place
 // The device side of a SumPlan (radix_sum.h) whose first terms are not in a pool: term ids below n_caller are rows of the
@@ -2843,6 +3154,229 @@ void cuda_logical_scalar_shift_64_inplace_async(CudaStreamsFFI streams, CudaRadi
 
 void cleanup_cuda_logical_scalar_shift_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
   scratch_destroy<ScalarShiftMem>(streams, mem_ptr_void, "cleanup logical_scalar_shift");
+}
+
+// ---- integer.h:212-244, :367-381: arithmetic shift and rotation by a clear amount, shift / rotation by an encrypted one
+// (hip_ names with the reference's parameter lists: the reference-named symbols stay link stubs).  A batch of integers
+// per call, capacity from hip_integer_scratch_batch.
+uint64_t hip_scratch_integer_arithmetic_scalar_shift_64_inplace_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks, uint32_t message_modulus, uint32_t carry_modulus,
+    enum SHIFT_OR_ROTATE_TYPE shift_type, bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  HX_PANIC_IF_FALSE(shift_type == RIGHT_SHIFT, "arithmetic_scalar_shift: shift type %u is not a right shift (a left shift "
+                    "is the logical one)", (uint32_t)shift_type);
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<ArithShiftMem>(streams, mem_ptr, allocate_gpu_memory, "arithmetic_scalar_shift",
+                                       [&](ArithShiftMem &m) { m.init(streams, p, num_blocks, g_scratch_batch); });
+}
+
+// the checks the three launches share; returns the number of integers
+static uint32_t shift_family_batch(uint32_t blocks, uint32_t max_cts, const Params &p, const CudaRadixCiphertextFFI *ct,
+                                   void *const *bsks, void *const *ksks, const char *who) {
+  HX_PANIC_IF_FALSE(ct && ct->ptr && bsks && ksks, "%s: null pointer", who);
+  HX_PANIC_IF_FALSE(ct->lwe_dimension == p.big_n, "%s: the blocks' lwe dimension should be %u", who, p.big_n);
+  const uint32_t cts = batch_of(ct, blocks, who);
+  HX_PANIC_IF_FALSE(cts >= 1 && cts <= max_cts, "%s: %u integers exceed the scratch capacity %u", who, cts, max_cts);
+  return cts;
+}
+// degrees and noise levels follow the blocks of a levelled move: block to[i] takes what block from[i] had
+static void move_block_info(CudaRadixCiphertextFFI *ct, const std::vector<uint32_t> &from, const std::vector<uint32_t> &to) {
+  for (uint64_t *arr : {ct->degrees, ct->noise_levels}) {
+    if (!arr) continue;
+    std::vector<uint64_t> old(arr, arr + ct->num_radix_blocks);
+    for (size_t i = 0; i < from.size(); ++i) arr[to[i]] = old[from[i]];
+  }
+}
+
+void hip_integer_arithmetic_scalar_shift_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array,
+                                                          uint32_t shift, int8_t *mem_ptr, void *const *bsks,
+                                                          void *const *ksks) {
+  first_gpu(streams);
+  auto *m = scratch_use<ArithShiftMem>(mem_ptr, "arithmetic_scalar_shift");
+  const Params &p = m->drv.p;
+  const uint32_t cts = shift_family_batch(m->blocks, m->max_cts, p, lwe_array, bsks, ksks, "arithmetic_scalar_shift");
+  const uint32_t L = m->blocks, b = m->bits, w = p.big_n + 1;
+  check_clean({lwe_array}, cts * L, p.msg, "arithmetic_scalar_shift", "the shift takes clean blocks");
+  if (shift == 0) return;
+  const hipStream_t st = S0(streams);
+  uint64_t *v = (uint64_t *)lwe_array->ptr;
+  const uint32_t q = (uint32_t)std::min<uint64_t>(shift / b, L), n = L - q, r = n ? shift % b : 0;  // n blocks survive
+  const size_t bw = (size_t)w * sizeof(uint64_t);
+  m->plan(st, shift, cts, n, r);
+  std::vector<uint32_t> from, to;
+  for (uint32_t c = 0; c < cts; ++c) {
+    const uint64_t *vc = v + (size_t)c * L * w;
+    uint64_t *pk = m->d_pack + (size_t)c * (L + 1) * w;
+    if (b == 1) {
+      HX_CHECK(hipMemcpyAsync(pk, vc, L * bw, hipMemcpyDeviceToDevice, st));
+      for (uint32_t t = 0; t < L; ++t) from.push_back(c * L + std::min(t + q, L - 1)), to.push_back(c * L + t);
+      continue;
+    }
+    if (r) {
+      if (n > 1) axpy(st, pk, nullptr, vc + (size_t)q * w, nullptr, p.msg, vc + (size_t)(q + 1) * w, nullptr, w, n - 1);
+      HX_CHECK(hipMemcpyAsync(pk + (size_t)(n - 1) * w, vc + (size_t)(L - 1) * w, bw, hipMemcpyDeviceToDevice, st));
+    } else if (n) {
+      HX_CHECK(hipMemcpyAsync(pk, vc + (size_t)q * w, n * bw, hipMemcpyDeviceToDevice, st));
+      for (uint32_t t = 0; t < n; ++t) from.push_back(c * L + t + q), to.push_back(c * L + t);
+    }
+    if (q) HX_CHECK(hipMemcpyAsync(pk + (size_t)L * w, vc + (size_t)(L - 1) * w, bw, hipMemcpyDeviceToDevice, st));
+  }
+  if (b > 1 && !r)  // the surviving blocks move as they are
+    for (uint32_t c = 0; c < cts && n; ++c)
+      HX_CHECK(hipMemcpyAsync(v + (size_t)c * L * w, m->d_pack + (size_t)c * (L + 1) * w, n * bw, hipMemcpyDeviceToDevice, st));
+  if (b > 1) m->drv.round(streams, v, m->i_out, m->d_pack, m->i_in, m->i_lut, m->round_rows, ksks, bsks);
+  axpy(st, v, m->i_to, b > 1 ? v : m->d_pack, m->i_from, 1, nullptr, nullptr, w, m->fill_rows);
+  move_block_info(lwe_array, from, to);
+  if (b > 1)
+    for (uint32_t c = 0; c < cts; ++c) {
+      if (r) set_block_info(lwe_array, c * L, n, p.msg - 1, 1);
+      set_block_info(lwe_array, c * L + n, q, p.msg - 1, 1);
+    }
+}
+
+void hip_cleanup_integer_arithmetic_scalar_shift_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<ArithShiftMem>(streams, mem_ptr_void, "cleanup arithmetic_scalar_shift");
+}
+
+uint64_t hip_scratch_integer_scalar_rotate_64_inplace_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks, uint32_t message_modulus, uint32_t carry_modulus,
+    enum SHIFT_OR_ROTATE_TYPE shift_type, bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  HX_PANIC_IF_FALSE(shift_type == LEFT_ROTATE || shift_type == RIGHT_ROTATE,
+                    "scalar_rotate: shift type %u is not a rotation", (uint32_t)shift_type);
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<ScalarRotateMem>(streams, mem_ptr, allocate_gpu_memory, "scalar_rotate", [&](ScalarRotateMem &m) {
+    m.init(streams, p, num_blocks, g_scratch_batch, shift_type == LEFT_ROTATE);
+  });
+}
+
+void hip_integer_scalar_rotate_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array, uint32_t n,
+                                                int8_t *mem_ptr, void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  auto *m = scratch_use<ScalarRotateMem>(mem_ptr, "scalar_rotate");
+  const Params &p = m->drv.p;
+  const uint32_t cts = shift_family_batch(m->blocks, m->max_cts, p, lwe_array, bsks, ksks, "scalar_rotate");
+  const uint32_t L = m->blocks, b = m->bits, w = p.big_n + 1;
+  check_clean({lwe_array}, cts * L, p.msg, "scalar_rotate", "the rotation takes clean blocks");
+  const uint32_t amount = n % (b * L), q = amount / b, r = amount % b;
+  if (amount == 0) return;
+  const hipStream_t st = S0(streams);
+  uint64_t *v = (uint64_t *)lwe_array->ptr;
+  RotatePack a{};
+  a.out = m->d_pack, a.x = v, a.words = w, a.rows = L, a.mode = kPickWrap;
+  a.dir = m->left ? kTowardsHigher : kTowardsLower;
+  if (r == 0) {  // whole blocks: block i + q (left) takes block i
+    a.s0 = 0, a.s1 = 1, a.r = q;
+    launch_rotate_pack(st, a, cts);
+    HX_CHECK(hipMemcpyAsync(v, m->d_pack, (size_t)cts * L * w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    std::vector<uint32_t> from, to;
+    for (uint32_t c = 0; c < cts; ++c)
+      for (uint32_t i = 0; i < L; ++i) from.push_back(c * L + i), to.push_back(c * L + (m->left ? (i + q) % L : (i + L - q) % L));
+    move_block_info(lwe_array, from, to);
+    return;
+  }
+  // msg block + its lower (left) / upper (right) neighbour, wrapping; a one-block integer is its own neighbour
+  a.s0 = p.msg, a.s1 = 1, a.r = 1 % L;
+  launch_rotate_pack(st, a, cts);
+  m->drv.round(streams, v, m->i_out + (size_t)q * m->max_cts * L, m->d_pack, nullptr, m->i_lut + (size_t)(r - 1) * m->max_cts * L,
+               cts * L, ksks, bsks);
+  set_block_info(lwe_array, 0, cts * L, p.msg - 1, 1);
+}
+
+void hip_cleanup_integer_scalar_rotate_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<ScalarRotateMem>(streams, mem_ptr_void, "cleanup scalar_rotate");
+}
+
+uint64_t hip_scratch_integer_shift_and_rotate_64_inplace_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks, uint32_t message_modulus, uint32_t carry_modulus,
+    enum SHIFT_OR_ROTATE_TYPE shift_type, bool is_signed, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<ShiftRotateMem>(streams, mem_ptr, allocate_gpu_memory, "shift_and_rotate", [&](ShiftRotateMem &m) {
+    m.init(streams, p, num_blocks, g_scratch_batch, (uint32_t)shift_type, is_signed);
+  });
+}
+
+void hip_integer_shift_and_rotate_64_inplace_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *lwe_array,
+                                                   CudaRadixCiphertextFFI const *lwe_shift, int8_t *mem_ptr,
+                                                   void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  auto *m = scratch_use<ShiftRotateMem>(mem_ptr, "shift_and_rotate");
+  const Params &p = m->drv.p;
+  HX_PANIC_IF_FALSE(lwe_shift && lwe_shift->ptr, "shift_and_rotate: null pointer");
+  const uint32_t cts = shift_family_batch(m->blocks, m->max_cts, p, lwe_array, bsks, ksks, "shift_and_rotate");
+  HX_PANIC_IF_FALSE(lwe_array->num_radix_blocks == lwe_shift->num_radix_blocks,
+                    "shift_and_rotate: the amount holds %u blocks, the value %u: they must be the same",
+                    lwe_shift->num_radix_blocks, lwe_array->num_radix_blocks);
+  HX_PANIC_IF_FALSE(lwe_array->lwe_dimension == lwe_shift->lwe_dimension,
+                    "shift_and_rotate: the amount and the value must have the same lwe dimension");
+  check_clean({lwe_array, lwe_shift}, cts * m->blocks, p.msg, "shift_and_rotate",
+              "the value and the amount must be clean (propagate them first)");
+  m->run(streams, (uint64_t *)lwe_array->ptr, (const uint64_t *)lwe_shift->ptr, cts, ksks, bsks);
+  set_block_info(lwe_array, 0, cts * m->blocks, p.msg - 1, 1);
+}
+
+void hip_cleanup_integer_shift_and_rotate_64_inplace(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<ShiftRotateMem>(streams, mem_ptr_void, "cleanup shift_and_rotate");
+}
+
+// bootstraps per integer of one call on this scratch
+uint64_t hip_integer_shift_and_rotate_pbs_count(int8_t *mem_ptr) {
+  return scratch_cast<ShiftRotateMem>(mem_ptr, "hip_integer_shift_and_rotate_pbs_count")->pbs_count();
+}
+
+// lwe_rotate_pack_kernel alone on caller-supplied rows (tests, tools/bench_shift_rotate.py): batch integers of `rows` rows of
+// `words` words in x and out; pad / ctrl may be null (mode != 2 / no control row)
+void hip_test_rotate_pack_async(void *stream, uint32_t gpu_index, void *out, void const *x, void const *pad,
+                                void const *ctrl, uint64_t s0, uint64_t s1, uint32_t words, uint32_t rows, uint32_t batch,
+                                uint32_t r, uint32_t dir, uint32_t mode, uint32_t pad_stride, uint32_t pad_row,
+                                uint32_t ctrl_stride, uint32_t ctrl_row) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(batch >= 1 && rows >= 1, "hip_test_rotate_pack: empty launch");
+  RotatePack a{(uint64_t *)out, (const uint64_t *)x, (const uint64_t *)pad, (const uint64_t *)ctrl, s0, s1, words, rows, r,
+               dir, mode, pad_stride, pad_row, ctrl_stride, ctrl_row};
+  launch_rotate_pack((hipStream_t)stream, a, batch);
+}
+
+// the same result for s0 = 1 composed from the primitives the layer had before the kernel, as the reference composes a barrel
+// stage (tools/bench_shift_rotate.py times one against the other): a device copy of the rows, per integer the rotation as
+// block copies and a memset or single-row copies for the rows pulled in, one axpy that packs, one axpy that adds the
+// control row to all.  tmp: 2 batch rows rows of scratch; ctrl_idx: batch rows entries c ctrl_stride + ctrl_row.
+void hip_test_rotate_pack_baseline_async(void *stream, uint32_t gpu_index, void *out, void const *x, void const *pad,
+                                         void const *ctrl, void const *ctrl_idx, void *tmp, uint64_t s1, uint32_t words,
+                                         uint32_t rows, uint32_t batch, uint32_t r, uint32_t dir, uint32_t mode,
+                                         uint32_t pad_stride, uint32_t pad_row) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(batch >= 1 && rows >= 1 && r < rows && dir <= kTowardsLower && mode <= kPickRow,
+                    "hip_test_rotate_pack_baseline: empty launch or unknown form");
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t bw = (size_t)words * sizeof(uint64_t), R = rows;
+  uint64_t *copy = (uint64_t *)tmp, *rot = copy + (size_t)batch * R * words;
+  HX_CHECK(hipMemcpyAsync(copy, x, batch * R * bw, hipMemcpyDeviceToDevice, st));
+  for (uint32_t c = 0; c < batch; ++c) {
+    const uint64_t *src = copy + (size_t)c * R * words;
+    uint64_t *dst = rot + (size_t)c * R * words;
+    // rows that stay inside the integer, then the r rows that wrap or are pulled in
+    const uint32_t in = rows - r, first_in = dir == kTowardsHigher ? r : 0, first_out = dir == kTowardsHigher ? 0 : in;
+    HX_CHECK(hipMemcpyAsync(dst + (size_t)first_in * words, src + (size_t)(dir == kTowardsHigher ? 0 : r) * words, in * bw,
+                            hipMemcpyDeviceToDevice, st));
+    if (r == 0) continue;
+    if (mode == kPickWrap)
+      HX_CHECK(hipMemcpyAsync(dst + (size_t)first_out * words, src + (size_t)(dir == kTowardsHigher ? in : 0) * words, r * bw,
+                              hipMemcpyDeviceToDevice, st));
+    else if (mode == kPickZero)
+      HX_CHECK(hipMemsetAsync(dst + (size_t)first_out * words, 0, r * bw, st));
+    else
+      for (uint32_t t = 0; t < r; ++t)
+        HX_CHECK(hipMemcpyAsync(dst + (size_t)(first_out + t) * words,
+                                (const uint64_t *)pad + ((size_t)c * pad_stride + pad_row) * words, bw,
+                                hipMemcpyDeviceToDevice, st));
+  }
+  axpy(st, (uint64_t *)out, nullptr, rot, nullptr, s1, (const uint64_t *)x, nullptr, words, batch * rows);
+  if (ctrl)
+    axpy(st, (uint64_t *)out, nullptr, (const uint64_t *)out, nullptr, 1, (const uint64_t *)ctrl, (const uint64_t *)ctrl_idx,
+         words, batch * rows);
 }
 
 // number of PBS one carry propagation / one multiplication of `num_blocks` blocks issues (for benches)

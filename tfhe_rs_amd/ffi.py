@@ -263,6 +263,21 @@ SIGNATURES = {
     "hip_integer_scalar_mul_pbs_count": (_u64, [_v, _v, _u32]),
     "hip_small_scalar_multiplication_integer_64_inplace_async": (None, [_S, _R, _u64, _u32, _u32]),
     "hip_test_group_sum_async": (None, [_v, _u32, _u32, _v, _v, _v, _v, _u32, _u32]),
+    # arithmetic shift / rotation by a clear amount; shift / rotation by an encrypted amount
+    "hip_scratch_integer_arithmetic_scalar_shift_64_inplace_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_arithmetic_scalar_shift_64_inplace_async": (None, [_S, _R, _u32, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_arithmetic_scalar_shift_64_inplace": (None, [_S, _i8pp]),
+    "hip_scratch_integer_scalar_rotate_64_inplace_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_scalar_rotate_64_inplace_async": (None, [_S, _R, _u32, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_scalar_rotate_64_inplace": (None, [_S, _i8pp]),
+    "hip_scratch_integer_shift_and_rotate_64_inplace_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _b, _b, _u32]),
+    "hip_integer_shift_and_rotate_64_inplace_async": (None, [_S, _R, _R, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_shift_and_rotate_64_inplace": (None, [_S, _i8pp]),
+    "hip_integer_shift_and_rotate_pbs_count": (_u64, [_v]),
+    "hip_test_rotate_pack_async": (None, [_v, _u32, _v, _v, _v, _v, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32,
+                                          _u32, _u32]),
+    "hip_test_rotate_pack_baseline_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _v, _u64, _u32, _u32, _u32, _u32, _u32, _u32,
+                                                   _u32, _u32]),
     # 128-bit PBS and noise squashing
     "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
     "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),

@@ -332,9 +332,52 @@ class CudaServerKey:
         _lib().cleanup_cuda_cmux_64(s, C.byref(mem))
         return out
 
-    def scalar_shift_assign(self, ct, shift, streams, left=True):
-        """ct <<= shift / ct >>= shift (logical, clear amount; radix/scalar_shift.rs unchecked_scalar_{left,right}_shift_assign),
-        ONE integer."""
+    def _shift_family(self, name, ct, scratch_args, launch_args, streams, count=False):
+        """scratch -> launch -> cleanup of one of the hip_ shift / rotate entry points, sized for ct's batch"""
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        mem = C.c_void_p()
+        lib = _lib()
+        lib.hip_integer_scratch_batch(ct.num_integers)
+        getattr(lib, f"hip_scratch_integer_{name}_64_inplace_async")(
+            s, C.byref(mem), self._bsk_params(), self._ksk_params(), ct.num_blocks, self.message_modulus,
+            self.carry_modulus, *scratch_args, True, self._noise_reduction())
+        lib.hip_integer_scratch_batch(1)
+        pbs = int(lib.hip_integer_shift_and_rotate_pbs_count(mem)) if count else None
+        getattr(lib, f"hip_integer_{name}_64_inplace_async")(s, C.byref(ct._ffi()), *launch_args, mem, bsks, ksks)
+        getattr(lib, f"hip_cleanup_integer_{name}_64_inplace")(s, C.byref(mem))
+        return pbs
+
+    def scalar_rotate_assign(self, ct, n, streams, left=True):
+        """ct = ct rotated left / right by the clear amount n (mod the bit width), every integer of the batch
+        (radix/scalar_rotate.rs unchecked_scalar_rotate_{left,right}_assign)."""
+        self._shift_family("scalar_rotate", ct, (2 if left else 3,), (int(n),), streams)
+
+    def shift_assign(self, ct, amount, streams, left=True, arithmetic=False, return_pbs_count=False):
+        """ct <<= amount / ct >>= amount with an ENCRYPTED amount of the same shape, every integer of the batch by its own
+        amount (radix/shift.rs unchecked_{left,right}_shift_assign).  arithmetic: ct is two's complement, the right shift
+        fills with its sign.  An amount of the bit width or more gives 0 (all ones for a negative arithmetic operand)."""
+        if arithmetic and left:
+            raise ValueError("an arithmetic shift is a right shift")
+        assert amount.num_integers == ct.num_integers and amount.num_blocks == ct.num_blocks
+        return self._shift_family("shift_and_rotate", ct, (0 if left else 1, bool(arithmetic)), (C.byref(amount._ffi()),),
+                                  streams, count=return_pbs_count)
+
+    def rotate_assign(self, ct, amount, streams, left=True, return_pbs_count=False):
+        """ct = ct rotated by an ENCRYPTED amount of the same shape (radix/rotate.rs unchecked_rotate_{left,right}_assign):
+        by (amount mod 2^m) mod bits, m = ceil(log2 bits) — amount mod bits when the bit width is a power of two."""
+        assert amount.num_integers == ct.num_integers and amount.num_blocks == ct.num_blocks
+        return self._shift_family("shift_and_rotate", ct, (2 if left else 3, False), (C.byref(amount._ffi()),), streams,
+                                  count=return_pbs_count)
+
+    def scalar_shift_assign(self, ct, shift, streams, left=True, arithmetic=False):
+        """ct <<= shift / ct >>= shift (clear amount; radix/scalar_shift.rs unchecked_scalar_{left,right}_shift_assign).
+        Logical: ONE integer.  arithmetic=True: the right shift of a two's complement value, every integer of the batch."""
+        if arithmetic:
+            if left:
+                raise ValueError("an arithmetic shift is a right shift")
+            self._shift_family("arithmetic_scalar_shift", ct, (1,), (int(shift),), streams)
+            return
         assert ct.num_integers == 1
         s, keep = self._streams(streams)
         ksks, bsks = self._key_ptrs(streams)
