@@ -148,25 +148,45 @@ static void generate_many_lut(const Params &p, uint64_t *acc, const std::vector<
 // (gpu/ffi.rs:95-132 "size on gpu" queries): allocations are counted, not made, and nothing is uploaded
 static thread_local bool t_dry = false;
 static thread_local uint64_t t_bytes = 0;
-static void radix_alloc(void **p, size_t bytes) {
-  t_bytes += bytes;
-  *p = nullptr;
-  if (!t_dry) *p = scratch_alloc(bytes);
-}
-
-template <class T>
-static T *dev_upload(hipStream_t st, const std::vector<T> &h) {
-  T *d = nullptr;
-  if (h.empty()) return d;
-  if (t_dry) {
-    t_bytes += h.size() * sizeof(T);  // (counted by a size query only: a real creation returns less, see scratch_create)
+// The owner of a set of device blocks.  Every struct of the layer holds one for the memory it keeps while it lives (`own`)
+// and, where it rebuilds index arrays for the shape of a call, a second one that it empties at the rebuild (`shape`); the
+// named pointers of the structs are views into these.  release() of a struct releases its members, then its owners.
+struct DeviceBlocks {
+  std::vector<void *> held;
+  void *take(size_t bytes) {
+    held.push_back(scratch_alloc(bytes));
+    return held.back();
+  }
+  template <class T>
+  void alloc(T *&p, size_t bytes) {
+    t_bytes += bytes;
+    p = t_dry ? nullptr : (T *)take(bytes);
+  }
+  template <class T>
+  T *upload(hipStream_t st, const std::vector<T> &h) {
+    const size_t bytes = h.size() * sizeof(T);
+    if (t_dry) t_bytes += bytes;  // (counted by a size query only: a real creation returns less, see scratch_create)
+    if (t_dry || h.empty()) return nullptr;
+    T *d = (T *)take(bytes);
+    HX_CHECK(hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, st));
+    HX_CHECK(hipStreamSynchronize(st));  // h may be a temporary
     return d;
   }
-  d = (T *)scratch_alloc(h.size() * sizeof(T));
-  HX_CHECK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  HX_CHECK(hipStreamSynchronize(st));  // h may be a temporary
-  return d;
-}
+  // one block back, for a buffer that grows by being replaced (the caller has waited for its readers)
+  void give_back(void *p) {
+    const auto it = std::find(held.begin(), held.end(), p);
+    HX_PANIC_IF_FALSE(it != held.end(), "radix layer: a device block is given back to an owner that does not hold it");
+    held.erase(it);
+    scratch_free(p);
+  }
+  // everything back; nothing happens on an owner that holds nothing (a size query, a member never set up, a second call)
+  void release(hipStream_t st) {
+    if (held.empty()) return;
+    HX_CHECK(hipStreamSynchronize(st));  // launches may still read the blocks
+    for (void *p : held) scratch_free(p);
+    held.clear();
+  }
+};
 
 // The KS -> PBS round driver (integer.cuh:869-990): `count` blocks gathered from `in` through in_idx are
 // keyswitched, bootstrapped with LUT lut_idx[s] and scattered to out[out_idx[s]].
@@ -247,6 +267,7 @@ struct LutDriver {
     bool direct = true;          // this GPU and the first one reach each other's memory (peer access enabled)
     uint64_t *h_stage = nullptr; // pinned host buffer for the copies when they do not
     hipEvent_t staged = nullptr, done = nullptr, copied = nullptr;
+    DeviceBlocks own, own0;  // the blocks on this GPU; the twins on the first GPU
   };
   std::vector<PerGpu> gpus;
 
@@ -278,21 +299,21 @@ struct LutDriver {
       g.gpu = s.gpu_indexes ? s.gpu_indexes[i] : 0;
       const hipStream_t st = (hipStream_t)s.streams[i];
       HX_CHECK(hipSetDevice((int)g.gpu));
-      if (!no_ks) radix_alloc((void **)&g.d_ks, (size_t)cap * (p.small_n + 1) * sizeof(uint64_t));
-      radix_alloc((void **)&g.d_luts, std::max<size_t>(1, num_luts) * lw * sizeof(uint64_t));
+      if (!no_ks) g.own.alloc(g.d_ks, (size_t)cap * (p.small_n + 1) * sizeof(uint64_t));
+      g.own.alloc(g.d_luts, std::max<size_t>(1, num_luts) * lw * sizeof(uint64_t));
       for (uint32_t t = 0; t < num_luts && !t_dry; ++t)
         HX_CHECK(hipMemcpyAsync(g.d_luts + t * lw, luts[t].data(), lw * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-      g.d_trivial = dev_upload(st, triv);
-      if (i == 0 && many_max > 1) radix_alloc((void **)&g.d_many, (size_t)many_max * cap * w * sizeof(uint64_t));
+      g.d_trivial = g.own.upload(st, triv);
+      if (i == 0 && many_max > 1) g.own.alloc(g.d_many, (size_t)many_max * cap * w * sizeof(uint64_t));
       if (i > 0) {
-        radix_alloc((void **)&g.d_in, (size_t)cap * wi * sizeof(uint64_t));
-        radix_alloc((void **)&g.d_out, (size_t)many_max * cap * w * sizeof(uint64_t));
-        radix_alloc((void **)&g.d_lut_idx, (size_t)cap * sizeof(uint64_t));
+        g.own.alloc(g.d_in, (size_t)cap * wi * sizeof(uint64_t));
+        g.own.alloc(g.d_out, (size_t)many_max * cap * w * sizeof(uint64_t));
+        g.own.alloc(g.d_lut_idx, (size_t)cap * sizeof(uint64_t));
         // An event is recorded on a stream of ITS device only (hipEventRecord rejects a foreign stream): `staged` and
         // `copied` are recorded on the first GPU's stream, `done` on this GPU's; waiting across devices is allowed.
         HX_CHECK(hipSetDevice((int)gpus[0].gpu));
-        radix_alloc((void **)&g.d0_in, (size_t)cap * wi * sizeof(uint64_t));
-        radix_alloc((void **)&g.d0_out, (size_t)many_max * cap * w * sizeof(uint64_t));
+        g.own0.alloc(g.d0_in, (size_t)cap * wi * sizeof(uint64_t));
+        g.own0.alloc(g.d0_out, (size_t)many_max * cap * w * sizeof(uint64_t));
         if (!t_dry) {
           HX_CHECK(hipEventCreateWithFlags(&g.staged, hipEventDisableTiming));
           HX_CHECK(hipEventCreateWithFlags(&g.copied, hipEventDisableTiming));
@@ -470,14 +491,12 @@ struct LutDriver {
         else
           cleanup_cuda_programmable_bootstrap_64(st, g.gpu, &g.pbs_buf);
       }
-      for (uint64_t *d : {g.d_ks, g.d_luts, g.d_trivial, g.d_in, g.d_out, g.d_lut_idx, g.d_many})
-        if (d) scratch_free(d);
+      g.own.release(st);
       for (hipEvent_t e : {g.staged, g.done, g.copied})
         if (e) HX_CHECK(hipEventDestroy(e));
       if (g.h_stage) HX_CHECK(hipHostFree(g.h_stage));
       HX_CHECK(hipSetDevice((int)gpus[0].gpu));
-      for (uint64_t *d : {g.d0_in, g.d0_out})
-        if (d) scratch_free(d);
+      g.own0.release((hipStream_t)s.streams[0]);
     }
     gpus.clear();
   }
@@ -495,10 +514,10 @@ static void first_gpu(const CudaStreamsFFI &s) { HX_CHECK(hipSetDevice((int)G0(s
 // ------------------------------------------------------------------ scratch protocol (scratch.h) on a stream set
 // A struct M of the layer fills itself in a callable given to scratch_create and frees what it declares in
 // release(const CudaStreamsFFI &).
-// create: the only place that sets the thread's dry-run state; `fill` allocates through radix_alloc / dev_upload.  (The core
+// create: the only place that sets the thread's dry-run state; `fill` allocates through the owners (DeviceBlocks).  (The core
 // scratch functions a fill calls neither read nor reset that state.)
 // Known and kept, a fix changes returned values: a size query counts the index uploads, a real creation does not
-// (dev_upload), so the two modes return different numbers; the reference returns one size_tracker in both.
+// (DeviceBlocks::upload), so the two modes return different numbers; the reference returns one size_tracker in both.
 template <class M, class Fill>
 static uint64_t scratch_create(const CudaStreamsFFI &s, int8_t **mem_ptr, bool allocate_gpu_memory, const char *who,
                                Fill &&fill) {
@@ -525,9 +544,10 @@ struct ApplyLutMem : ScratchHeader {
   uint64_t *d_lut_idx = nullptr;  // all zero
   uint64_t degree = 0;
   uint32_t num_many_lut = 1;      // apply_many_univariate_lut: functions packed in the accumulator
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     drv.release(s);
-    if (d_lut_idx) scratch_free(d_lut_idx);
+    own.release(S0(s));
   }
 };
 
@@ -588,7 +608,7 @@ struct PropagateMem : ScratchHeader {
   // (shifted states; carries into the elements); P2: dense sums of one round
   uint64_t *d_pool = nullptr, *d_p = nullptr;
   uint32_t cached_cts = 0;
-  std::vector<uint64_t *> dev_arrays;
+  DeviceBlocks own, shape;  // shape: the index arrays for cached_cts integers
   struct Idx {
     uint64_t *a = nullptr, *b = nullptr, *o = nullptr, *lut = nullptr;
     uint32_t count = 0;
@@ -624,24 +644,17 @@ struct PropagateMem : ScratchHeader {
 
   Idx make(hipStream_t st, const std::vector<uint64_t> &a, const std::vector<uint64_t> &b,
            const std::vector<uint64_t> &o, const std::vector<uint64_t> &l) {
-    auto up_ = [&](const std::vector<uint64_t> &h) {
-      uint64_t *d = dev_upload(st, h);
-      if (d) dev_arrays.push_back(d);
-      return d;
-    };
     Idx r;
-    r.a = up_(a);
-    r.b = up_(b);
-    r.o = up_(o);
-    r.lut = up_(l);
+    r.a = shape.upload(st, a);
+    r.b = shape.upload(st, b);
+    r.o = shape.upload(st, o);
+    r.lut = shape.upload(st, l);
     r.count = (uint32_t)l.size();
     return r;
   }
 
   void build_indexes(hipStream_t st, uint32_t cts) {
-    if (!dev_arrays.empty()) HX_CHECK(hipStreamSynchronize(st));  // launches of the previous shape may still read them
-    for (auto *d : dev_arrays) scratch_free(d);
-    dev_arrays.clear();
+    shape.release(st);  // (waits: launches of the previous shape may still read them)
     up.clear();
     down.clear();
     const uint32_t L = blocks;
@@ -851,9 +864,9 @@ struct PropagateMem : ScratchHeader {
     const uint32_t T = cts * num_blocks;
     drv.init(ss, p, std::min<uint32_t>(T, 1u << 16), luts, 2);
     const size_t w = p.big_n + 1;
-    radix_alloc((void **)&d_pool, (size_t)cts * pool_slots(num_blocks) * w * sizeof(uint64_t));
-    radix_alloc((void **)&d_p, (size_t)T * w * sizeof(uint64_t));
-    radix_alloc((void **)&d_pack, (size_t)cts * w * sizeof(uint64_t));
+    own.alloc(d_pool, (size_t)cts * pool_slots(num_blocks) * w * sizeof(uint64_t));
+    own.alloc(d_p, (size_t)T * w * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)cts * w * sizeof(uint64_t));
     if (!t_dry) build_indexes(S0(ss), cts);  // a call with fewer integers rebuilds them
   }
 
@@ -915,11 +928,8 @@ struct PropagateMem : ScratchHeader {
 
   void release(const CudaStreamsFFI &ss) {
     drv.release(ss);
-    for (auto *d : dev_arrays) scratch_free(d);
-    dev_arrays.clear();
-    cached_cts = 0;  // no index arrays are left
-    for (uint64_t *d : {d_pool, d_p, d_pack})
-      if (d) scratch_free(d);
+    shape.release(S0(ss));
+    own.release(S0(ss));
   }
 };
 
@@ -995,12 +1005,12 @@ struct MulMem : ScratchHeader {
     const size_t per_ct = (size_t)slots * w * sizeof(uint64_t);
     sub = (uint32_t)std::max<size_t>(1, std::min<size_t>(cts, ((size_t)12 << 30) / per_ct));
     drv.init(ss, p, 1u << 16, luts);
-    radix_alloc((void **)&d_pool, (size_t)sub * per_ct);
+    own.alloc(d_pool, (size_t)sub * per_ct);
     const size_t n_prod = prod_slot.size();
     size_t max_groups = 0;
     for (auto &s : steps) max_groups = std::max(max_groups, s.msg_slot.size());
-    radix_alloc((void **)&d_pack, (size_t)sub * n_prod * w * sizeof(uint64_t));
-    radix_alloc((void **)&d_sum, std::max<size_t>(1, (size_t)sub * max_groups) * w * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)sub * n_prod * w * sizeof(uint64_t));
+    own.alloc(d_sum, std::max<size_t>(1, (size_t)sub * max_groups) * w * sizeof(uint64_t));
     prop.init(ss, p, num_blocks, sub);
     if (!t_dry) {
       build_pass(S0(ss), std::min(sub, cts));
@@ -1012,7 +1022,6 @@ struct MulMem : ScratchHeader {
   // brings another count): block products, every column-sum step, the final additions
   struct PassIdx {
     uint32_t nb = 0;
-    std::vector<uint64_t *> owned;
     uint64_t *pa = nullptr, *pb = nullptr, *po = nullptr, *pl = nullptr;
     struct StepIdx {
       uint64_t *off = nullptr, *mem = nullptr, *in = nullptr, *out = nullptr, *lut = nullptr;
@@ -1021,23 +1030,14 @@ struct MulMem : ScratchHeader {
     std::vector<StepIdx> steps;
     uint64_t *foff = nullptr, *fmem = nullptr;
   } pass;
-
-  void free_pass() {
-    for (auto *d : pass.owned) scratch_free(d);
-    pass = PassIdx();
-  }
+  DeviceBlocks own, shape;  // shape: the arrays of `pass`
 
   void build_pass(hipStream_t st, uint32_t nb) {
-    if (!pass.owned.empty()) HX_CHECK(hipStreamSynchronize(st));  // launches of the previous shape may still read them
-    free_pass();
+    shape.release(st);  // (waits: launches of the previous shape may still read them)
+    pass = PassIdx();
     pass.nb = nb;
     const uint32_t L = blocks;
     const size_t n_prod = prod_slot.size();
-    auto up = [&](const std::vector<uint64_t> &h) {
-      uint64_t *d = dev_upload(st, h);
-      if (d) pass.owned.push_back(d);
-      return d;
-    };
     {  // block products
       std::vector<uint64_t> a(nb * n_prod), b(nb * n_prod), o(nb * n_prod), l(nb * n_prod);
       for (uint32_t c = 0; c < nb; ++c)
@@ -1047,7 +1047,8 @@ struct MulMem : ScratchHeader {
           o[c * n_prod + q] = (uint64_t)c * slots + prod_slot[q];
           l[c * n_prod + q] = prod_lut[q];
         }
-      pass.pa = up(a), pass.pb = up(b), pass.po = up(o), pass.pl = up(l);
+      pass.pa = shape.upload(st, a), pass.pb = shape.upload(st, b);
+      pass.po = shape.upload(st, o), pass.pl = shape.upload(st, l);
     }
     for (const Step &s : steps) {  // column sums
       PassIdx::StepIdx si;
@@ -1070,7 +1071,8 @@ struct MulMem : ScratchHeader {
           for (size_t m = 0; m < s.members.size(); ++m) mem[c * s.members.size() + m] = (uint64_t)c * slots + s.members[m];
         }
         off[nb * G] = nb * s.members.size();
-        si.off = up(off), si.mem = up(mem), si.in = up(in), si.out = up(out), si.lut = up(lut);
+        si.off = shape.upload(st, off), si.mem = shape.upload(st, mem);
+        si.in = shape.upload(st, in), si.out = shape.upload(st, out), si.lut = shape.upload(st, lut);
         si.groups = (uint32_t)(nb * G);
         si.count = (uint32_t)in.size();
       }
@@ -1083,7 +1085,7 @@ struct MulMem : ScratchHeader {
           for (uint64_t x : final_cols[col]) mem.push_back((uint64_t)c * slots + x);
           off.push_back(mem.size());
         }
-      pass.foff = up(off), pass.fmem = up(mem);
+      pass.foff = shape.upload(st, off), pass.fmem = shape.upload(st, mem);
     }
   }
 
@@ -1124,12 +1126,10 @@ struct MulMem : ScratchHeader {
   }
 
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
-    free_pass();
     drv.release(ss);
     prop.release(ss);
-    for (uint64_t *d : {d_pool, d_pack, d_sum})
-      if (d) scratch_free(d);
+    shape.release(S0(ss));
+    own.release(S0(ss));
   }
 };
 
@@ -1141,6 +1141,7 @@ struct BoolMulMem : ScratchHeader {
   LutDriver drv;
   uint32_t blocks = 0, max_cts = 0;
   uint64_t *d_pack = nullptr, *d_cond_idx = nullptr, *d_lut_idx = nullptr;
+  DeviceBlocks own;
 
   void init(const CudaStreamsFFI &ss, const Params &p, uint32_t num_blocks, uint32_t cts) {
     blocks = num_blocks;
@@ -1150,12 +1151,12 @@ struct BoolMulMem : ScratchHeader {
     generate_lut(p, luts[0].data(), [m](uint64_t x) -> uint64_t { return (x % m) == 0 ? 0 : x / m; });
     const uint32_t T = cts * num_blocks;
     drv.init(ss, p, std::min<uint32_t>(T, 1u << 16), luts);
-    radix_alloc((void **)&d_pack, (size_t)T * (p.big_n + 1) * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)T * (p.big_n + 1) * sizeof(uint64_t));
     if (!t_dry) {  // (so a size query leaves these two uploads out, unlike every other scratch)
       std::vector<uint64_t> ci(T), li(T, 0);
       for (uint32_t i = 0; i < T; ++i) ci[i] = i / num_blocks;  // the boolean of integer c is block c of its operand
-      d_cond_idx = dev_upload(S0(ss), ci);
-      d_lut_idx = dev_upload(S0(ss), li);
+      d_cond_idx = own.upload(S0(ss), ci);
+      d_lut_idx = own.upload(S0(ss), li);
     }
   }
   // out <- condition ? value : 0; `cond` holds one block per integer
@@ -1169,10 +1170,8 @@ struct BoolMulMem : ScratchHeader {
     drv.round(ss, out, nullptr, d_pack, nullptr, d_lut_idx, T, ksks, bsks);
   }
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
     drv.release(ss);
-    for (uint64_t *d : {d_pack, d_cond_idx, d_lut_idx})
-      if (d) scratch_free(d);
+    own.release(S0(ss));
   }
 };
 
@@ -1184,10 +1183,10 @@ struct BitopMem : ScratchHeader {
   LutDriver drv;
   uint32_t op = 0;
   uint64_t *d_pack = nullptr, *d_lut_idx = nullptr;  // packed operands; all-zero LUT indexes (ciphertext forms)
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     drv.release(s);
-    for (uint64_t *d : {d_pack, d_lut_idx})
-      if (d) scratch_free(d);
+    own.release(S0(s));
   }
 };
 static uint64_t bitop_apply(uint32_t op, uint64_t a, uint64_t b) {
@@ -1211,9 +1210,10 @@ struct SubMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x53554231;  // "SUB1"
   PropagateMem prop;
   uint64_t *d_neg = nullptr;
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     prop.release(s);
-    if (d_neg) scratch_free(d_neg);
+    own.release(S0(s));
   }
 };
 
@@ -1223,10 +1223,10 @@ struct FullPropMem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x46505031;  // "FPP1"
   LutDriver drv;  // LUTs: 0 message, 1 carry
   uint64_t *d_two = nullptr, *d_lut_idx = nullptr;  // the block twice -> (message, carry); indexes {0, 1}
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     drv.release(s);
-    for (uint64_t *d : {d_two, d_lut_idx})
-      if (d) scratch_free(d);
+    own.release(S0(s));
   }
 };
 
@@ -1248,7 +1248,7 @@ struct CompareMem {  // only ever a member of CompareScratch: no header
     uint64_t *off = nullptr, *mem = nullptr, *lut = nullptr;
   };
   std::vector<Level> levels;
-  std::vector<uint64_t *> dev_arrays;
+  DeviceBlocks own;
   uint32_t last_slot = 0;
 
   bool ordering() const { return op >= GT && op <= LE; }
@@ -1260,9 +1260,9 @@ struct CompareMem {  // only ever a member of CompareScratch: no header
     const size_t w = (size_t)p.big_n + 1, lw = (size_t)(p.k + 1) * p.N;
     if (ordering()) {
       prop.init(ss, p, L, 1);
-      radix_alloc((void **)&d_tmp, L * w * sizeof(uint64_t));
-      radix_alloc((void **)&d_neg, L * w * sizeof(uint64_t));
-      radix_alloc((void **)&d_bool, w * sizeof(uint64_t));
+      own.alloc(d_tmp, L * w * sizeof(uint64_t));
+      own.alloc(d_neg, L * w * sizeof(uint64_t));
+      own.alloc(d_bool, w * sizeof(uint64_t));
       return;
     }
     // comparison.cuh are_all_comparisons_block_true: chunks of (msg * carry - 1) / (msg - 1) block results — 5 at 2_2, which is also
@@ -1278,7 +1278,7 @@ struct CompareMem {  // only ever a member of CompareScratch: no header
       generate_lut(p, luts[2 + G + c - 1].data(), [c](uint64_t x) -> uint64_t { return x != c; });
     }
     eq.init(ss, p, L, luts);
-    radix_alloc((void **)&d_pack, L * w * sizeof(uint64_t));
+    own.alloc(d_pack, L * w * sizeof(uint64_t));
     // pool: the block results, then every level's results
     uint32_t slots = L, n = L;
     std::vector<uint32_t> sizes;
@@ -1287,11 +1287,10 @@ struct CompareMem {  // only ever a member of CompareScratch: no header
       sizes.push_back(n);
       slots += n;
     }
-    radix_alloc((void **)&d_pool, (size_t)slots * w * sizeof(uint64_t));
-    radix_alloc((void **)&d_sum, (size_t)std::max<uint32_t>(1, sizes.empty() ? 1 : sizes[0]) * w * sizeof(uint64_t));
+    own.alloc(d_pool, (size_t)slots * w * sizeof(uint64_t));
+    own.alloc(d_sum, (size_t)std::max<uint32_t>(1, sizes.empty() ? 1 : sizes[0]) * w * sizeof(uint64_t));
     const bool ne = op == NE;
-    d_lut0 = dev_upload(S0(ss), std::vector<uint64_t>(L, (L == 1 && ne) ? 1 : 0));
-    dev_arrays.push_back(d_lut0);
+    d_lut0 = own.upload(S0(ss), std::vector<uint64_t>(L, (L == 1 && ne) ? 1 : 0));
     uint32_t in_off = 0, in_n = L, out_off = L;
     for (size_t l = 0; l < sizes.size(); ++l) {
       Level lv;
@@ -1306,10 +1305,9 @@ struct CompareMem {  // only ever a member of CompareScratch: no header
         const uint32_t c = (uint32_t)(off[g + 1] - off[g]);
         lut[g] = (last && ne) ? 2 + G + c - 1 : 2 + c - 1;
       }
-      lv.off = dev_upload(S0(ss), off);
-      lv.mem = dev_upload(S0(ss), mem);
-      lv.lut = dev_upload(S0(ss), lut);
-      for (uint64_t *d : {lv.off, lv.mem, lv.lut}) dev_arrays.push_back(d);
+      lv.off = own.upload(S0(ss), off);
+      lv.mem = own.upload(S0(ss), mem);
+      lv.lut = own.upload(S0(ss), lut);
       levels.push_back(lv);
       in_off = out_off;
       in_n = lv.groups;
@@ -1350,13 +1348,9 @@ struct CompareMem {  // only ever a member of CompareScratch: no header
   }
 
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
-    if (ordering()) prop.release(ss); else eq.release(ss);
-    for (uint64_t *d : dev_arrays)
-      if (d) scratch_free(d);
-    dev_arrays.clear();
-    for (uint64_t *d : {d_tmp, d_neg, d_bool, d_pack, d_pool, d_sum})
-      if (d) scratch_free(d);
+    prop.release(ss);  // (orderings; the other of the two was never set up and holds nothing)
+    eq.release(ss);
+    own.release(S0(ss));
   }
 };
 
@@ -1368,6 +1362,7 @@ struct CmuxMem : ScratchHeader {
   LutDriver drv;  // LUTs: 0 keep if the condition is 1, 1 keep if it is 0, 2 message
   uint32_t blocks = 0;
   uint64_t *d_pack = nullptr, *d_zero_idx = nullptr, *d_lut_idx = nullptr, *d_lut2 = nullptr;
+  DeviceBlocks own;
 
   void init(const CudaStreamsFFI &ss, const Params &p, uint32_t L) {
     blocks = L;
@@ -1377,12 +1372,12 @@ struct CmuxMem : ScratchHeader {
     generate_lut(p, luts[1].data(), [m](uint64_t x) -> uint64_t { return x < m ? x : 0; });
     generate_lut(p, luts[2].data(), [m](uint64_t x) -> uint64_t { return x % m; });
     drv.init(ss, p, 2 * L, luts);
-    radix_alloc((void **)&d_pack, (size_t)2 * L * (p.big_n + 1) * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)2 * L * (p.big_n + 1) * sizeof(uint64_t));
     std::vector<uint64_t> li(2 * L, 0);
     for (uint32_t i = L; i < 2 * L; ++i) li[i] = 1;
-    d_zero_idx = dev_upload(S0(ss), std::vector<uint64_t>(L, 0));
-    d_lut_idx = dev_upload(S0(ss), li);
-    d_lut2 = dev_upload(S0(ss), std::vector<uint64_t>(L, 2));
+    d_zero_idx = own.upload(S0(ss), std::vector<uint64_t>(L, 0));
+    d_lut_idx = own.upload(S0(ss), li);
+    d_lut2 = own.upload(S0(ss), std::vector<uint64_t>(L, 2));
   }
   void run(const CudaStreamsFFI &ss, uint64_t *out, const uint64_t *cond, const uint64_t *t, const uint64_t *f,
            void *const *ksks, void *const *bsks) {
@@ -1396,10 +1391,8 @@ struct CmuxMem : ScratchHeader {
     drv.round(ss, out, nullptr, out, nullptr, d_lut2, L, ksks, bsks);
   }
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
     drv.release(ss);
-    for (uint64_t *d : {d_pack, d_zero_idx, d_lut_idx, d_lut2})
-      if (d) scratch_free(d);
+    own.release(S0(ss));
   }
 };
 
@@ -1419,10 +1412,10 @@ struct ScalarShiftMem : ScratchHeader {
   LutDriver drv;  // LUT r - 1: the shift by r bits inside a block (r = 1 .. bits per block - 1), this scratch's direction
   uint32_t blocks = 0, bits = 0, left = 0;
   uint64_t *d_pack = nullptr, *d_lut_idx = nullptr;  // packed pairs / block copy; one constant index array per r
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     drv.release(s);
-    for (uint64_t *d : {d_pack, d_lut_idx})
-      if (d) scratch_free(d);
+    own.release(S0(s));
   }
 };
 
@@ -1459,15 +1452,6 @@ static void check_clean(std::initializer_list<const CudaRadixCiphertextFFI *> op
 }
 
 // ------------------------------------------------------------------ shifts and rotations
-// uploads an index array of a call (kept alive by the scratch) in place of the one it held
-static void replace_upload(hipStream_t st, uint64_t *&d, const std::vector<uint64_t> &h) {
-  if (d) {
-    HX_CHECK(hipStreamSynchronize(st));  // an earlier call may still read it
-    scratch_free(d);
-  }
-  d = dev_upload(st, h);
-}
-
 // shift_and_rotate.cuh / integer.h:230-244: shift or rotation by an ENCRYPTED amount, a barrel shifter over the bits.
 // b = log2(msg) bits per block, L blocks, B = b L bits, m = ceil(log2 B) control bits.  Rounds of one call, every
 // integer of the batch in the same rounds:
@@ -1501,6 +1485,7 @@ struct ShiftRotateMem : ScratchHeader {
   // index arrays, [integer][row] so that a call with fewer integers reads a prefix
   uint64_t *i_bits_in = nullptr, *i_bits_lut = nullptr, *i_ctrl_in = nullptr, *i_ctrl_lut = nullptr, *i_const = nullptr,
            *i_sign = nullptr, *i_top = nullptr, *i_bit = nullptr, *i_cond = nullptr, *i_hi = nullptr, *i_lo = nullptr;
+  DeviceBlocks own;
 
   bool shift() const { return type == LEFT_SHIFT || type == RIGHT_SHIFT; }
   uint64_t compare_pbs() const {
@@ -1545,10 +1530,10 @@ struct ShiftRotateMem : ScratchHeader {
     });
     const uint32_t rows = cts * std::max(B, L);
     drv.init(ss, p, std::min<uint32_t>(rows, 1u << 16), luts);
-    radix_alloc((void **)&d_bits, (size_t)cts * B * w * sizeof(uint64_t));
-    radix_alloc((void **)&d_cur, (size_t)cts * B * w * sizeof(uint64_t));
-    radix_alloc((void **)&d_pack, (size_t)cts * B * w * sizeof(uint64_t));
-    radix_alloc((void **)&d_ctrl, (size_t)cts * std::max(1u, m) * w * sizeof(uint64_t));
+    own.alloc(d_bits, (size_t)cts * B * w * sizeof(uint64_t));
+    own.alloc(d_cur, (size_t)cts * B * w * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)cts * B * w * sizeof(uint64_t));
+    own.alloc(d_ctrl, (size_t)cts * std::max(1u, m) * w * sizeof(uint64_t));
     const hipStream_t st = S0(ss);
     std::vector<uint64_t> bi((size_t)cts * B), bl((size_t)cts * B), ci((size_t)cts * m), cl((size_t)cts * m),
         top((size_t)cts * L), bit((size_t)std::max(1u, b - 1) * cts * L), cond((size_t)cts * L), sign(cts);
@@ -1562,13 +1547,13 @@ struct ShiftRotateMem : ScratchHeader {
       for (uint32_t d = 0; d < m; ++d) ci[(size_t)c * m + d] = (uint64_t)c * L + d / b, cl[(size_t)c * m + d] = b + d % b;
       sign[c] = (uint64_t)c * B + B - 1;
     }
-    i_bits_in = dev_upload(st, bi), i_bits_lut = dev_upload(st, bl);
-    i_ctrl_in = dev_upload(st, ci), i_ctrl_lut = dev_upload(st, cl);
-    i_top = dev_upload(st, top), i_bit = dev_upload(st, bit), i_cond = dev_upload(st, cond), i_sign = dev_upload(st, sign);
+    i_bits_in = own.upload(st, bi), i_bits_lut = own.upload(st, bl);
+    i_ctrl_in = own.upload(st, ci), i_ctrl_lut = own.upload(st, cl);
+    i_top = own.upload(st, top), i_bit = own.upload(st, bit), i_cond = own.upload(st, cond), i_sign = own.upload(st, sign);
     // constant LUT indexes: [2 b] * rows (mux), then + 1, + 2, + 3 on cts L rows each
     std::vector<uint64_t> k((size_t)cts * B + 3 * (size_t)cts * L);
     for (size_t i = 0; i < k.size(); ++i) k[i] = i < (size_t)cts * B ? 2 * b : 2 * b + 1 + (i - (size_t)cts * B) / ((size_t)cts * L);
-    i_const = dev_upload(st, k);
+    i_const = own.upload(st, k);
     if (!overshift) return;
     // "amount >= B" on the clear digits of B
     pairs = p.msg == 2;
@@ -1577,17 +1562,17 @@ struct ShiftRotateMem : ScratchHeader {
     Params pc = p;
     if (pairs) pc.msg = 4, pc.carry = p.msg * p.carry / 4;  // the same plaintext space, read as digits of two bits
     cmp.init(ss, pc, cmp_blocks, GE);
-    radix_alloc((void **)&d_cond, (size_t)cts * w * sizeof(uint64_t));
-    if (pairs || cmp_blocks != L) radix_alloc((void **)&d_padded, (size_t)cmp_blocks * w * sizeof(uint64_t));
+    own.alloc(d_cond, (size_t)cts * w * sizeof(uint64_t));
+    if (pairs || cmp_blocks != L) own.alloc(d_padded, (size_t)cmp_blocks * w * sizeof(uint64_t));
     std::vector<uint64_t> triv((size_t)cmp_blocks * w, 0);
     uint64_t v = B;
     for (uint32_t i = 0; i < cmp_blocks; ++i, v /= pc.msg) triv[(size_t)i * w + w - 1] = (v % pc.msg) * p.delta();
     HX_PANIC_IF_FALSE(v == 0, "shift_and_rotate: the bit count %u does not fit %u digits", B, cmp_blocks);
-    d_triv = dev_upload(st, triv);
+    d_triv = own.upload(st, triv);
     if (pairs) {
       std::vector<uint64_t> hi(L / 2), lo(L / 2);
       for (uint32_t i = 0; i < L / 2; ++i) hi[i] = 2 * i + 1, lo[i] = 2 * i;
-      i_hi = dev_upload(st, hi), i_lo = dev_upload(st, lo);
+      i_hi = own.upload(st, hi), i_lo = own.upload(st, lo);
     }
   }
 
@@ -1654,12 +1639,9 @@ struct ShiftRotateMem : ScratchHeader {
   }
 
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
     drv.release(ss);
-    if (overshift) cmp.release(ss);
-    for (uint64_t *d : {d_bits, d_cur, d_pack, d_ctrl, d_cond, d_padded, d_triv, i_bits_in, i_bits_lut, i_ctrl_in,
-                        i_ctrl_lut, i_const, i_sign, i_top, i_bit, i_cond, i_hi, i_lo})
-      if (d) scratch_free(d);
+    cmp.release(ss);
+    own.release(S0(ss));
   }
 };
 
@@ -1675,6 +1657,7 @@ struct ArithShiftMem : ScratchHeader {
   uint64_t *d_pack = nullptr;  // [integer][L + 1]: the rows of the round, row L the padding row's input
   uint64_t *i_in = nullptr, *i_out = nullptr, *i_lut = nullptr, *i_from = nullptr, *i_to = nullptr;  // of the cached call
   uint32_t key_shift = ~0u, key_cts = 0, round_rows = 0, fill_rows = 0;
+  DeviceBlocks own, shape;  // shape: the index arrays of the cached call
 
   void init(const CudaStreamsFFI &ss, const Params &p, uint32_t L, uint32_t cts) {
     HX_PANIC_IF_FALSE(L >= 1 && cts >= 1, "arithmetic_scalar_shift: no blocks");
@@ -1692,7 +1675,7 @@ struct ArithShiftMem : ScratchHeader {
     }
     generate_lut(p, luts[2 * (b - 1)].data(), [msg, b](uint64_t x) -> uint64_t { return (msg - 1) * ((x % msg) >> (b - 1)); });
     drv.init(ss, p, cts * (L + 1), luts);
-    radix_alloc((void **)&d_pack, (size_t)cts * (L + 1) * (p.big_n + 1) * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)cts * (L + 1) * (p.big_n + 1) * sizeof(uint64_t));
   }
 
   // the rows of the call's round and of the fill that follows it; n blocks survive, r bits remain
@@ -1713,17 +1696,17 @@ struct ArithShiftMem : ScratchHeader {
           from.push_back((uint64_t)c * (L + 1) + std::min(t + (L - n), L - 1)), to.push_back((uint64_t)c * L + t);
       }
     }
-    replace_upload(st, i_in, in), replace_upload(st, i_out, out), replace_upload(st, i_lut, lut);
-    replace_upload(st, i_from, from), replace_upload(st, i_to, to);
+    shape.release(st);  // (waits: an earlier call may still read them)
+    i_in = shape.upload(st, in), i_out = shape.upload(st, out), i_lut = shape.upload(st, lut);
+    i_from = shape.upload(st, from), i_to = shape.upload(st, to);
     round_rows = (uint32_t)in.size(), fill_rows = (uint32_t)from.size();
     key_shift = shift, key_cts = cts;
   }
 
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
     drv.release(ss);
-    for (uint64_t *d : {d_pack, i_in, i_out, i_lut, i_from, i_to})
-      if (d) scratch_free(d);
+    shape.release(S0(ss));
+    own.release(S0(ss));
   }
 };
 
@@ -1736,6 +1719,7 @@ struct ScalarRotateMem : ScratchHeader {
   LutDriver drv;  // LUT r - 1: the shift by r bits inside a block, this scratch's direction
   uint32_t blocks = 0, bits = 0, left = 0, max_cts = 0;
   uint64_t *d_pack = nullptr, *i_lut = nullptr, *i_out = nullptr;  // i_lut: [r - 1][integer][block]; i_out: [q][integer][block]
+  DeviceBlocks own;
 
   void init(const CudaStreamsFFI &ss, const Params &p, uint32_t L, uint32_t cts, bool is_left) {
     HX_PANIC_IF_FALSE(L >= 1 && cts >= 1, "scalar_rotate: no blocks");
@@ -1746,7 +1730,7 @@ struct ScalarRotateMem : ScratchHeader {
     std::vector<std::vector<uint64_t>> luts(std::max(1u, b - 1), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
     for (uint32_t r = 1; r < b; ++r) generate_lut(p, luts[r - 1].data(), shift_in_block(p.msg, b, r, is_left));
     drv.init(ss, p, cts * L, luts);
-    radix_alloc((void **)&d_pack, (size_t)cts * L * (p.big_n + 1) * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)cts * L * (p.big_n + 1) * sizeof(uint64_t));
     if (b == 1) return;
     const size_t T = (size_t)cts * L;
     std::vector<uint64_t> li((size_t)(b - 1) * T), oi((size_t)L * T);
@@ -1755,13 +1739,11 @@ struct ScalarRotateMem : ScratchHeader {
       for (uint32_t c = 0; c < cts; ++c)
         for (uint32_t i = 0; i < L; ++i)  // the packed pair of block i lands q blocks further in the rotation's direction
           oi[(size_t)q * T + (size_t)c * L + i] = (uint64_t)c * L + (is_left ? (i + q) % L : (i + L - q) % L);
-    i_lut = dev_upload(S0(ss), li), i_out = dev_upload(S0(ss), oi);
+    i_lut = own.upload(S0(ss), li), i_out = own.upload(S0(ss), oi);
   }
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
     drv.release(ss);
-    for (uint64_t *d : {d_pack, i_lut, i_out})
-      if (d) scratch_free(d);
+    own.release(S0(ss));
   }
 };
 
@@ -1781,9 +1763,9 @@ struct ColumnSum {
   };
   std::vector<StepIdx> steps;
   uint64_t *foff = nullptr, *fmem = nullptr;
-  std::vector<uint64_t *> owned;
   uint64_t *d_pool = nullptr, *d_sum = nullptr;
   size_t pool_rows = 0, sum_rows = 0;
+  DeviceBlocks own, shape;  // shape: the index arrays of the plan for nb integers
 
   // takes the plan of columns `cols` over the degrees `deg` (deg.size() first terms, the first n_caller_ in caller rows)
   void set_plan(SumPlan &&pl, uint32_t L_, uint32_t n_caller_, uint32_t caller_rows_, size_t terms) {
@@ -1805,30 +1787,18 @@ struct ColumnSum {
       if (want <= have) return;
       if (d) {
         HX_CHECK(hipStreamSynchronize(st));  // launches may still use the smaller buffer
-        scratch_free(d);
+        own.give_back(d);
       }
-      radix_alloc((void **)&d, want * w * sizeof(uint64_t));
+      own.alloc(d, want * w * sizeof(uint64_t));
       have = want;
     };
     grow(d_pool, pool_rows, pr);
     grow(d_sum, sum_rows, sr);
   }
-  void free_indexes(hipStream_t st) {
-    if (!owned.empty()) HX_CHECK(hipStreamSynchronize(st));  // launches of the previous plan may still read them
-    for (auto *d : owned) scratch_free(d);
-    owned.clear();
-    steps.clear();
-    foff = fmem = nullptr;
-    nb = 0;
-  }
   // index arrays of the plan for cts integers (build_pass of the multiplication is the model)
   void upload(hipStream_t st, uint32_t cts, uint64_t lut_msg, uint64_t lut_carry) {
-    free_indexes(st);
-    auto up = [&](const std::vector<uint64_t> &h) {
-      uint64_t *d = dev_upload(st, h);
-      if (d) owned.push_back(d);
-      return d;
-    };
+    shape.release(st);  // (waits: launches of the previous plan may still read them)
+    steps.clear();
     for (const SumStep &s : plan.steps) {
       StepIdx si;
       const size_t G = s.msg_slot.size(), M = s.members.size();
@@ -1848,7 +1818,8 @@ struct ColumnSum {
         for (size_t m = 0; m < M; ++m) mem[c * M + m] = row(s.members[m], c);
       }
       off[cts * G] = cts * M;
-      si.off = up(off), si.mem = up(mem), si.in = up(in), si.out = up(out), si.lut = up(lut);
+      si.off = shape.upload(st, off), si.mem = shape.upload(st, mem);
+      si.in = shape.upload(st, in), si.out = shape.upload(st, out), si.lut = shape.upload(st, lut);
       si.groups = (uint32_t)(cts * G);
       si.count = (uint32_t)in.size();
       steps.push_back(si);
@@ -1859,7 +1830,7 @@ struct ColumnSum {
         for (uint64_t x : plan.final_cols[col]) mem.push_back(row(x, c));
         off.push_back(mem.size());
       }
-    foff = up(off), fmem = up(mem);
+    foff = shape.upload(st, off), fmem = shape.upload(st, mem);
     nb = cts;
   }
   void reduce(const CudaStreamsFFI &ss, const LutDriver &drv, const uint64_t *caller, uint32_t w, void *const *ksks,
@@ -1882,10 +1853,8 @@ struct ColumnSum {
     HX_CHECK(hipMemcpyAsync(out, d_sum, (size_t)nb * L * w * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
   }
   void release(hipStream_t st) {
-    free_indexes(st);
-    for (uint64_t *d : {d_pool, d_sum})
-      if (d) scratch_free(d);
-    d_pool = d_sum = nullptr;
+    shape.release(st);
+    own.release(st);
   }
 };
 
@@ -1930,7 +1899,6 @@ struct SumMem : ScratchHeader {
     key = d;
   }
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
     cs.release(S0(ss));
     drv.release(ss);
   }
@@ -1955,7 +1923,7 @@ struct ScalarMulMem : ScratchHeader {
   std::vector<uint64_t> pre_j, pre_r;  // the shifted blocks some set bit uses, per integer
   // device arrays of the preshift round for cs.nb integers
   uint64_t *pk0 = nullptr, *pkj = nullptr, *pkm = nullptr, *pre_in = nullptr, *pre_out = nullptr, *pre_lut = nullptr;
-  std::vector<uint64_t *> owned;
+  DeviceBlocks own, shape;  // shape: the arrays of the preshift round
 
   static std::vector<uint8_t> scalar_key(const uint64_t *decomposed, uint32_t n, uint32_t limit) {
     std::vector<uint8_t> k(std::min(n, limit));
@@ -2005,7 +1973,7 @@ struct ScalarMulMem : ScratchHeader {
     const uint64_t widest = (uint64_t)cts * blocks * std::max(bits, scalar_bits);  // no round holds more blocks
     drv.init(ss, p, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(widest, 1u << 16)), luts);
     const size_t w = (size_t)p.big_n + 1;
-    radix_alloc((void **)&d_pack, (size_t)cts * blocks * w * sizeof(uint64_t));
+    own.alloc(d_pack, (size_t)cts * blocks * w * sizeof(uint64_t));
     prop.init(ss, p, num_blocks, cts);
     // sized for the scalar with every bit set; a wider plan (there is none among the scalars tried) grows it
     make_plan(std::vector<uint8_t>(scalar_bits, 1));
@@ -2015,13 +1983,7 @@ struct ScalarMulMem : ScratchHeader {
 
   void upload(hipStream_t st, uint32_t cts) {
     cs.upload(st, cts, 0, 1);
-    for (auto *d : owned) scratch_free(d);  // (cs.upload waited for the stream)
-    owned.clear();
-    auto up = [&](const std::vector<uint64_t> &h) {
-      uint64_t *d = dev_upload(st, h);
-      if (d) owned.push_back(d);
-      return d;
-    };
+    shape.release(st);
     const uint32_t L = blocks;
     std::vector<uint64_t> r0, rj, rm, in, out, lut;
     for (uint32_t c = 0; c < cts; ++c) {
@@ -2033,7 +1995,8 @@ struct ScalarMulMem : ScratchHeader {
         lut.push_back(1 + pre_r[s]);
       }
     }
-    pk0 = up(r0), pkj = up(rj), pkm = up(rm), pre_in = up(in), pre_out = up(out), pre_lut = up(lut);
+    pk0 = shape.upload(st, r0), pkj = shape.upload(st, rj), pkm = shape.upload(st, rm);
+    pre_in = shape.upload(st, in), pre_out = shape.upload(st, out), pre_lut = shape.upload(st, lut);
   }
 
   // v <- v * scalar for `cts` integers (the plan of the scalar is in place)
@@ -2056,13 +2019,11 @@ struct ScalarMulMem : ScratchHeader {
   }
 
   void release(const CudaStreamsFFI &ss) {
-    HX_CHECK(hipStreamSynchronize(S0(ss)));
     cs.release(S0(ss));
-    for (auto *d : owned) scratch_free(d);
-    owned.clear();
     drv.release(ss);
     prop.release(ss);
-    if (d_pack) scratch_free(d_pack);
+    shape.release(S0(ss));
+    own.release(S0(ss));
   }
 };
 
@@ -2094,18 +2055,16 @@ struct PackingKsMem : ScratchHeader {
   CompressionShape sh;
   uint32_t cap = 0;  // LWEs per call
   uint64_t *d_rows = nullptr, *d_trivial = nullptr;
+  DeviceBlocks own;
   void init(const CudaStreamsFFI &s, const CompressionShape &shape, uint32_t capacity) {
     sh = shape;
     cap = std::max(1u, capacity);
-    radix_alloc((void **)&d_rows, (size_t)cap * sh.ncols() * sizeof(uint64_t));
+    own.alloc(d_rows, (size_t)cap * sh.ncols() * sizeof(uint64_t));
     std::vector<uint64_t> triv(cap);
     for (uint32_t i = 0; i < cap; ++i) triv[i] = i;
-    d_trivial = dev_upload(S0(s), triv);
+    d_trivial = own.upload(S0(s), triv);
   }
-  void release(const CudaStreamsFFI &) {
-    for (uint64_t *d : {d_rows, d_trivial})
-      if (d) scratch_free(d);
-  }
+  void release(const CudaStreamsFFI &s) { own.release(S0(s)); }
 };
 
 struct CompressMem : ScratchHeader {
@@ -2113,9 +2072,10 @@ struct CompressMem : ScratchHeader {
   PackingKsMem pks;  // member: no header of its own in use
   uint32_t msg = 0, carry = 0, lwe_per_glwe = 0, bits = 0;
   uint64_t *d_scaled = nullptr;  // the input blocks times message_modulus
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     pks.release(s);
-    if (d_scaled) scratch_free(d_scaled);
+    own.release(S0(s));
   }
 };
 
@@ -2127,14 +2087,14 @@ struct DecompressMem : ScratchHeader {
   uint32_t *d_indexes = nullptr, *h_indexes = nullptr;  // h_indexes: pinned staging of the caller's host array
   hipEvent_t uploaded = nullptr;                         // behind the last copy out of h_indexes
   int8_t *pbs_buf = nullptr;
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     const hipStream_t st = S0(s);
     if (pbs_buf) {
       if (p.grouping) cleanup_cuda_multi_bit_programmable_bootstrap_64(st, gpu, &pbs_buf);
       else cleanup_cuda_programmable_bootstrap_64(st, gpu, &pbs_buf);
     }
-    for (void *d : {(void *)d_extracted, (void *)d_lut, (void *)d_trivial, (void *)d_lut_idx, (void *)d_indexes})
-      if (d) scratch_free(d);
+    own.release(st);
     if (h_indexes) HX_CHECK(hipHostFree(h_indexes));
     if (uploaded) HX_CHECK(hipEventDestroy(uploaded));
   }
@@ -2163,11 +2123,11 @@ struct NoiseSquashMem : ScratchHeader {
   unsigned __int128 *d_lut = nullptr;
   int8_t *pbs_buf = nullptr;
   uint32_t grouping = 0;  // the kind: 0 a classic 128-bit key, otherwise the grouping factor of a multi-bit one
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     if (pbs_buf && grouping) hip_cleanup_multi_bit_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
     else if (pbs_buf) hip_cleanup_programmable_bootstrap_128(S0(s), gpu, &pbs_buf);
-    for (void *d : {(void *)d_packed, (void *)d_after_ks, (void *)d_trivial, (void *)d_lo, (void *)d_hi, (void *)d_lut})
-      if (d) scratch_free(d);
+    own.release(S0(s));
   }
 };
 
@@ -2180,14 +2140,13 @@ struct ExpandMem : ScratchHeader {
   uint32_t n_c = 0;                // the casting key's input dimension: the compact lists' mask length
   uint32_t cast_out_n = 0, cast_base_log = 0, cast_level = 0;  // SMALL_TO_BIG: the casting keyswitch of its own
   uint32_t num_lwes = 0, gpu = 0;
-  bool has_drv = false;
-  LutDriver drv;
+  LutDriver drv;  // (not set up where nothing is bootstrapped)
   ExpandJob *d_jobs = nullptr;  // per output row: where its list's mask starts, which body it takes (built once, here)
   uint64_t *d_expanded = nullptr, *d_cast = nullptr, *d_in_idx = nullptr, *d_out_idx = nullptr, *d_lut_idx = nullptr;
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
-    if (has_drv) drv.release(s);
-    for (void *d : {(void *)d_jobs, (void *)d_expanded, (void *)d_cast, (void *)d_in_idx, (void *)d_out_idx, (void *)d_lut_idx})
-      if (d) scratch_free(d);
+    drv.release(s);
+    own.release(S0(s));
   }
 };
 
@@ -2202,10 +2161,8 @@ struct RerandMem : ScratchHeader {
   uint32_t count = 0, gpu = 0;
   ExpandJob *d_jobs = nullptr;  // row o: the list's mask (offset 0) times X^o
   uint64_t *d_expanded = nullptr, *d_switched = nullptr, *d_trivial = nullptr;
-  void release(const CudaStreamsFFI &) {
-    for (void *d : {(void *)d_jobs, (void *)d_expanded, (void *)d_switched, (void *)d_trivial})
-      if (d) scratch_free(d);
-  }
+  DeviceBlocks own;
+  void release(const CudaStreamsFFI &s) { own.release(S0(s)); }
 };
 
 // Oblivious pseudo-random bits (cuda/include/integer/oprf.h int_grouped_oprf_memory, cuda/src/integer/oprf.cuh;
@@ -2218,10 +2175,10 @@ struct OprfMem : ScratchHeader {
   std::vector<uint32_t> bits;         // per block: the random bits it takes
   uint64_t *d_lut_idx = nullptr;      // per block: bits - 1
   uint64_t *d_corrections = nullptr;  // per block: (2^bits - 1) * delta / 2, added to the body
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     drv.release(s);
-    for (uint64_t *d : {d_lut_idx, d_corrections})
-      if (d) scratch_free(d);
+    own.release(S0(s));
   }
 };
 
@@ -2248,7 +2205,7 @@ static uint64_t scratch_apply_lut(CudaStreamsFFI streams, int8_t **mem_ptr, void
     m.drv.init(streams, p, std::max<uint32_t>(1, count), luts);
     m.degree = lut_degree;
     m.num_many_lut = num_many_lut;
-    radix_alloc((void **)&m.d_lut_idx, idx_bytes);
+    m.own.alloc(m.d_lut_idx, idx_bytes);
     if (!t_dry) HX_CHECK(hipMemsetAsync(m.d_lut_idx, 0, idx_bytes, S0(streams)));
   });
 }
@@ -2629,8 +2586,8 @@ static uint64_t scratch_bitop(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweB
     }
     m.drv.init(streams, p, cap, luts);
     if (!scalar) {
-      radix_alloc((void **)&m.d_pack, (size_t)cap * (p.big_n + 1) * sizeof(uint64_t));
-      radix_alloc((void **)&m.d_lut_idx, (size_t)cap * sizeof(uint64_t));
+      m.own.alloc(m.d_pack, (size_t)cap * (p.big_n + 1) * sizeof(uint64_t));
+      m.own.alloc(m.d_lut_idx, (size_t)cap * sizeof(uint64_t));
       if (!t_dry) HX_CHECK(hipMemsetAsync(m.d_lut_idx, 0, (size_t)cap * sizeof(uint64_t), S0(streams)));
     }
   });
@@ -2745,7 +2702,7 @@ uint64_t scratch_cuda_sub_and_propagate_single_carry_64_inplace_async(
                       "sub_and_propagate_single_carry: output flag %u is not wired (0 = none, 2 = carry)", requested_flag);
     const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
     m.prop.init(streams, p, num_blocks, g_scratch_batch);
-    radix_alloc((void **)&m.d_neg, (size_t)num_blocks * g_scratch_batch * (p.big_n + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_neg, (size_t)num_blocks * g_scratch_batch * (p.big_n + 1) * sizeof(uint64_t));
   });
 }
 
@@ -2843,8 +2800,8 @@ uint64_t scratch_cuda_full_propagation_64_inplace_async(CudaStreamsFFI streams, 
     generate_lut(p, luts[0].data(), [msg](uint64_t x) { return x % msg; });
     generate_lut(p, luts[1].data(), [msg](uint64_t x) { return x / msg; });
     m.drv.init(streams, p, 2, luts);
-    radix_alloc((void **)&m.d_two, 2 * (size_t)(p.big_n + 1) * sizeof(uint64_t));
-    m.d_lut_idx = dev_upload(S0(streams), std::vector<uint64_t>{0, 1});
+    m.own.alloc(m.d_two, 2 * (size_t)(p.big_n + 1) * sizeof(uint64_t));
+    m.d_lut_idx = m.own.upload(S0(streams), std::vector<uint64_t>{0, 1});
   });
 }
 
@@ -2888,6 +2845,7 @@ struct CompareScratch : ScratchHeader {
   CompareMem cmp;
   CmuxMem mux;  // MAX / MIN only
   uint64_t *d_flag = nullptr;
+  DeviceBlocks own;
 
   bool select() const { return op == MAX || op == MIN; }
   // shared by the ciphertext and the scalar form (one integer per call: hip_integer_scratch_batch is not read)
@@ -2902,7 +2860,7 @@ struct CompareScratch : ScratchHeader {
     cmp.init(streams, p, count, select() ? (uint32_t)GE : op_type);
     if (select()) {
       mux.init(streams, p, count);
-      radix_alloc((void **)&d_flag, (size_t)(p.big_n + 1) * sizeof(uint64_t));
+      own.alloc(d_flag, (size_t)(p.big_n + 1) * sizeof(uint64_t));
     }
   }
   void run(const CudaStreamsFFI &streams, CudaRadixCiphertextFFI *lwe_array_out, CudaRadixCiphertextFFI const *lwe_array_1,
@@ -2938,8 +2896,8 @@ struct CompareScratch : ScratchHeader {
   }
   void release(const CudaStreamsFFI &s) {
     cmp.release(s);
-    if (select()) mux.release(s);
-    if (d_flag) scratch_free(d_flag);
+    mux.release(s);
+    own.release(S0(s));
   }
 };
 }  // namespace
@@ -2976,9 +2934,10 @@ struct ScalarCompareScratch : ScratchHeader {
   static constexpr uint32_t kMagic = 0x53435231;  // "SCR1"
   CompareScratch cmp;
   uint64_t *d_triv = nullptr;
+  DeviceBlocks own;
   void release(const CudaStreamsFFI &s) {
     cmp.release(s);
-    if (d_triv) scratch_free(d_triv);
+    own.release(S0(s));
   }
 };
 }  // namespace
@@ -2993,7 +2952,7 @@ uint64_t scratch_cuda_integer_scalar_comparison_64_async(CudaStreamsFFI streams,
       streams, mem_ptr, allocate_gpu_memory, "integer_scalar_comparison", [&](ScalarCompareScratch &m) {
         m.cmp.init(streams, bsk_params, ksk_params, lwe_ciphertext_count, message_modulus, carry_modulus, (uint32_t)op_type,
                    is_signed, (uint32_t)noise_reduction_type);
-        radix_alloc((void **)&m.d_triv, (size_t)lwe_ciphertext_count * (m.cmp.cmp.params().big_n + 1) * sizeof(uint64_t));
+        m.own.alloc(m.d_triv, (size_t)lwe_ciphertext_count * (m.cmp.cmp.params().big_n + 1) * sizeof(uint64_t));
       });
 }
 
@@ -3091,10 +3050,10 @@ uint64_t scratch_cuda_logical_scalar_shift_64_inplace_async(CudaStreamsFFI strea
     std::vector<std::vector<uint64_t>> luts(std::max(1u, bits - 1), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
     for (uint32_t r = 1; r < bits; ++r) generate_lut(p, luts[r - 1].data(), shift_in_block(msg, bits, r, left));
     m.drv.init(streams, p, num_blocks, luts);
-    radix_alloc((void **)&m.d_pack, (size_t)num_blocks * (p.big_n + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_pack, (size_t)num_blocks * (p.big_n + 1) * sizeof(uint64_t));
     std::vector<uint64_t> li((size_t)std::max(1u, bits - 1) * num_blocks);
     for (size_t i = 0; i < li.size(); ++i) li[i] = i / num_blocks;
-    m.d_lut_idx = dev_upload(S0(streams), li);
+    m.d_lut_idx = m.own.upload(S0(streams), li);
   });
 }
 
@@ -3645,7 +3604,7 @@ uint64_t hip_scratch_integer_compress_radix_ciphertext_64_async(
   return scratch_create<CompressMem>(streams, mem_ptr, allocate_gpu_memory, "integer_compress", [&](CompressMem &m) {
     m.pks.init(streams, sh, num_radix_blocks);
     m.msg = message_modulus, m.carry = carry_modulus, m.lwe_per_glwe = lwe_per_glwe, m.bits = storage_log_modulus;
-    radix_alloc((void **)&m.d_scaled, (size_t)m.pks.cap * (sh.n_in + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_scaled, (size_t)m.pks.cap * (sh.n_in + 1) * sizeof(uint64_t));
   });
 }
 
@@ -3698,14 +3657,14 @@ uint64_t hip_scratch_integer_decompress_radix_ciphertext_64_async(
     m.lwe_per_glwe = lwe_per_glwe, m.bits = storage_log_modulus;
     m.cap = std::max(1u, num_blocks_to_decompress);
     m.gpu = G0(streams);
-    radix_alloc((void **)&m.d_extracted, (size_t)m.cap * (p.small_n + 1) * sizeof(uint64_t));
-    radix_alloc((void **)&m.d_indexes, (size_t)m.cap * sizeof(uint32_t));
-    radix_alloc((void **)&m.d_lut_idx, (size_t)m.cap * sizeof(uint64_t));
+    m.own.alloc(m.d_extracted, (size_t)m.cap * (p.small_n + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_indexes, (size_t)m.cap * sizeof(uint32_t));
+    m.own.alloc(m.d_lut_idx, (size_t)m.cap * sizeof(uint64_t));
     std::vector<uint64_t> lut((size_t)(p.k + 1) * p.N), triv(m.cap);
     generate_rescaling_lut(p, lut.data());
     for (uint32_t i = 0; i < m.cap; ++i) triv[i] = i;
-    m.d_lut = dev_upload(st, lut);
-    m.d_trivial = dev_upload(st, triv);
+    m.d_lut = m.own.upload(st, lut);
+    m.d_trivial = m.own.upload(st, triv);
     if (!t_dry) {
       HX_CHECK(hipMemsetAsync(m.d_lut_idx, 0, (size_t)m.cap * sizeof(uint64_t), st));
       HX_CHECK(hipHostMalloc((void **)&m.h_indexes, (size_t)m.cap * sizeof(uint32_t), 0));
@@ -3819,19 +3778,17 @@ struct PackingKs128Mem : ScratchHeader {
   Pks128Shape sh;
   uint32_t cap = 0;  // LWEs per call
   Pks128Workspace ws;
+  DeviceBlocks own;
   void init(const Pks128Shape &shape, uint32_t capacity) {
     sh = shape;
     cap = std::max(1u, capacity);
-    radix_alloc((void **)&ws.rows, pks128_rows_bytes(cap, sh.n_in, sh.ncols(), sh.base_log, sh.level));
+    own.alloc(ws.rows, pks128_rows_bytes(cap, sh.n_in, sh.ncols(), sh.base_log, sh.level));
     if (const uint64_t bytes = pks128_digits_bytes(cap, sh.n_in, sh.base_log, sh.level)) {
-      radix_alloc(&ws.digits, bytes);
-      radix_alloc((void **)&ws.digit_sums, (size_t)cap * 16);
+      own.alloc(ws.digits, bytes);
+      own.alloc(ws.digit_sums, (size_t)cap * 16);
     }
   }
-  void release(const CudaStreamsFFI &) {
-    for (void *d : {(void *)ws.rows, ws.digits, (void *)ws.digit_sums})
-      if (d) scratch_free(d);
-  }
+  void release(const CudaStreamsFFI &s) { own.release(S0(s)); }
 };
 struct Compress128Mem : ScratchHeader {
   static constexpr uint32_t kMagic = 0x434D3132;  // "CM12"
@@ -3844,8 +3801,9 @@ struct Decompress128Mem : ScratchHeader {
   uint32_t kc = 0, Nc = 0, lwe_per_glwe = 0, bits = 0, cap = 0, msg = 0, carry = 0;
   uint32_t *d_indexes = nullptr, *h_indexes = nullptr;  // h_indexes: pinned staging of the caller's host array
   hipEvent_t uploaded = nullptr;                         // behind the last copy out of h_indexes
-  void release(const CudaStreamsFFI &) {
-    if (d_indexes) scratch_free(d_indexes);
+  DeviceBlocks own;
+  void release(const CudaStreamsFFI &s) {
+    own.release(S0(s));
     if (h_indexes) HX_CHECK(hipHostFree(h_indexes));
     if (uploaded) HX_CHECK(hipEventDestroy(uploaded));
   }
@@ -3967,7 +3925,7 @@ uint64_t hip_scratch_integer_decompress_radix_ciphertext_128_async(
     m.lwe_per_glwe = lwe_per_glwe, m.bits = storage_log_modulus;
     m.msg = message_modulus, m.carry = carry_modulus;
     m.cap = std::max(1u, num_blocks_to_decompress);
-    radix_alloc((void **)&m.d_indexes, (size_t)m.cap * sizeof(uint32_t));
+    m.own.alloc(m.d_indexes, (size_t)m.cap * sizeof(uint32_t));
     if (!t_dry) {
       HX_CHECK(hipHostMalloc((void **)&m.h_indexes, (size_t)m.cap * sizeof(uint32_t), 0));
       HX_CHECK(hipEventCreateWithFlags(&m.uploaded, hipEventDisableTiming));
@@ -4055,13 +4013,13 @@ static uint64_t scratch_noise_squashing(
     m.cap_in = std::max(1u, num_original_blocks), m.cap_out = std::max(1u, num_radix_blocks);
     m.gpu = G0(streams);
     m.grouping = grouping_factor;
-    radix_alloc((void **)&m.d_packed, (size_t)m.cap_out * (m.big_n + 1) * sizeof(uint64_t));
-    radix_alloc((void **)&m.d_after_ks, (size_t)m.cap_out * (m.small_n + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_packed, (size_t)m.cap_out * (m.big_n + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_after_ks, (size_t)m.cap_out * (m.small_n + 1) * sizeof(uint64_t));
     std::vector<uint64_t> triv(m.cap_out), lo(m.cap_out), hi(m.cap_out);
     for (uint32_t i = 0; i < m.cap_out; ++i) triv[i] = i, lo[i] = 2 * i, hi[i] = 2 * i + 1;
-    m.d_trivial = dev_upload(st, triv);
-    m.d_lo = dev_upload(st, lo);
-    m.d_hi = dev_upload(st, hi);
+    m.d_trivial = m.own.upload(st, triv);
+    m.d_lo = m.own.upload(st, lo);
+    m.d_hi = m.own.upload(st, hi);
     // the identity on message_modulus * carry_modulus values, encoded on 128 bits: delta = 2^127 / (msg * carry)
     const uint32_t sup = m.msg * m.carry, box = m.N / sup, half = box / 2;
     const unsigned __int128 delta = ((unsigned __int128)1 << 127) / sup;
@@ -4071,7 +4029,7 @@ static uint64_t scratch_noise_squashing(
       for (uint32_t j = i * box; j < (i + 1) * box; ++j) body[j] = (unsigned __int128)i * delta;
     for (uint32_t i = 0; i < half; ++i) body[i] = (unsigned __int128)0 - body[i];
     std::rotate(body, body + half, body + m.N);
-    m.d_lut = dev_upload(st, lut);
+    m.d_lut = m.own.upload(st, lut);
     if (m.grouping)
       t_bytes += hip_scratch_multi_bit_programmable_bootstrap_128_async(st, m.gpu, &m.pbs_buf, m.k, m.N, m.pbs_level, m.cap_out,
                                                                         !t_dry);
@@ -4209,7 +4167,7 @@ uint64_t hip_scratch_expand_without_verification_64_async(
       for (uint32_t d = 0; d < num_lwes_per_compact_list[l]; ++d) jobs.push_back(ExpandJob{at, d, 0});
       at += (uint64_t)n_c + num_lwes_per_compact_list[l];
     }
-    m.d_jobs = dev_upload(st, jobs);
+    m.d_jobs = m.own.upload(st, jobs);
     if (kind == NO_CASTING) return;
     // zk_utilities.h:190-230,283-300: per list of c bodies first the c message extractions, then the c carry extractions;
     // output 2i is the message block of body i, 2i + 1 its carry block; a boolean output takes the sanitising table
@@ -4226,9 +4184,9 @@ uint64_t hip_scratch_expand_without_verification_64_async(
       }
       offset += c;
     }
-    m.d_in_idx = dev_upload(st, in_idx);
-    m.d_out_idx = dev_upload(st, out_idx);
-    m.d_lut_idx = dev_upload(st, lut_idx);
+    m.d_in_idx = m.own.upload(st, in_idx);
+    m.d_out_idx = m.own.upload(st, out_idx);
+    m.d_lut_idx = m.own.upload(st, lut_idx);
     const uint64_t msg = p.msg, carry = p.carry;
     std::vector<std::function<uint64_t(uint64_t)>> fs;
     if (kind == SANITY_CHECK) {
@@ -4239,13 +4197,12 @@ uint64_t hip_scratch_expand_without_verification_64_async(
     }
     std::vector<std::vector<uint64_t>> luts(fs.size(), std::vector<uint64_t>((size_t)(p.k + 1) * p.N));
     for (size_t t = 0; t < fs.size(); ++t) generate_lut(p, luts[t].data(), fs[t]);
-    radix_alloc((void **)&m.d_expanded, (size_t)num_lwes * ((size_t)n_c + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_expanded, (size_t)num_lwes * ((size_t)n_c + 1) * sizeof(uint64_t));
     if (ks_type == SMALL_TO_BIG) {
       m.cast_out_n = casting_ksk_params.output_lwe_dimension;
       m.cast_base_log = casting_ksk_params.base_log, m.cast_level = casting_ksk_params.level_count;
-      radix_alloc((void **)&m.d_cast, (size_t)num_lwes * ((size_t)m.cast_out_n + 1) * sizeof(uint64_t));
+      m.own.alloc(m.d_cast, (size_t)num_lwes * ((size_t)m.cast_out_n + 1) * sizeof(uint64_t));
     }
-    m.has_drv = true;
     m.drv.init(streams, p, blocks, luts, 1, ks_type == BIG_TO_SMALL ? n_c : 0);
   });
 }
@@ -4317,10 +4274,10 @@ uint64_t hip_scratch_rerand_64_async(CudaStreamsFFI streams, int8_t **mem_ptr, C
     std::vector<ExpandJob> jobs(count);
     std::vector<uint64_t> triv(count);
     for (uint32_t o = 0; o < count; ++o) jobs[o] = ExpandJob{0, o, 0}, triv[o] = o;
-    m.d_jobs = dev_upload(st, jobs);
-    m.d_trivial = dev_upload(st, triv);
-    radix_alloc((void **)&m.d_expanded, (size_t)count * ((size_t)n_in + 1) * sizeof(uint64_t));
-    radix_alloc((void **)&m.d_switched, (size_t)count * ((size_t)m.n_out + 1) * sizeof(uint64_t));
+    m.d_jobs = m.own.upload(st, jobs);
+    m.d_trivial = m.own.upload(st, triv);
+    m.own.alloc(m.d_expanded, (size_t)count * ((size_t)n_in + 1) * sizeof(uint64_t));
+    m.own.alloc(m.d_switched, (size_t)count * ((size_t)m.n_out + 1) * sizeof(uint64_t));
   });
 }
 
@@ -4402,8 +4359,8 @@ uint64_t hip_scratch_integer_grouped_oprf_64_async(CudaStreamsFFI streams, int8_
       corrections[i] = (((uint64_t)1 << m.bits[i]) - 1) * delta / 2;
       processed += m.bits[i];
     }
-    m.d_lut_idx = dev_upload(st, lut_idx);
-    m.d_corrections = dev_upload(st, corrections);
+    m.d_lut_idx = m.own.upload(st, lut_idx);
+    m.d_corrections = m.own.upload(st, corrections);
     m.drv.init(streams, p, m.num_blocks, luts, 1, 0, true);
   });
 }
