@@ -983,6 +983,67 @@ void hip_test_rotate_pack_baseline_async(void *stream, uint32_t gpu_index, void 
                                          uint32_t rows, uint32_t batch, uint32_t r, uint32_t dir, uint32_t mode,
                                          uint32_t pad_stride, uint32_t pad_row);
 
+/* ------------------------------------------------------------------ Trivium transciphering (extensions)
+ * cuda/include/trivium/trivium.h under hip_ names with the reference's parameter lists, on the shared scratch protocol;
+ * the reference-named symbols remain link stubs.  num_inputs = N ciphers run side by side.  Position p of a register
+ * occupies blocks p N .. p N + N - 1 (a: 93 positions, b: 84, c: 111); bit i of input n of the key / the IV is block
+ * i N + n (80 N blocks each); the keystream bit of step t of input n is block t N + n.  Bits are 0 / 1 in the message
+ * space.  init: a[i] = key[79 - i], b[i] = iv[79 - i] (i < 80), c[108 .. 110] = 1 (trivial encryptions), everything else 0,
+ * then 1,152 steps without output; it writes all 288 N register blocks.  step: num_steps steps from the registers, which hold
+ * the same layout before and after.  64 steps run in two bootstrap rounds: 384 N bootstraps without keystream, 512 N with
+ * it; init is 6,912 N bootstraps in 36 rounds.  Registers and keystream leave a call with degree 1 and noise level 1.
+ * Limits: a row reaches the value and noise level max(message_modulus + 1, 5), which must be at most
+ * message_modulus * carry_modulus - 1 and at most (message_modulus * carry_modulus - 1) / (message_modulus - 1) — (2, 4),
+ * (2, 8), (4, 4), (4, 16), (8, 8) pass, (2, 2) is refused; input blocks (key, IV, the registers of step) have degree and
+ * noise level at most 1; num_steps is a multiple of 64; a, b, c hold 93 N, 84 N, 111 N blocks, key and iv 80 N, the
+ * keystream num_steps N; num_inputs equals the scratch's; a scratch serves the call it was created for.
+ * hip_trivium_pbs_count: bootstraps of one call on that scratch (init: the warm-up, num_steps is not read); every call
+ * checks it against the rounds it issued. */
+uint64_t hip_scratch_trivium_init_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+    uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_inputs);
+void hip_trivium_init_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *a_reg,
+    CudaRadixCiphertextFFI *b_reg, CudaRadixCiphertextFFI *c_reg,
+    const CudaRadixCiphertextFFI *key, const CudaRadixCiphertextFFI *iv,
+    uint32_t num_inputs, int8_t *mem_ptr, void *const *bsks, void *const *ksks);
+void hip_cleanup_trivium_init(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+uint64_t hip_scratch_trivium_step_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+    uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_inputs);
+void hip_trivium_step_async(CudaStreamsFFI streams,
+                            CudaRadixCiphertextFFI *keystream_output,
+                            CudaRadixCiphertextFFI *a_reg,
+                            CudaRadixCiphertextFFI *b_reg,
+                            CudaRadixCiphertextFFI *c_reg, uint32_t num_inputs,
+                            uint32_t num_steps, int8_t *mem_ptr,
+                            void *const *bsks, void *const *ksks);
+void hip_cleanup_trivium_step(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+uint64_t hip_trivium_pbs_count(int8_t *mem_ptr, uint32_t num_steps);
+/* tests: batches between two re-basings of the state tapes of that scratch, 2 .. 18 (18 when the scratch is created) */
+void hip_test_trivium_set_window(int8_t *mem_ptr, uint32_t window);
+/* tests, benches: the tap kernel alone.  out_g[q inputs + n] = sum over the terms t of group g of
+ * scalar_t * src_t[(pos_t +- q) inputs + n] on u64 words, rows of `words` words, q < bits[g]; up to 4 groups of up to 5
+ * terms.  HOST arrays: outs / bits / terms one entry per group; srcs / pos / backwards / scalars five per group (term t of
+ * group g at 5 g + t); backwards[i] != 0: bit q reads position pos - q (pos >= bits - 1).  No output may overlap a row read. */
+void hip_test_tap_sum_async(void *stream, uint32_t gpu_index, uint32_t words, uint32_t inputs, uint32_t groups,
+                            void *const *outs, uint32_t const *bits, uint32_t const *terms, void const *const *srcs,
+                            uint32_t const *pos, uint32_t const *backwards, uint64_t const *scalars);
+/* benches: the data movement of one batch of 64 steps with keystream, composed from device copies and pairwise additions in
+ * the reference's order (cuda/src/trivium/trivium.cuh:110-275).  a, b, c: the registers, updated in place; r1 / r2 stand for
+ * the outputs of the two rounds, [and_a | and_b | and_c | t3] and [a | b | c | z] of 64 * inputs rows each; in1 / in2
+ * receive the rows the two tap launches form; keystream receives r2's z rows in step order.
+ * tmp: (111 + 12 * 64) * inputs rows. */
+void hip_test_trivium_batch_baseline_async(void *stream, uint32_t gpu_index, void *a, void *b, void *c, void *in1,
+                                           void const *r1, void *in2, void const *r2, void *keystream, void *tmp,
+                                           uint32_t words, uint32_t inputs, uint64_t message_modulus);
+
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's
  * cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103 and cuda/include/fft/fft128.h), under hip_ names

@@ -2185,6 +2185,8 @@ struct OprfMem : ScratchHeader {
 }  // namespace radix
 }  // namespace tfhe_hip
 
+#include "radix_trivium.h"  // TriviumMem and the tap kernel, on the round driver and the owners above
+
 using namespace tfhe_hip;
 using namespace tfhe_hip::radix;
 
@@ -3336,6 +3338,150 @@ void hip_test_rotate_pack_baseline_async(void *stream, uint32_t gpu_index, void 
   if (ctrl)
     axpy(st, (uint64_t *)out, nullptr, (const uint64_t *)out, nullptr, 1, (const uint64_t *)ctrl, (const uint64_t *)ctrl_idx,
          words, batch * rows);
+}
+
+// ---- Trivium transciphering (radix_trivium.h; hip_ names with the parameter lists of cuda/include/trivium/trivium.h: the
+// reference-named symbols stay link stubs) ------------------------------------------------------------------------------
+namespace {
+uint64_t trivium_scratch(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+                         CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus, uint32_t carry_modulus,
+                         bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_inputs,
+                         bool warmup) {
+  const char *who = warmup ? "trivium_init" : "trivium_step";
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<TriviumMem>(streams, mem_ptr, allocate_gpu_memory, who,
+                                    [&](TriviumMem &m) { m.init(streams, p, num_inputs, warmup, who); });
+}
+// a register, the key, the IV or the keystream: `bits` positions of N rows, every block a clean bit
+uint64_t *trivium_rows(const CudaRadixCiphertextFFI *ct, uint32_t bits, const TriviumMem &m, bool is_input, const char *who,
+                       const char *what) {
+  HX_PANIC_IF_FALSE(ct && ct->ptr, "%s: null pointer (%s)", who, what);
+  HX_PANIC_IF_FALSE(ct->lwe_dimension == m.drv.p.big_n, "%s: the blocks' lwe dimension should be %u", who, m.drv.p.big_n);
+  HX_PANIC_IF_FALSE(ct->num_radix_blocks == bits * m.inputs, "%s: %s holds %u blocks, %u bits of %u inputs are %u", who, what,
+                    ct->num_radix_blocks, bits, m.inputs, bits * m.inputs);
+  for (uint32_t i = 0; is_input && i < ct->num_radix_blocks; ++i) {
+    HX_PANIC_IF_FALSE(!ct->degrees || ct->degrees[i] <= 1, "%s: block %u of %s has degree %llu, a bit has at most 1", who, i,
+                      what, (unsigned long long)ct->degrees[i]);
+    HX_PANIC_IF_FALSE(!ct->noise_levels || ct->noise_levels[i] <= 1, "%s: block %u of %s has noise level %llu, at most 1",
+                      who, i, what, (unsigned long long)ct->noise_levels[i]);
+  }
+  return (uint64_t *)ct->ptr;
+}
+TriviumMem *trivium_use(int8_t *mem_ptr, bool warmup, uint32_t num_inputs, void *const *bsks, void *const *ksks,
+                        const char *who) {
+  auto *m = scratch_use<TriviumMem>(mem_ptr, who);
+  HX_PANIC_IF_FALSE(m->warmup == warmup, "%s: the scratch was created by the other trivium scratch call", who);
+  HX_PANIC_IF_FALSE(bsks && ksks, "%s: null pointer", who);
+  HX_PANIC_IF_FALSE(num_inputs == m->inputs, "%s: %u inputs on a scratch created for %u", who, num_inputs, m->inputs);
+  return m;
+}
+}  // namespace
+
+uint64_t hip_scratch_trivium_init_async(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+                                        CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+                                        uint32_t carry_modulus, bool allocate_gpu_memory,
+                                        enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_inputs) {
+  return trivium_scratch(streams, mem_ptr, bsk_params, ksk_params, message_modulus, carry_modulus, allocate_gpu_memory,
+                         noise_reduction_type, num_inputs, true);
+}
+
+void hip_trivium_init_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *a_reg, CudaRadixCiphertextFFI *b_reg,
+                            CudaRadixCiphertextFFI *c_reg, const CudaRadixCiphertextFFI *key,
+                            const CudaRadixCiphertextFFI *iv, uint32_t num_inputs, int8_t *mem_ptr, void *const *bsks,
+                            void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "trivium_init";
+  TriviumMem *m = trivium_use(mem_ptr, true, num_inputs, bsks, ksks, who);
+  CudaRadixCiphertextFFI *const regs[3] = {a_reg, b_reg, c_reg};
+  const char *const names[3] = {"register a", "register b", "register c"};
+  uint64_t *rows[3];
+  for (uint32_t r = 0; r < 3; ++r) rows[r] = trivium_rows(regs[r], kTriviumBits[r], *m, false, who, names[r]);
+  const uint64_t *k = trivium_rows(key, kTriviumKeyBits, *m, true, who, "the key");
+  const uint64_t *v = trivium_rows(iv, kTriviumKeyBits, *m, true, who, "the iv");
+  m->warm_up(streams, rows, k, v, ksks, bsks);
+  for (uint32_t r = 0; r < 3; ++r) set_block_info(regs[r], 0, regs[r]->num_radix_blocks, 1, 1);
+}
+
+void hip_cleanup_trivium_init(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<TriviumMem>(streams, mem_ptr_void, "cleanup trivium_init");
+}
+
+uint64_t hip_scratch_trivium_step_async(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+                                        CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+                                        uint32_t carry_modulus, bool allocate_gpu_memory,
+                                        enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_inputs) {
+  return trivium_scratch(streams, mem_ptr, bsk_params, ksk_params, message_modulus, carry_modulus, allocate_gpu_memory,
+                         noise_reduction_type, num_inputs, false);
+}
+
+void hip_trivium_step_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *keystream_output, CudaRadixCiphertextFFI *a_reg,
+                            CudaRadixCiphertextFFI *b_reg, CudaRadixCiphertextFFI *c_reg, uint32_t num_inputs,
+                            uint32_t num_steps, int8_t *mem_ptr, void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "trivium_step";
+  TriviumMem *m = trivium_use(mem_ptr, false, num_inputs, bsks, ksks, who);
+  HX_PANIC_IF_FALSE(num_steps % kTriviumBatch == 0, "%s: num_steps %u is not a multiple of %u", who, num_steps, kTriviumBatch);
+  CudaRadixCiphertextFFI *const regs[3] = {a_reg, b_reg, c_reg};
+  const char *const names[3] = {"register a", "register b", "register c"};
+  uint64_t *rows[3];
+  for (uint32_t r = 0; r < 3; ++r) rows[r] = trivium_rows(regs[r], kTriviumBits[r], *m, true, who, names[r]);
+  if (num_steps == 0) return;
+  uint64_t *z = trivium_rows(keystream_output, num_steps, *m, false, who, "the keystream");
+  m->step(streams, rows, z, num_steps, ksks, bsks);
+  for (uint32_t r = 0; r < 3; ++r) set_block_info(regs[r], 0, regs[r]->num_radix_blocks, 1, 1);
+  set_block_info(keystream_output, 0, keystream_output->num_radix_blocks, 1, 1);
+}
+
+void hip_cleanup_trivium_step(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<TriviumMem>(streams, mem_ptr_void, "cleanup trivium_step");
+}
+
+// bootstraps of one call on this scratch: the warm-up for a scratch of trivium_init (num_steps is not read), num_steps
+// steps with keystream for a scratch of trivium_step
+uint64_t hip_trivium_pbs_count(int8_t *mem_ptr, uint32_t num_steps) {
+  return scratch_cast<TriviumMem>(mem_ptr, "hip_trivium_pbs_count")->pbs_count(num_steps);
+}
+
+// tests: batches between two re-basings of the tapes, 2 .. 18
+void hip_test_trivium_set_window(int8_t *mem_ptr, uint32_t window) {
+  auto *m = scratch_cast<TriviumMem>(mem_ptr, "hip_test_trivium_set_window");
+  HX_PANIC_IF_FALSE(window >= 2 && window <= m->window_max, "hip_test_trivium_set_window: %u is outside 2 .. %u", window,
+                    m->window_max);
+  m->window = window;
+}
+
+// lwe_tap_sum_kernel alone on a caller-given table (tests, tools/bench_trivium.py).  Host arrays: outs / bits / terms hold
+// one entry per group, srcs / pos / backwards / scalars 5 per group (term t of group g at 5 g + t); backwards: bit q reads
+// position pos - q instead of pos + q
+void hip_test_tap_sum_async(void *stream, uint32_t gpu_index, uint32_t words, uint32_t inputs, uint32_t groups,
+                            void *const *outs, uint32_t const *bits, uint32_t const *terms, void const *const *srcs,
+                            uint32_t const *pos, uint32_t const *backwards, uint64_t const *scalars) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(groups >= 1 && groups <= kTapGroups && outs && bits && terms && srcs && pos && backwards && scalars,
+                    "hip_test_tap_sum: %u groups or a null array", groups);
+  TapTable t{};
+  t.words = words, t.inputs = inputs, t.groups = groups;
+  for (uint32_t g = 0; g < groups; ++g) {
+    HX_PANIC_IF_FALSE(terms[g] <= kTapTerms, "hip_test_tap_sum: group %u has %u terms", g, terms[g]);
+    t.g[g].out = (uint64_t *)outs[g], t.g[g].bits = bits[g], t.g[g].terms = terms[g];
+    for (uint32_t i = 0; i < terms[g]; ++i)
+      t.g[g].t[i] = TapTerm{(const uint64_t *)srcs[kTapTerms * g + i], scalars[kTapTerms * g + i], pos[kTapTerms * g + i],
+                            backwards[kTapTerms * g + i] ? -1 : 1};
+  }
+  launch_tap_sum((hipStream_t)stream, t);
+}
+
+// one batch's data movement composed from the older primitives in the reference's order (radix_trivium.h,
+// trivium_batch_baseline): a, b, c are updated in place from r2, keystream receives r2's z rows in step order
+void hip_test_trivium_batch_baseline_async(void *stream, uint32_t gpu_index, void *a, void *b, void *c, void *in1,
+                                           void const *r1, void *in2, void const *r2, void *keystream, void *tmp,
+                                           uint32_t words, uint32_t inputs, uint64_t message_modulus) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(a && b && c && in1 && r1 && in2 && r2 && keystream && tmp && words >= 1 && inputs >= 1,
+                    "hip_test_trivium_batch_baseline: null pointer or empty rows");
+  uint64_t *const regs[3] = {(uint64_t *)a, (uint64_t *)b, (uint64_t *)c};
+  trivium_batch_baseline((hipStream_t)stream, regs, (uint64_t *)in1, (const uint64_t *)r1, (uint64_t *)in2,
+                         (const uint64_t *)r2, (uint64_t *)keystream, (uint64_t *)tmp, words, inputs, message_modulus);
 }
 
 // number of PBS one carry propagation / one multiplication of `num_blocks` blocks issues (for benches)

@@ -278,6 +278,17 @@ SIGNATURES = {
                                           _u32, _u32]),
     "hip_test_rotate_pack_baseline_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _v, _u64, _u32, _u32, _u32, _u32, _u32, _u32,
                                                    _u32, _u32]),
+    # Trivium transciphering
+    "hip_scratch_trivium_init_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _b, _u32, _u32]),
+    "hip_trivium_init_async": (None, [_S, _R, _R, _R, _R, _R, _u32, _v, _i8pp, _i8pp]),
+    "hip_cleanup_trivium_init": (None, [_S, _i8pp]),
+    "hip_scratch_trivium_step_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _b, _u32, _u32]),
+    "hip_trivium_step_async": (None, [_S, _R, _R, _R, _R, _u32, _u32, _v, _i8pp, _i8pp]),
+    "hip_cleanup_trivium_step": (None, [_S, _i8pp]),
+    "hip_trivium_pbs_count": (_u64, [_v, _u32]),
+    "hip_test_trivium_set_window": (None, [_v, _u32]),
+    "hip_test_tap_sum_async": (None, [_v, _u32, _u32, _u32, _u32, _v, _v, _v, _v, _v, _v, _v]),
+    "hip_test_trivium_batch_baseline_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _v, _v, _v, _v, _u32, _u32, _u64]),
     # 128-bit PBS and noise squashing
     "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
     "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),

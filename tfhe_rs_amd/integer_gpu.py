@@ -24,6 +24,7 @@ OUTPUT_FLAG_NONE, OUTPUT_FLAG_OVERFLOW, OUTPUT_FLAG_CARRY = 0, 1, 2   # integer/
 KS_TYPE_BIG_TO_SMALL, KS_TYPE_SMALL_TO_BIG = 0, 1                      # keyswitch/ks_enums.h
 EXPAND_KIND = {"no_casting": 0, "casting": 1, "sanity_check": 2}       # zk/zk_enums.h
 RERAND_WITH_KS, RERAND_WITHOUT_KS = 0, 1                               # integer/integer.h:45
+TRIVIUM_KEY_BITS, TRIVIUM_BATCH_SIZE, TRIVIUM_REGISTER_BITS = 80, 64, (93, 84, 111)   # trivium/trivium_utilities.h:5-12
 
 
 class CudaServerKey:
@@ -370,6 +371,57 @@ class CudaServerKey:
         return self._shift_family("shift_and_rotate", ct, (2 if left else 3, False), (C.byref(amount._ffi()),), streams,
                                   count=return_pbs_count)
 
+    # ---- Trivium transciphering (integer/gpu/server_key/radix/trivium.rs)
+    def _trivium_call(self, kind, num_inputs, streams, launch, num_steps=0, window=None):
+        """scratch -> launch -> cleanup of hip_trivium_{init,step}; returns the published bootstrap count of the call"""
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        mem = C.c_void_p()
+        lib = _lib()
+        getattr(lib, f"hip_scratch_trivium_{kind}_async")(
+            s, C.byref(mem), self._bsk_params(), self._ksk_params(), self.message_modulus, self.carry_modulus, True,
+            self._noise_reduction(), num_inputs)
+        if window is not None:
+            lib.hip_test_trivium_set_window(mem, window)
+        pbs = int(lib.hip_trivium_pbs_count(mem, num_steps))
+        launch(lib, s, mem, bsks, ksks)
+        getattr(lib, f"hip_cleanup_trivium_{kind}")(s, C.byref(mem))
+        return pbs
+
+    def trivium_init(self, key, iv, streams, return_pbs_count=False):
+        """The state after Trivium's 1,152 warm-up steps, N ciphers side by side: `key` and `iv` hold 80 N blocks, bit i of
+        input n at block i N + n, every block an encrypted bit.  6,912 N bootstraps in 36 rounds."""
+        if key.total_blocks % TRIVIUM_KEY_BITS or key.total_blocks == 0 or iv.total_blocks != key.total_blocks:
+            raise ValueError(f"Input key and IV must contain {TRIVIUM_KEY_BITS} encrypted bits per input.")
+        n = key.total_blocks // TRIVIUM_KEY_BITS
+        w = key.lwe_dimension + 1
+        state = CudaTriviumState(*(CudaUnsignedRadixCiphertext(CudaVec(bits * n * w, streams), 1, bits * n, key.lwe_dimension)
+                                   for bits in TRIVIUM_REGISTER_BITS))
+        pbs = self._trivium_call("init", n, streams, lambda lib, s, mem, bsks, ksks: lib.hip_trivium_init_async(
+            s, C.byref(state.a._ffi()), C.byref(state.b._ffi()), C.byref(state.c._ffi()), C.byref(key._ffi()),
+            C.byref(iv._ffi()), n, mem, bsks, ksks))
+        return (state, pbs) if return_pbs_count else state
+
+    def trivium_next(self, state, num_steps, streams, return_pbs_count=False, _window=None):
+        """The next `num_steps` keystream bits (a multiple of 64) of every input; the state advances.  Returns num_steps N
+        blocks, the bit of step t of input n at block t N + n.  512 N bootstraps per 64 steps, in two rounds."""
+        if num_steps % TRIVIUM_BATCH_SIZE:
+            raise ValueError(f"The number of steps must be a multiple of {TRIVIUM_BATCH_SIZE}.")
+        n = state.num_inputs
+        w = state.a.lwe_dimension + 1
+        keystream = CudaUnsignedRadixCiphertext(CudaVec(max(1, num_steps * n * w), streams), 1, num_steps * n,
+                                                state.a.lwe_dimension)
+        pbs = self._trivium_call("step", n, streams, lambda lib, s, mem, bsks, ksks: lib.hip_trivium_step_async(
+            s, C.byref(keystream._ffi()), C.byref(state.a._ffi()), C.byref(state.b._ffi()), C.byref(state.c._ffi()), n,
+            num_steps, mem, bsks, ksks), num_steps=num_steps, window=_window)
+        return (keystream, pbs) if return_pbs_count else keystream
+
+    def trivium_generate_keystream(self, key, iv, num_steps, streams):
+        """trivium_init, then trivium_next on a state that is dropped afterwards."""
+        if num_steps % TRIVIUM_BATCH_SIZE:
+            raise ValueError(f"The number of steps must be a multiple of {TRIVIUM_BATCH_SIZE}.")
+        return self.trivium_next(self.trivium_init(key, iv, streams), num_steps, streams)
+
     def scalar_shift_assign(self, ct, shift, streams, left=True, arithmetic=False):
         """ct <<= shift / ct >>= shift (clear amount; radix/scalar_shift.rs unchecked_scalar_{left,right}_shift_assign).
         Logical: ONE integer.  arithmetic=True: the right shift of a two's complement value, every integer of the batch."""
@@ -598,6 +650,19 @@ class CudaUnsignedRadixCiphertext:
         _lib().hip_rerand_64_async(s, self.d_blocks.ptr, zeros.d_vec.ptr, mem, keys)
         _lib().hip_cleanup_rerand_64(s, C.byref(mem))
         self._info[1][:] = 1
+
+
+class CudaTriviumState:
+    """integer/gpu/server_key/radix/trivium.rs CudaTriviumState: the registers a (93 positions), b (84) and c (111) of N
+    ciphers side by side, position p of a register at blocks p N .. p N + N - 1, every block an encrypted bit."""
+
+    def __init__(self, a, b, c):
+        self.a, self.b, self.c = a, b, c
+        counts = [r.total_blocks // bits for r, bits in zip((a, b, c), TRIVIUM_REGISTER_BITS)]
+        assert len(set(counts)) == 1 and all(r.total_blocks == bits * counts[0]
+                                             for r, bits in zip((a, b, c), TRIVIUM_REGISTER_BITS)), \
+            "the registers hold 93, 84 and 111 blocks per input"
+        self.num_inputs = counts[0]
 
 
 # ---------------------------------------------------------------------------------------------- ciphertext compression
