@@ -1044,6 +1044,78 @@ void hip_test_trivium_batch_baseline_async(void *stream, uint32_t gpu_index, voi
                                            void const *r1, void *in2, void const *r2, void *keystream, void *tmp,
                                            uint32_t words, uint32_t inputs, uint64_t message_modulus);
 
+/* ------------------------------------------------------------------ division with remainder, absolute value (extensions)
+ * cuda/include/integer/integer.h:465-499 under hip_ names with the reference's parameter lists, on the shared scratch
+ * protocol; the reference-named symbols remain link stubs.  A call takes a batch of integers ([integer][block], num_blocks
+ * blocks each, capacity from hip_integer_scratch_batch); every round covers the whole batch.  Two's complement operands when
+ * is_signed.  Bit-by-bit restoring division (tfhe-rs unsigned_unchecked_div_rem_parallelized): the divisor's masks and
+ * "a bit above position s is set" flags once per call, then per bit one shift round, the cleaning of the merged remainder,
+ * the overflowing subtraction on the carry tree and one select round; three launches of one kernel form their inputs, no
+ * host synchronisation, upload or row copy inside the loop.
+ * Unsigned division by zero: quotient all ones, remainder = numerator.  Signed: truncation towards zero, the remainder has
+ * the numerator's sign, MIN / -1 wraps to MIN with remainder 0; x / 0 = 1 for x < 0 and -1 for x >= 0, remainder x.
+ * Outputs leave with degree message_modulus - 1 and noise level 1.
+ * Limits (refused at scratch time): message_modulus 4, 8 or 16; 3 (message_modulus - 1) + 2 <= message_modulus *
+ * carry_modulus - 1; noise levels 5 and message_modulus + 1 at most (message_modulus * carry_modulus - 1) /
+ * (message_modulus - 1); what carry propagation accepts — (4, 4), (4, 16), (8, 8) pass, (2, 2) is refused.  Operand blocks
+ * have degree at most message_modulus - 1; the four operands hold the same number of blocks with the key's lwe dimension; no
+ * output overlaps an input or the other output; is_signed equals the scratch's.
+ * hip_integer_div_rem_pbs_count: bootstraps of one division (per pair of a batch); every call checks it against the rounds
+ * it issued.  abs: (x + mask) ^ mask with the sign mask as one row per integer, 1 + propagation + num_blocks bootstraps;
+ * nothing is launched when !is_signed. */
+uint64_t hip_scratch_integer_div_rem_64_async(
+    CudaStreamsFFI streams, bool is_signed, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_div_rem_64_async(CudaStreamsFFI streams,
+                                  CudaRadixCiphertextFFI *quotient,
+                                  CudaRadixCiphertextFFI *remainder,
+                                  CudaRadixCiphertextFFI const *numerator,
+                                  CudaRadixCiphertextFFI const *divisor,
+                                  bool is_signed, int8_t *mem_ptr,
+                                  void *const *bsks, void *const *ksks);
+void hip_cleanup_integer_div_rem_64(CudaStreamsFFI streams,
+                                    int8_t **mem_ptr_void);
+uint64_t hip_scratch_integer_abs_inplace_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, bool is_signed,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_abs_inplace_64_async(CudaStreamsFFI streams,
+                                      CudaRadixCiphertextFFI *ct,
+                                      int8_t *mem_ptr, bool is_signed,
+                                      void *const *bsks, void *const *ksks);
+void hip_cleanup_integer_abs_inplace_64(CudaStreamsFFI streams,
+                                        int8_t **mem_ptr_void);
+uint64_t hip_integer_div_rem_pbs_count(bool is_signed, uint32_t num_blocks, uint32_t message_modulus,
+                                       uint32_t carry_modulus);
+/* tests, benches: the stage kernel alone.  out_g[c][first_out + r] = constant_g on the body word + sum over the terms t of
+ * group g of scalar_t * row_t(c, j), j = first_g + r, on u64 words, rows of `words` words; a term reads row j * step + offset
+ * of its array (step 1, or 0: one row for every j), below row 0 its stand-in row (or nothing: null); arrays hold their
+ * integers `stride` rows apart and `extent` rows each.  Up to 4 groups of up to 4 terms.  HOST arrays: outs / constants one
+ * entry per group, group_u32 six (stride, extent, first_out, first, rows, terms); srcs / stands / scalars four per group
+ * (term t of group g at 4 g + t), term_u32 six per term (stride, extent, offset as int32, step, stand_stride, stand_row).
+ * Refused: an output that overlaps a row read or another output, a row outside its array, more groups or terms. */
+void hip_test_divrem_sum_async(void *stream, uint32_t gpu_index, uint32_t words, uint32_t integers, uint32_t groups,
+                               void *const *outs, uint64_t const *constants, uint32_t const *group_u32,
+                               void const *const *srcs, void const *const *stands, uint64_t const *scalars,
+                               uint32_t const *term_u32);
+/* benches: stage 1, 2 or 3 of iteration s of the division loop composed from device copies, memsets and pairwise additions
+ * in the reference's order (cuda/src/integer/div_rem.cuh:589-870).  Arrays hold their integers num_blocks rows apart (fl,
+ * up: one row per integer).  Stage 1 reads r1, r2, num and writes in1; stage 2 reads s1, s2, negd, neglow (this iteration's
+ * low part, null when the top block is whole), consts (num_blocks trivial rows of message_modulus - 1) and writes in2 and v;
+ * stage 3 reads cl, v, fl, up (null in the last iteration), one (a trivial 1), zero_idx (num_blocks zeros on the device) and
+ * writes in3.  tmp: 2 num_blocks + 1 rows. */
+void hip_test_divrem_iteration_baseline_async(void *stream, uint32_t gpu_index, void const *r1, void const *r2,
+                                              void const *num, void const *s1, void const *s2, void const *negd,
+                                              void const *neglow, void const *cl, void *v, void const *fl, void const *up,
+                                              void const *consts, void const *one, void const *zero_idx, void *in1, void *in2,
+                                              void *in3, void *tmp, uint32_t words, uint32_t num_blocks, uint32_t batch,
+                                              uint32_t s, uint32_t bits, uint64_t message_modulus, uint32_t stage);
+
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's
  * cuda/include/pbs/programmable_bootstrap.h:57-60,68-72,92-97,102-103 and cuda/include/fft/fft128.h), under hip_ names

@@ -2186,6 +2186,7 @@ struct OprfMem : ScratchHeader {
 }  // namespace tfhe_hip
 
 #include "radix_trivium.h"  // TriviumMem and the tap kernel, on the round driver and the owners above
+#include "radix_divrem.h"   // DivRemMem, AbsMem and the stage kernel, on the round driver and the carry propagation
 
 using namespace tfhe_hip;
 using namespace tfhe_hip::radix;
@@ -3482,6 +3483,192 @@ void hip_test_trivium_batch_baseline_async(void *stream, uint32_t gpu_index, voi
   uint64_t *const regs[3] = {(uint64_t *)a, (uint64_t *)b, (uint64_t *)c};
   trivium_batch_baseline((hipStream_t)stream, regs, (uint64_t *)in1, (const uint64_t *)r1, (uint64_t *)in2,
                          (const uint64_t *)r2, (uint64_t *)keystream, (uint64_t *)tmp, words, inputs, message_modulus);
+}
+
+// ---- integer.h:465-499: division with remainder and absolute value (radix_divrem.h; hip_ names with the reference's
+// parameter lists: the reference-named symbols stay link stubs).  A batch of integer pairs per call, capacity from
+// hip_integer_scratch_batch; two's complement operands when is_signed.
+uint64_t hip_scratch_integer_div_rem_64_async(CudaStreamsFFI streams, bool is_signed, int8_t **mem_ptr,
+                                              CudaLweBootstrapKeyParamsFFI bsk_params,
+                                              CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+                                              uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+                                              enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<DivRemMem>(streams, mem_ptr, allocate_gpu_memory, "div_rem", [&](DivRemMem &m) {
+    m.core.init(streams, p, num_blocks, g_scratch_batch, is_signed, false, "div_rem");
+  });
+}
+
+void hip_integer_div_rem_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *quotient, CudaRadixCiphertextFFI *remainder,
+                                  CudaRadixCiphertextFFI const *numerator, CudaRadixCiphertextFFI const *divisor,
+                                  bool is_signed, int8_t *mem_ptr, void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "div_rem";
+  auto *m = scratch_use<DivRemMem>(mem_ptr, who);
+  DivRemCore &d = m->core;
+  const Params &p = d.drv.p;
+  HX_PANIC_IF_FALSE(quotient && remainder && numerator && divisor && quotient->ptr && remainder->ptr && numerator->ptr &&
+                        divisor->ptr && bsks && ksks, "%s: null pointer", who);
+  HX_PANIC_IF_FALSE(is_signed == d.is_signed, "%s: the scratch was created for %s operands, the call is %s", who,
+                    d.is_signed ? "signed" : "unsigned", is_signed ? "signed" : "unsigned");
+  const CudaRadixCiphertextFFI *const ops[4] = {quotient, remainder, numerator, divisor};
+  for (const CudaRadixCiphertextFFI *o : ops) {
+    HX_PANIC_IF_FALSE(o->num_radix_blocks == numerator->num_radix_blocks,
+                      "%s: quotient, remainder, numerator and divisor hold %u, %u, %u and %u blocks: they must be the same", who,
+                      quotient->num_radix_blocks, remainder->num_radix_blocks, numerator->num_radix_blocks,
+                      divisor->num_radix_blocks);
+    HX_PANIC_IF_FALSE(o->lwe_dimension == p.big_n, "%s: the blocks' lwe dimension should be %u", who, p.big_n);
+  }
+  const uint32_t L = d.blocks, cts = batch_of(numerator, L, who);
+  HX_PANIC_IF_FALSE(cts >= 1 && cts <= d.max_cts, "%s: %u integers exceed the scratch capacity %u", who, cts, d.max_cts);
+  check_clean({numerator, divisor}, cts * L, p.msg, who, "numerator and divisor must be clean (propagate them first)");
+  const size_t w = (size_t)p.big_n + 1, bytes = (size_t)cts * L * w * sizeof(uint64_t);
+  const auto meet = [bytes](const void *x, const void *y) {
+    const char *a = (const char *)x, *b = (const char *)y;
+    return a < b + bytes && b < a + bytes;
+  };
+  HX_PANIC_IF_FALSE(!meet(quotient->ptr, remainder->ptr) && !meet(quotient->ptr, numerator->ptr) &&
+                        !meet(quotient->ptr, divisor->ptr) && !meet(remainder->ptr, numerator->ptr) &&
+                        !meet(remainder->ptr, divisor->ptr),
+                    "%s: an output overlaps an input or the other output", who);
+  const uint64_t before = d.issued(), want = (uint64_t)cts * DivRemCore::division_pbs(is_signed, L, p.msg);
+  d.div_rem(streams, (const uint64_t *)numerator->ptr, (const uint64_t *)divisor->ptr, cts, ksks, bsks);
+  const hipStream_t st = S0(streams);
+  HX_CHECK(hipMemcpyAsync(quotient->ptr, d.ptr(d.OUT2), bytes, hipMemcpyDeviceToDevice, st));
+  HX_CHECK(hipMemcpyAsync(remainder->ptr, d.ptr(d.OUT2) + (size_t)cts * L * w, bytes, hipMemcpyDeviceToDevice, st));
+  HX_PANIC_IF_FALSE(d.issued() - before == want, "%s: %llu bootstraps issued, %llu counted", who,
+                    (unsigned long long)(d.issued() - before), (unsigned long long)want);
+  set_block_info(quotient, 0, cts * L, p.msg - 1, 1);
+  set_block_info(remainder, 0, cts * L, p.msg - 1, 1);
+}
+
+void hip_cleanup_integer_div_rem_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<DivRemMem>(streams, mem_ptr_void, "cleanup div_rem");
+}
+
+// bootstraps of one division of two integers of num_blocks blocks (a batch issues that many per pair); every call checks it
+// against the rounds it issued
+uint64_t hip_integer_div_rem_pbs_count(bool is_signed, uint32_t num_blocks, uint32_t message_modulus, uint32_t carry_modulus) {
+  (void)carry_modulus;
+  return DivRemCore::division_pbs(is_signed, num_blocks, message_modulus);
+}
+
+uint64_t hip_scratch_integer_abs_inplace_64_async(CudaStreamsFFI streams, int8_t **mem_ptr, bool is_signed,
+                                                  CudaLweBootstrapKeyParamsFFI bsk_params,
+                                                  CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+                                                  uint32_t message_modulus, uint32_t carry_modulus, bool allocate_gpu_memory,
+                                                  enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<AbsMem>(streams, mem_ptr, allocate_gpu_memory, "abs", [&](AbsMem &m) {
+    m.core.init(streams, p, num_blocks, g_scratch_batch, is_signed, true, "abs");
+  });
+}
+
+// an unsigned value is its own absolute value: nothing is launched (abs.cuh:38)
+void hip_integer_abs_inplace_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *ct, int8_t *mem_ptr, bool is_signed,
+                                      void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  auto *m = scratch_use<AbsMem>(mem_ptr, "abs");
+  DivRemCore &d = m->core;
+  const Params &p = d.drv.p;
+  HX_PANIC_IF_FALSE(is_signed == d.is_signed, "abs: the scratch was created for %s operands, the call is %s",
+                    d.is_signed ? "signed" : "unsigned", is_signed ? "signed" : "unsigned");
+  const uint32_t cts = shift_family_batch(d.blocks, d.max_cts, p, ct, bsks, ksks, "abs");
+  check_clean({ct}, cts * d.blocks, p.msg, "abs", "the value must be clean (propagate it first)");
+  if (!is_signed) return;
+  const uint64_t before = d.issued(), want = (uint64_t)cts * DivRemCore::abs_pbs(d.blocks);
+  d.abs_inplace(streams, (uint64_t *)ct->ptr, cts, ksks, bsks);
+  HX_PANIC_IF_FALSE(d.issued() - before == want, "abs: %llu bootstraps issued, %llu counted",
+                    (unsigned long long)(d.issued() - before), (unsigned long long)want);
+  set_block_info(ct, 0, cts * d.blocks, p.msg - 1, 1);
+}
+
+void hip_cleanup_integer_abs_inplace_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<AbsMem>(streams, mem_ptr_void, "cleanup abs");
+}
+
+// lwe_divrem_sum_kernel alone on a caller-given table (tests, tools/bench_div_rem.py).  HOST arrays: group g's entries at
+// g in outs / constants and at 6 g .. 6 g + 5 in group_u32 (stride, extent, first_out, first, rows, terms); term t of group
+// g at 4 g + t in srcs / stands / scalars and at 6 (4 g + t) .. + 5 in term_u32 (stride, extent, offset as int32, step,
+// stand_stride, stand_row)
+void hip_test_divrem_sum_async(void *stream, uint32_t gpu_index, uint32_t words, uint32_t integers, uint32_t groups,
+                               void *const *outs, uint64_t const *constants, uint32_t const *group_u32,
+                               void const *const *srcs, void const *const *stands, uint64_t const *scalars,
+                               uint32_t const *term_u32) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(groups <= kDivGroups && outs && constants && group_u32 && srcs && stands && scalars && term_u32,
+                    "hip_test_divrem_sum: %u groups (at most %u) or a null array", groups, kDivGroups);
+  DivTable t = div_table(words, integers);
+  t.groups = groups;
+  for (uint32_t g = 0; g < groups; ++g) {
+    const uint32_t *gu = group_u32 + 6 * g;
+    HX_PANIC_IF_FALSE(gu[5] <= kDivTerms, "hip_test_divrem_sum: group %u has %u terms (at most %u)", g, gu[5], kDivTerms);
+    DivGroup &G = t.g[g];
+    G.out = (uint64_t *)outs[g], G.constant = constants[g];
+    G.stride = gu[0], G.extent = gu[1], G.first_out = gu[2], G.first = gu[3], G.rows = gu[4], G.terms = gu[5];
+    for (uint32_t i = 0; i < G.terms; ++i) {
+      const uint32_t k = kDivTerms * g + i, *tu = term_u32 + 6 * k;
+      G.t[i] = DivTerm{(const uint64_t *)srcs[k], (const uint64_t *)stands[k], scalars[k], tu[0], tu[1], (int32_t)tu[2], tu[3],
+                       tu[4], tu[5]};
+    }
+  }
+  launch_divrem_sum((hipStream_t)stream, t);
+}
+
+// benches: the data movement of iteration s of the loop composed from the primitives the layer had before the kernel, in
+// the reference's order (div_rem.cuh:589-870): per integer the numerator block and the remainder pushed one block up into
+// a workspace and packed against the remainder, the merged remainder added, copied into the subtraction's operand, the
+// negated divisor added to its whole blocks and to its trimmed top block, the blocks above filled from constant rows; the
+// flags summed into one row and added through a broadcast index to the clean and to the new remainder.
+// Arrays as radix_divrem.h names them, integers L rows apart (fl, up: one row per integer): in1 receives launch 1's rows,
+// in2 launch 2's merged remainder, v the subtraction's operand, in3 launch 3's rows.  negd / neglow: the negated divisor and
+// the negated low part for this iteration (null when the top block is whole); consts: L rows of the trivial msg - 1; one: a
+// trivial 1; zero_idx: L zeros on the device; tmp: 2 L + 1 rows.
+void hip_test_divrem_iteration_baseline_async(void *stream, uint32_t gpu_index, void const *r1, void const *r2,
+                                              void const *num, void const *s1, void const *s2, void const *negd,
+                                              void const *neglow, void const *cl, void *v, void const *fl, void const *up,
+                                              void const *consts, void const *one, void const *zero_idx, void *in1, void *in2,
+                                              void *in3, void *tmp, uint32_t words, uint32_t num_blocks, uint32_t batch,
+                                              uint32_t s, uint32_t bits, uint64_t message_modulus, uint32_t stage) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(r1 && r2 && num && s1 && s2 && negd && cl && v && fl && consts && one && zero_idx && in1 && in2 && in3 &&
+                        tmp && words && num_blocks && batch && bits && s < bits * num_blocks && stage >= 1 && stage <= 3,
+                    "hip_test_divrem_iteration_baseline: null pointer, empty rows or an iteration beyond the last");
+  const hipStream_t st = (hipStream_t)stream;
+  const uint32_t L = num_blocks, B = bits * L, n = s / bits + 1, blk = (B - 1 - s) / bits, t_low = (s + 1) % bits,
+                 whole = t_low ? n - 1 : n;
+  HX_PANIC_IF_FALSE(!t_low || neglow, "hip_test_divrem_iteration_baseline: the top block is trimmed and neglow is null");
+  const size_t w = words, bw = w * sizeof(uint64_t);
+  const uint64_t f = s + 1 == B ? 2 : 3;
+  const auto U = [](const void *p) { return (const uint64_t *)p; };
+  const auto copy = [&](uint64_t *out, const uint64_t *x, size_t rows) {
+    HX_CHECK(hipMemcpyAsync(out, x, rows * bw, hipMemcpyDeviceToDevice, st));
+  };
+  uint64_t *ws = (uint64_t *)tmp, *ws2 = ws + L * w, *flag = ws2 + L * w;
+  for (uint32_t c = 0; c < batch; ++c) {
+    const size_t at = (size_t)c * L * w;
+    if (stage == 1) {
+      copy(ws, U(num) + at + blk * w, 1);
+      if (n > 1) copy(ws + w, U(r1) + at, n - 1);
+      axpy(st, (uint64_t *)in1 + (size_t)c * n * w, nullptr, U(r1) + at, nullptr, message_modulus, ws, nullptr, words, n);
+      HX_CHECK(hipMemsetAsync(ws2, 0, bw, st));
+      if (n > 1) copy(ws2 + w, U(r2) + at, n - 1);
+      axpy(st, (uint64_t *)in1 + (size_t)(batch + c) * n * w, nullptr, U(r2) + at, nullptr, message_modulus, ws2, nullptr, words, n);
+    } else if (stage == 2) {
+      uint64_t *merged = (uint64_t *)in2 + (size_t)c * n * w, *vc = (uint64_t *)v + at;
+      axpy(st, merged, nullptr, U(s1) + at, nullptr, 1, U(s2) + at, nullptr, words, n);
+      copy(vc, merged, n);
+      if (whole) axpy(st, vc, nullptr, vc, nullptr, 1, U(negd) + at, nullptr, words, whole);
+      if (t_low) axpy(st, vc + (n - 1) * w, nullptr, vc + (n - 1) * w, nullptr, 1, U(neglow) + at + (n - 1) * w, nullptr, words, 1);
+      if (n < L) copy(vc + n * w, U(consts) + n * w, L - n);
+    } else {
+      axpy(st, flag, nullptr, U(fl) + c * w, nullptr, ~(uint64_t)0, U(one), nullptr, words, 1);
+      if (up) axpy(st, flag, nullptr, flag, nullptr, 1, U(up) + c * w, nullptr, words, 1);
+      axpy(st, (uint64_t *)in3 + (size_t)c * n * w, nullptr, U(cl) + at, nullptr, f, flag, U(zero_idx), words, n);
+      axpy(st, (uint64_t *)in3 + (size_t)(batch + c) * n * w, nullptr, U(v) + at, nullptr, f, flag, U(zero_idx), words, n);
+      copy((uint64_t *)in3 + ((size_t)2 * batch * n + c) * w, flag, 1);
+    }
+  }
 }
 
 // number of PBS one carry propagation / one multiplication of `num_blocks` blocks issues (for benches)

@@ -289,6 +289,16 @@ SIGNATURES = {
     "hip_test_trivium_set_window": (None, [_v, _u32]),
     "hip_test_tap_sum_async": (None, [_v, _u32, _u32, _u32, _u32, _v, _v, _v, _v, _v, _v, _v]),
     "hip_test_trivium_batch_baseline_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _v, _v, _v, _v, _u32, _u32, _u64]),
+    # division with remainder, absolute value
+    "hip_scratch_integer_div_rem_64_async": (_u64, [_S, _b, _i8pp, _BK, _KK, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_div_rem_64_async": (None, [_S, _R, _R, _R, _R, _b, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_div_rem_64": (None, [_S, _i8pp]),
+    "hip_scratch_integer_abs_inplace_64_async": (_u64, [_S, _i8pp, _b, _BK, _KK, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_abs_inplace_64_async": (None, [_S, _R, _v, _b, _i8pp, _i8pp]),
+    "hip_cleanup_integer_abs_inplace_64": (None, [_S, _i8pp]),
+    "hip_integer_div_rem_pbs_count": (_u64, [_b, _u32, _u32, _u32]),
+    "hip_test_divrem_sum_async": (None, [_v, _u32, _u32, _u32, _u32, _v, _v, _v, _v, _v, _v, _v]),
+    "hip_test_divrem_iteration_baseline_async": (None, [_v] + [_u32] + [_v] * 18 + [_u32] * 5 + [_u64, _u32]),
     # 128-bit PBS and noise squashing
     "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
     "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),

@@ -371,6 +371,52 @@ class CudaServerKey:
         return self._shift_family("shift_and_rotate", ct, (2 if left else 3, False), (C.byref(amount._ffi()),), streams,
                                   count=return_pbs_count)
 
+    # ---- division (integer/gpu/server_key/radix/div_mod.rs, abs.rs)
+    def div_rem(self, numerator, divisor, streams, signed=False, return_pbs_count=False):
+        """(numerator / divisor, numerator % divisor), every pair of the batch in the same rounds (radix/div_mod.rs
+        unchecked_div_rem).  signed: two's complement operands, truncation towards zero, the remainder takes the
+        numerator's sign, MIN / -1 wraps to MIN.  Unsigned x / 0 = all ones, x % 0 = x; signed x / 0 = 1 for x < 0, else -1."""
+        assert numerator.num_integers == divisor.num_integers and numerator.num_blocks == divisor.num_blocks
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        q = CudaUnsignedRadixCiphertext.zeros_like(numerator, streams)
+        r = CudaUnsignedRadixCiphertext.zeros_like(numerator, streams)
+        mem = C.c_void_p()
+        lib = _lib()
+        lib.hip_integer_scratch_batch(numerator.num_integers)
+        lib.hip_scratch_integer_div_rem_64_async(s, bool(signed), C.byref(mem), self._bsk_params(), self._ksk_params(),
+                                                 numerator.num_blocks, self.message_modulus, self.carry_modulus, True,
+                                                 self._noise_reduction())
+        lib.hip_integer_scratch_batch(1)
+        lib.hip_integer_div_rem_64_async(s, C.byref(q._ffi()), C.byref(r._ffi()), C.byref(numerator._ffi()),
+                                         C.byref(divisor._ffi()), bool(signed), mem, bsks, ksks)
+        lib.hip_cleanup_integer_div_rem_64(s, C.byref(mem))
+        if not return_pbs_count:
+            return q, r
+        pbs = int(lib.hip_integer_div_rem_pbs_count(bool(signed), numerator.num_blocks, self.message_modulus,
+                                                    self.carry_modulus))
+        return q, r, pbs * numerator.num_integers
+
+    def div(self, numerator, divisor, streams, signed=False):
+        return self.div_rem(numerator, divisor, streams, signed)[0]
+
+    def rem(self, numerator, divisor, streams, signed=False):
+        return self.div_rem(numerator, divisor, streams, signed)[1]
+
+    def abs_assign(self, ct, streams):
+        """ct = |ct| for two's complement integers, every integer of the batch (radix/abs.rs unchecked_abs); |MIN| = MIN."""
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        mem = C.c_void_p()
+        lib = _lib()
+        lib.hip_integer_scratch_batch(ct.num_integers)
+        lib.hip_scratch_integer_abs_inplace_64_async(s, C.byref(mem), True, self._bsk_params(), self._ksk_params(),
+                                                     ct.num_blocks, self.message_modulus, self.carry_modulus, True,
+                                                     self._noise_reduction())
+        lib.hip_integer_scratch_batch(1)
+        lib.hip_integer_abs_inplace_64_async(s, C.byref(ct._ffi()), mem, True, bsks, ksks)
+        lib.hip_cleanup_integer_abs_inplace_64(s, C.byref(mem))
+
     # ---- Trivium transciphering (integer/gpu/server_key/radix/trivium.rs)
     def _trivium_call(self, kind, num_inputs, streams, launch, num_steps=0, window=None):
         """scratch -> launch -> cleanup of hip_trivium_{init,step}; returns the published bootstrap count of the call"""
