@@ -45,6 +45,12 @@ pub type EXPAND_KIND = ffi::c_uint;
 pub const RERAND_MODE_RERAND_WITH_KS: RERAND_MODE = 0;
 pub const RERAND_MODE_RERAND_WITHOUT_KS: RERAND_MODE = 1;
 pub type RERAND_MODE = ffi::c_uint;
+pub const Direction_Trailing: Direction = 0;
+pub const Direction_Leading: Direction = 1;
+pub type Direction = ffi::c_uint;
+pub const BitValue_Zero: BitValue = 0;
+pub const BitValue_One: BitValue = 1;
+pub type BitValue = ffi::c_uint;
 
 #[repr(C)]
 #[derive(Debug, Copy, Clone)]

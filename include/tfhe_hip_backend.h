@@ -52,6 +52,9 @@ enum KS_TYPE { BIG_TO_SMALL = 0, SMALL_TO_BIG = 1 };
 enum EXPAND_KIND { NO_CASTING = 0, CASTING = 1, SANITY_CHECK = 2 };
 /* cuda/include/integer/integer.h:45-48 */
 enum RERAND_MODE { RERAND_WITH_KS = 0, RERAND_WITHOUT_KS = 1 };
+/* cuda/include/integer/integer.h:41-43 */
+enum Direction { Trailing = 0, Leading = 1 };
+enum BitValue { Zero = 0, One = 1 };
 
 /* ------------------------------------------------------------------ device runtime
  * backends/tfhe-cuda-common/cuda/include/device.h:58-92 (cuda_bind.rs:5-150) */
@@ -1115,6 +1118,83 @@ void hip_test_divrem_iteration_baseline_async(void *stream, uint32_t gpu_index, 
                                               void const *consts, void const *one, void const *zero_idx, void *in1, void *in2,
                                               void *in3, void *tmp, uint32_t words, uint32_t num_blocks, uint32_t batch,
                                               uint32_t s, uint32_t bits, uint64_t message_modulus, uint32_t stage);
+
+/* ------------------------------------------------------------------ bit counts: runs, ilog2, popcounts (extensions)
+ * cuda/include/integer/integer.h:648-662 and :701-718 under hip_ names with the reference's parameter lists, on the shared
+ * scratch protocol; the reference-named symbols remain link stubs.  hip_*_count_ones_64 is our own (the reference's GPU
+ * backend has no popcount entry point): bit_value One counts the ones, Zero the zeros.  Out of place.  A call takes a batch
+ * of integers ([integer][block], num_blocks blocks each, capacity from hip_integer_scratch_batch) and writes
+ * counter_num_blocks blocks per integer; a signed operand is counted on its two's complement bits as they stand.
+ * With b = log2(message_modulus), B = b * num_blocks: counter_num_blocks = ceil((floor(log2 B) + 1) / b) for the runs and
+ * the popcounts, ceil((floor(log2(B - 1)) + 2) / b) for ilog2; another value is refused at scratch time.
+ * Runs: ceil(log2 num_blocks) scan rounds (the first reads the operand's blocks in place, bivariate: "my run if my neighbour
+ * is a full run"), then the sum of num_blocks single-block terms and one carry propagation.  ilog2 = sum (b - t_i) - 1 on the
+ * scan of the leading zeros: no round more; ilog2(0) is all ones.  Popcounts: one round over the pairs of blocks.
+ * hip_integer_ilog2_64_async keeps the three trivial operands of the reference's parameter list: they must not be null and
+ * trivial_ct_neg_n must hold counter_num_blocks blocks, as the reference checks; they are otherwise NOT read.
+ * Outputs leave with degree message_modulus - 1 and noise level 1.
+ * Refused at scratch time: message_modulus below 3 or fewer than 16 values per block (the carry propagation), a
+ * message_modulus that is not a power of two.  Refused by a call: an operand block of degree above message_modulus - 1, an
+ * output that overlaps the input, more integers than the scratch holds, a scratch of another kind.
+ * hip_integer_bit_count_pbs_count / _rounds: bootstraps per integer and rounds of one call, kind 0 a run, 1 ilog2, 2 a
+ * popcount; functions of their four arguments; every call checks the bootstraps it issued against the first. */
+uint64_t hip_scratch_integer_count_of_consecutive_bits_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t counter_num_blocks, uint32_t message_modulus,
+    uint32_t carry_modulus, enum Direction direction, enum BitValue bit_value,
+    bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_count_of_consecutive_bits_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *output_ct,
+    CudaRadixCiphertextFFI const *input_ct, int8_t *mem_ptr, void *const *bsks,
+    void *const *ksks);
+void hip_cleanup_integer_count_of_consecutive_bits_64(CudaStreamsFFI streams,
+                                                      int8_t **mem_ptr_void);
+uint64_t hip_scratch_integer_ilog2_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+    uint32_t carry_modulus, uint32_t input_num_blocks,
+    uint32_t counter_num_blocks, uint32_t num_bits_in_ciphertext,
+    bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_ilog2_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *output_ct,
+    CudaRadixCiphertextFFI const *input_ct,
+    CudaRadixCiphertextFFI const *trivial_ct_neg_n,
+    CudaRadixCiphertextFFI const *trivial_ct_2,
+    CudaRadixCiphertextFFI const *trivial_ct_m_minus_1_block, int8_t *mem_ptr,
+    void *const *bsks, void *const *ksks);
+void hip_cleanup_integer_ilog2_64(CudaStreamsFFI streams,
+                                  int8_t **mem_ptr_void);
+uint64_t hip_scratch_integer_count_ones_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+    uint32_t counter_num_blocks, uint32_t message_modulus,
+    uint32_t carry_modulus, enum BitValue bit_value, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_count_ones_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *output_ct,
+    CudaRadixCiphertextFFI const *input_ct, int8_t *mem_ptr, void *const *bsks,
+    void *const *ksks);
+void hip_cleanup_integer_count_ones_64(CudaStreamsFFI streams,
+                                       int8_t **mem_ptr_void);
+uint64_t hip_integer_bit_count_pbs_count(uint32_t kind, uint32_t num_blocks, uint32_t message_modulus,
+                                         uint32_t carry_modulus);
+uint32_t hip_integer_bit_count_rounds(uint32_t kind, uint32_t num_blocks, uint32_t message_modulus,
+                                      uint32_t carry_modulus);
+/* tests, benches: the pack kernel alone.  out[c][g] = s0 * x[c * x_stride + first + g * step] + s1 * x[c * x_stride + first +
+ * g * step + delta] on u64 words, rows of `words` words, g < ceil(rows / step); a partner g * step + delta outside
+ * 0 .. rows - 1 contributes nothing.  out is dense.  Refused: a null or empty operand, delta == 0 or |delta| >= rows, a step
+ * other than 1 or 2, an output that overlaps the rows read, more than 65,535 integers. */
+void hip_test_pair_pack_async(void *stream, uint32_t gpu_index, void *out, void const *x, uint64_t s0, uint64_t s1,
+                              uint32_t words, uint32_t batch, uint32_t x_stride, uint32_t first, uint32_t rows,
+                              uint32_t step, int delta);
+/* benches: the same rows for s0 = 1, step = 1, first = 0, x_stride = rows composed per integer from a device copy and a
+ * memset into tmp (batch * rows rows), then one pairwise addition that packs. */
+void hip_test_pair_pack_baseline_async(void *stream, uint32_t gpu_index, void *out, void const *x, void *tmp, uint64_t s1,
+                                       uint32_t words, uint32_t batch, uint32_t rows, int delta);
 
 /* ------------------------------------------------------------------ 128-bit PBS and noise squashing (extensions)
  * The programmable bootstrap over the 128-bit torus that noise squashing runs on (fft128_pbs.rs; the reference's

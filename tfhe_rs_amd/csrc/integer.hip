@@ -2187,6 +2187,7 @@ struct OprfMem : ScratchHeader {
 
 #include "radix_trivium.h"  // TriviumMem and the tap kernel, on the round driver and the owners above
 #include "radix_divrem.h"   // DivRemMem, AbsMem and the stage kernel, on the round driver and the carry propagation
+#include "radix_bitcount.h" // the bit-count scratches and the pair-pack kernel, on the round driver, the sums and the propagation
 
 using namespace tfhe_hip;
 using namespace tfhe_hip::radix;
@@ -3669,6 +3670,170 @@ void hip_test_divrem_iteration_baseline_async(void *stream, uint32_t gpu_index, 
       copy((uint64_t *)in3 + ((size_t)2 * batch * n + c) * w, flag, 1);
     }
   }
+}
+
+// ---- integer.h:41-43, :648-662, :701-718: runs of leading / trailing bits, ilog2, and the popcounts (radix_bitcount.h; hip_
+// names with the reference's parameter lists: the reference-named symbols stay link stubs; count_ones is our own, the
+// reference's GPU backend has no entry point for it).  Out of place; a batch of integers per call, capacity from
+// hip_integer_scratch_batch; a signed operand is counted on its two's complement bits as they stand.
+namespace {
+void bit_count_scratch_params(CudaLweBootstrapKeyParamsFFI bsk_params, CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t msg,
+                                  uint32_t carry, uint32_t noise, const char *who, Params &p) {
+  BitCountCore::check_base(msg, carry, who);  // (before make_params: its refusal of these moduli names no entry point)
+  p = make_params(bsk_params, ksk_params, msg, carry, noise);
+}
+void bit_count_call(const CudaStreamsFFI &streams, BitCountCore &d, CudaRadixCiphertextFFI *output_ct,
+                    CudaRadixCiphertextFFI const *input_ct, void *const *bsks, void *const *ksks, const char *who) {
+  const Params &p = d.drv.p;
+  HX_PANIC_IF_FALSE(output_ct && input_ct && output_ct->ptr && input_ct->ptr && bsks && ksks, "%s: null pointer", who);
+  HX_PANIC_IF_FALSE(output_ct->lwe_dimension == p.big_n && input_ct->lwe_dimension == p.big_n,
+                    "%s: the blocks' lwe dimension should be %u", who, p.big_n);
+  const uint32_t L = d.blocks, nc = d.counter, cts = batch_of(input_ct, L, who);
+  HX_PANIC_IF_FALSE(cts >= 1 && cts <= d.max_cts, "%s: %u integers exceed the scratch capacity %u", who, cts, d.max_cts);
+  HX_PANIC_IF_FALSE(output_ct->num_radix_blocks == cts * nc, "%s: the output holds %u blocks, %u integers take %u counter blocks each",
+                    who, output_ct->num_radix_blocks, cts, nc);
+  check_clean({input_ct}, cts * L, p.msg, who, "the operand must be clean (propagate it first)");
+  const size_t w = (size_t)p.big_n + 1;
+  const char *o = (const char *)output_ct->ptr, *i = (const char *)input_ct->ptr;
+  HX_PANIC_IF_FALSE(o + (size_t)cts * nc * w * sizeof(uint64_t) <= i || i + (size_t)cts * L * w * sizeof(uint64_t) <= o,
+                    "%s: the output and the input must be different ciphertexts", who);
+  const uint64_t before = d.issued(), want = (uint64_t)cts * BitCountCore::pbs_count(d.kind, L, p.msg, p.carry);
+  d.run(streams, (uint64_t *)output_ct->ptr, (const uint64_t *)input_ct->ptr, cts, ksks, bsks);
+  HX_PANIC_IF_FALSE(d.issued() - before == want, "%s: %llu bootstraps issued, %llu counted", who,
+                    (unsigned long long)(d.issued() - before), (unsigned long long)want);
+  set_block_info(output_ct, 0, cts * nc, p.msg - 1, 1);
+}
+}  // namespace
+
+uint64_t hip_scratch_integer_count_of_consecutive_bits_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params, CudaLweKeyswitchKeyParamsFFI ksk_params,
+    uint32_t num_blocks, uint32_t counter_num_blocks, uint32_t message_modulus, uint32_t carry_modulus, enum Direction direction,
+    enum BitValue bit_value, bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const char *who = "count_of_consecutive_bits";
+  Params p;
+  bit_count_scratch_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type, who, p);
+  HX_PANIC_IF_FALSE((direction == Trailing || direction == Leading) && (bit_value == Zero || bit_value == One),
+                    "%s: direction %u, bit value %u", who, (uint32_t)direction, (uint32_t)bit_value);
+  return scratch_create<ConsecutiveBitsMem>(streams, mem_ptr, allocate_gpu_memory, who, [&](ConsecutiveBitsMem &m) {
+    m.core.init(streams, p, kBitCountRuns, num_blocks, counter_num_blocks, g_scratch_batch, direction == Leading, bit_value == One, who);
+  });
+}
+void hip_integer_count_of_consecutive_bits_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *output_ct,
+                                                    CudaRadixCiphertextFFI const *input_ct, int8_t *mem_ptr, void *const *bsks,
+                                                    void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "count_of_consecutive_bits";
+  bit_count_call(streams, scratch_use<ConsecutiveBitsMem>(mem_ptr, who)->core, output_ct, input_ct, bsks, ksks, who);
+}
+void hip_cleanup_integer_count_of_consecutive_bits_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<ConsecutiveBitsMem>(streams, mem_ptr_void, "cleanup count_of_consecutive_bits");
+}
+
+uint64_t hip_scratch_integer_ilog2_64_async(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+                                            CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+                                            uint32_t carry_modulus, uint32_t input_num_blocks, uint32_t counter_num_blocks,
+                                            uint32_t num_bits_in_ciphertext, bool allocate_gpu_memory,
+                                            enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const char *who = "ilog2";
+  Params p;
+  bit_count_scratch_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type, who, p);
+  HX_PANIC_IF_FALSE(num_bits_in_ciphertext == input_num_blocks * BitCountCore::log2_ceil(message_modulus),
+                    "%s: num_bits_in_ciphertext is %u, %u blocks of modulus %u hold %u", who, num_bits_in_ciphertext, input_num_blocks,
+                    message_modulus, input_num_blocks * BitCountCore::log2_ceil(message_modulus));
+  return scratch_create<Ilog2Mem>(streams, mem_ptr, allocate_gpu_memory, who, [&](Ilog2Mem &m) {
+    m.core.init(streams, p, kBitCountIlog2, input_num_blocks, counter_num_blocks, g_scratch_batch, true, false, who);
+  });
+}
+// the three trivial operands are those of the reference's parameter list: their block counts are checked as the reference
+// checks them (trivial_ct_neg_n against counter_num_blocks), they are otherwise NOT read — the - 1 of
+// sum (b - t[i]) - 1 is a row set the scratch holds
+void hip_integer_ilog2_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *output_ct, CudaRadixCiphertextFFI const *input_ct,
+                                CudaRadixCiphertextFFI const *trivial_ct_neg_n, CudaRadixCiphertextFFI const *trivial_ct_2,
+                                CudaRadixCiphertextFFI const *trivial_ct_m_minus_1_block, int8_t *mem_ptr, void *const *bsks,
+                                void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "ilog2";
+  BitCountCore &d = scratch_use<Ilog2Mem>(mem_ptr, who)->core;
+  HX_PANIC_IF_FALSE(trivial_ct_neg_n && trivial_ct_2 && trivial_ct_m_minus_1_block, "%s: null pointer", who);
+  HX_PANIC_IF_FALSE(trivial_ct_neg_n->num_radix_blocks == d.counter,
+                    "%s: num blocks of trivial_ct_neg_n should be equal to counter_num_blocks", who);
+  bit_count_call(streams, d, output_ct, input_ct, bsks, ksks, who);
+}
+void hip_cleanup_integer_ilog2_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<Ilog2Mem>(streams, mem_ptr_void, "cleanup ilog2");
+}
+
+uint64_t hip_scratch_integer_count_ones_64_async(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+                                                 CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t num_blocks,
+                                                 uint32_t counter_num_blocks, uint32_t message_modulus, uint32_t carry_modulus,
+                                                 enum BitValue bit_value, bool allocate_gpu_memory,
+                                                 enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  const char *who = "count_ones";
+  Params p;
+  bit_count_scratch_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type, who, p);
+  HX_PANIC_IF_FALSE(bit_value == Zero || bit_value == One, "%s: bit value %u", who, (uint32_t)bit_value);
+  return scratch_create<CountOnesMem>(streams, mem_ptr, allocate_gpu_memory, who, [&](CountOnesMem &m) {
+    m.core.init(streams, p, kBitCountPop, num_blocks, counter_num_blocks, g_scratch_batch, false, bit_value == One, who);
+  });
+}
+void hip_integer_count_ones_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *output_ct,
+                                     CudaRadixCiphertextFFI const *input_ct, int8_t *mem_ptr, void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "count_ones";
+  bit_count_call(streams, scratch_use<CountOnesMem>(mem_ptr, who)->core, output_ct, input_ct, bsks, ksks, who);
+}
+void hip_cleanup_integer_count_ones_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<CountOnesMem>(streams, mem_ptr_void, "cleanup count_ones");
+}
+
+// bootstraps / rounds of one call on one integer of num_blocks blocks (a batch issues the bootstraps per integer, in the same
+// rounds).  kind: 0 a run of leading / trailing bits, 1 ilog2, 2 count_ones / count_zeros.  A function of the four arguments
+// alone: the scan's closed count, the plan of the column sums for these degrees, the carry propagation over the counter
+// blocks.  Every call checks the bootstraps against the rounds it issued.
+uint64_t hip_integer_bit_count_pbs_count(uint32_t kind, uint32_t num_blocks, uint32_t message_modulus, uint32_t carry_modulus) {
+  HX_PANIC_IF_FALSE(kind <= kBitCountPop && num_blocks >= 1, "hip_integer_bit_count_pbs_count: kind %u, %u blocks", kind, num_blocks);
+  BitCountCore::check_base(message_modulus, carry_modulus, "hip_integer_bit_count_pbs_count");
+  return BitCountCore::pbs_count(kind, num_blocks, message_modulus, carry_modulus);
+}
+uint32_t hip_integer_bit_count_rounds(uint32_t kind, uint32_t num_blocks, uint32_t message_modulus, uint32_t carry_modulus) {
+  HX_PANIC_IF_FALSE(kind <= kBitCountPop && num_blocks >= 1, "hip_integer_bit_count_rounds: kind %u, %u blocks", kind, num_blocks);
+  BitCountCore::check_base(message_modulus, carry_modulus, "hip_integer_bit_count_rounds");
+  return BitCountCore::round_count(kind, num_blocks, message_modulus, carry_modulus);
+}
+
+// lwe_pair_pack_kernel alone on caller-supplied rows (tests, tools/bench_bit_count.py): batch integers x_stride rows apart
+// in x, rows first .. first + rows - 1 of each; out receives ceil(rows / step) dense rows per integer
+void hip_test_pair_pack_async(void *stream, uint32_t gpu_index, void *out, void const *x, uint64_t s0, uint64_t s1,
+                              uint32_t words, uint32_t batch, uint32_t x_stride, uint32_t first, uint32_t rows, uint32_t step,
+                              int delta) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  launch_pair_pack((hipStream_t)stream, PairPack{(uint64_t *)out, (const uint64_t *)x, s0, s1, words, x_stride, first, rows, step, delta, 0},
+                   batch);
+}
+
+// the same rows for s0 = 1, step = 1, first = 0, x_stride = rows composed from the primitives the layer had before the kernel,
+// as the reference composes a Hillis-Steele step (tools/bench_bit_count.py times one against the other): per integer a copy of
+// the rows that have a partner and a memset of those that have none, then one axpy that packs.  tmp: batch rows rows.
+void hip_test_pair_pack_baseline_async(void *stream, uint32_t gpu_index, void *out, void const *x, void *tmp, uint64_t s1,
+                                       uint32_t words, uint32_t batch, uint32_t rows, int delta) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  const uint32_t d = (uint32_t)(delta < 0 ? -delta : delta);
+  HX_PANIC_IF_FALSE(out && x && tmp && words && batch && delta != 0 && d < rows, "hip_test_pair_pack_baseline: null pointer or distance");
+  const hipStream_t st = (hipStream_t)stream;
+  const size_t bw = (size_t)words * sizeof(uint64_t);
+  for (uint32_t c = 0; c < batch; ++c) {
+    const uint64_t *src = (const uint64_t *)x + (size_t)c * rows * words;
+    uint64_t *dst = (uint64_t *)tmp + (size_t)c * rows * words;
+    // partner of row i is row i + delta
+    if (delta > 0) {
+      HX_CHECK(hipMemcpyAsync(dst, src + (size_t)d * words, (rows - d) * bw, hipMemcpyDeviceToDevice, st));
+      HX_CHECK(hipMemsetAsync(dst + (size_t)(rows - d) * words, 0, d * bw, st));
+    } else {
+      HX_CHECK(hipMemsetAsync(dst, 0, d * bw, st));
+      HX_CHECK(hipMemcpyAsync(dst + (size_t)d * words, src, (rows - d) * bw, hipMemcpyDeviceToDevice, st));
+    }
+  }
+  axpy(st, (uint64_t *)out, nullptr, (const uint64_t *)tmp, nullptr, s1, (const uint64_t *)x, nullptr, words, batch * rows);
 }
 
 // number of PBS one carry propagation / one multiplication of `num_blocks` blocks issues (for benches)

@@ -299,6 +299,20 @@ SIGNATURES = {
     "hip_integer_div_rem_pbs_count": (_u64, [_b, _u32, _u32, _u32]),
     "hip_test_divrem_sum_async": (None, [_v, _u32, _u32, _u32, _u32, _v, _v, _v, _v, _v, _v, _v]),
     "hip_test_divrem_iteration_baseline_async": (None, [_v] + [_u32] + [_v] * 18 + [_u32] * 5 + [_u64, _u32]),
+    # bit counts: runs of leading / trailing bits, ilog2, popcounts
+    "hip_scratch_integer_count_of_consecutive_bits_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_count_of_consecutive_bits_64_async": (None, [_S, _R, _R, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_count_of_consecutive_bits_64": (None, [_S, _i8pp]),
+    "hip_scratch_integer_ilog2_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_ilog2_64_async": (None, [_S, _R, _R, _R, _R, _R, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_ilog2_64": (None, [_S, _i8pp]),
+    "hip_scratch_integer_count_ones_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _u32, _u32, _u32, _b, _u32]),
+    "hip_integer_count_ones_64_async": (None, [_S, _R, _R, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_count_ones_64": (None, [_S, _i8pp]),
+    "hip_integer_bit_count_pbs_count": (_u64, [_u32, _u32, _u32, _u32]),
+    "hip_integer_bit_count_rounds": (_u32, [_u32, _u32, _u32, _u32]),
+    "hip_test_pair_pack_async": (None, [_v, _u32, _v, _v, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, C.c_int]),
+    "hip_test_pair_pack_baseline_async": (None, [_v, _u32, _v, _v, _v, _u64, _u32, _u32, _u32, C.c_int]),
     # 128-bit PBS and noise squashing
     "hip_convert_lwe_programmable_bootstrap_key_128_async": (None, [_v, _u32, _v, _v, _u32, _u32, _u32, _u32]),
     "hip_scratch_programmable_bootstrap_128_async": (_u64, [_v, _u32, _i8pp, _u32, _u32, _u32, _u32, _u32, _b, _u32]),

@@ -417,6 +417,137 @@ class CudaServerKey:
         lib.hip_integer_abs_inplace_64_async(s, C.byref(ct._ffi()), mem, True, bsks, ksks)
         lib.hip_cleanup_integer_abs_inplace_64(s, C.byref(mem))
 
+    # ---- bit counts (integer/gpu/server_key/radix/ilog2.rs; count_ones / count_zeros: radix_parallel/count_zeros_ones.rs)
+    BIT_COUNT_RUNS, BIT_COUNT_ILOG2, BIT_COUNT_POP = 0, 1, 2      # `kind` of hip_integer_bit_count_pbs_count
+
+    def counter_num_blocks(self, num_blocks, ilog2=False):
+        """blocks of the result: ceil((floor(log2 B) + 1) / b) for a run or a popcount over B = b * num_blocks bits
+        (ilog2.rs:32-33), ceil((floor(log2(B - 1)) + 2) / b) for ilog2 (ilog2.rs:166-167)"""
+        b = self.message_modulus.bit_length() - 1
+        B = b * num_blocks
+        need = ((B - 1).bit_length() - 1 if B > 1 else 0) + 2 if ilog2 else B.bit_length()
+        return -(-need // b)
+
+    def _bit_count(self, kind, ct, streams, scratch, launch, return_pbs_count):
+        """scratch -> launch -> cleanup of one bit-count entry point, sized for ct's batch; out of place"""
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        nc = self.counter_num_blocks(ct.num_blocks, ilog2=kind == self.BIT_COUNT_ILOG2)
+        out = CudaUnsignedRadixCiphertext(CudaVec(ct.num_integers * nc * (ct.lwe_dimension + 1), streams), ct.num_integers, nc,
+                                          ct.lwe_dimension)
+        mem = C.c_void_p()
+        lib = _lib()
+        name = ("count_of_consecutive_bits", "ilog2", "count_ones")[kind]
+        lib.hip_integer_scratch_batch(ct.num_integers)
+        scratch(lib, s, C.byref(mem), nc)
+        lib.hip_integer_scratch_batch(1)
+        launch(lib, s, out, mem, bsks, ksks)
+        getattr(lib, f"hip_cleanup_integer_{name}_64")(s, C.byref(mem))
+        if not return_pbs_count:
+            return out
+        pbs = int(lib.hip_integer_bit_count_pbs_count(kind, ct.num_blocks, self.message_modulus, self.carry_modulus))
+        return out, pbs * ct.num_integers
+
+    def _unchecked_run(self, ct, streams, leading, ones, return_pbs_count=False):
+        return self._bit_count(
+            self.BIT_COUNT_RUNS, ct, streams,
+            lambda lib, s, mem, nc: lib.hip_scratch_integer_count_of_consecutive_bits_64_async(
+                s, mem, self._bsk_params(), self._ksk_params(), ct.num_blocks, nc, self.message_modulus, self.carry_modulus,
+                1 if leading else 0, 1 if ones else 0, True, self._noise_reduction()),
+            lambda lib, s, out, mem, bsks, ksks: lib.hip_integer_count_of_consecutive_bits_64_async(
+                s, C.byref(out._ffi()), C.byref(ct._ffi()), mem, bsks, ksks),
+            return_pbs_count)
+
+    def unchecked_leading_zeros(self, ct, streams, return_pbs_count=False):
+        """the number of consecutive zeros from the most significant bit, every integer of the batch, as an unsigned integer
+        of counter_num_blocks blocks (ilog2.rs unchecked_leading_zeros); the operand's blocks must be clean"""
+        return self._unchecked_run(ct, streams, True, False, return_pbs_count)
+
+    def unchecked_leading_ones(self, ct, streams, return_pbs_count=False):
+        return self._unchecked_run(ct, streams, True, True, return_pbs_count)
+
+    def unchecked_trailing_zeros(self, ct, streams, return_pbs_count=False):
+        return self._unchecked_run(ct, streams, False, False, return_pbs_count)
+
+    def unchecked_trailing_ones(self, ct, streams, return_pbs_count=False):
+        return self._unchecked_run(ct, streams, False, True, return_pbs_count)
+
+    def unchecked_ilog2(self, ct, streams, return_pbs_count=False):
+        """floor(log2(ct)) as an unsigned integer of counter_num_blocks(ilog2=True) blocks, in the rounds of leading_zeros
+        (ilog2.rs unchecked_ilog2); ilog2(0) is all ones.  The three trivial operands of the reference's parameter list are
+        handed over with the reference's block counts; the backend does not read them."""
+        w = ct.lwe_dimension + 1
+
+        def launch(lib, s, out, mem, bsks, ksks):
+            nc = out.num_blocks
+            triv = [CudaUnsignedRadixCiphertext(CudaVec(n * w, streams), 1, n, ct.lwe_dimension) for n in (nc, nc, 1)]
+            lib.hip_integer_ilog2_64_async(s, C.byref(out._ffi()), C.byref(ct._ffi()), *(C.byref(t._ffi()) for t in triv), mem,
+                                           bsks, ksks)
+            streams.synchronize()          # (the trivial operands go out of scope)
+
+        return self._bit_count(
+            self.BIT_COUNT_ILOG2, ct, streams,
+            lambda lib, s, mem, nc: lib.hip_scratch_integer_ilog2_64_async(
+                s, mem, self._bsk_params(), self._ksk_params(), self.message_modulus, self.carry_modulus, ct.num_blocks, nc,
+                ct.num_blocks * (self.message_modulus.bit_length() - 1), True, self._noise_reduction()),
+            launch, return_pbs_count)
+
+    def _unchecked_popcount(self, ct, streams, ones, return_pbs_count=False):
+        return self._bit_count(
+            self.BIT_COUNT_POP, ct, streams,
+            lambda lib, s, mem, nc: lib.hip_scratch_integer_count_ones_64_async(
+                s, mem, self._bsk_params(), self._ksk_params(), ct.num_blocks, nc, self.message_modulus, self.carry_modulus,
+                1 if ones else 0, True, self._noise_reduction()),
+            lambda lib, s, out, mem, bsks, ksks: lib.hip_integer_count_ones_64_async(
+                s, C.byref(out._ffi()), C.byref(ct._ffi()), mem, bsks, ksks),
+            return_pbs_count)
+
+    def unchecked_count_ones(self, ct, streams, return_pbs_count=False):
+        """the number of set bits, one round over the pairs of blocks, a sum and a carry propagation
+        (count_zeros_ones.rs unchecked_count_ones_parallelized)"""
+        return self._unchecked_popcount(ct, streams, True, return_pbs_count)
+
+    def unchecked_count_zeros(self, ct, streams, return_pbs_count=False):
+        return self._unchecked_popcount(ct, streams, False, return_pbs_count)
+
+    def _clean(self, ct, streams):
+        """ct itself when every block is clean, else a propagated duplicate (ONE integer: full_propagate_assign)"""
+        if int(ct.degrees.max(initial=0)) <= self.message_modulus - 1:
+            return ct
+        dup = ct.duplicate(streams)
+        dup._info[0][:], dup._info[1][:] = ct._info[0], ct._info[1]
+        self.full_propagate_assign(dup, streams)
+        return dup
+
+    def leading_zeros(self, ct, streams, return_pbs_count=False):
+        """unchecked_leading_zeros on the operand, propagated first on a duplicate when a block is not clean; the bootstraps
+        reported are the count's alone"""
+        return self.unchecked_leading_zeros(self._clean(ct, streams), streams, return_pbs_count)
+
+    def leading_ones(self, ct, streams, return_pbs_count=False):
+        return self.unchecked_leading_ones(self._clean(ct, streams), streams, return_pbs_count)
+
+    def trailing_zeros(self, ct, streams, return_pbs_count=False):
+        return self.unchecked_trailing_zeros(self._clean(ct, streams), streams, return_pbs_count)
+
+    def trailing_ones(self, ct, streams, return_pbs_count=False):
+        return self.unchecked_trailing_ones(self._clean(ct, streams), streams, return_pbs_count)
+
+    def ilog2(self, ct, streams, return_pbs_count=False):
+        return self.unchecked_ilog2(self._clean(ct, streams), streams, return_pbs_count)
+
+    def count_ones(self, ct, streams, return_pbs_count=False):
+        return self.unchecked_count_ones(self._clean(ct, streams), streams, return_pbs_count)
+
+    def count_zeros(self, ct, streams, return_pbs_count=False):
+        return self.unchecked_count_zeros(self._clean(ct, streams), streams, return_pbs_count)
+
+    def checked_ilog2(self, ct, streams):
+        """(ilog2(ct), ct > 0) of ONE unsigned integer (ilog2.rs checked_ilog2): the flag is scalar_compare(ct, 0, "gt").
+        Unsigned only: a signed operand needs `ct > 0` as a signed comparison, which is not wired."""
+        clean = self._clean(ct, streams)
+        return self.unchecked_ilog2(clean, streams), self.scalar_compare(clean, 0, "gt", streams)
+
     # ---- Trivium transciphering (integer/gpu/server_key/radix/trivium.rs)
     def _trivium_call(self, kind, num_inputs, streams, launch, num_steps=0, window=None):
         """scratch -> launch -> cleanup of hip_trivium_{init,step}; returns the published bootstrap count of the call"""
