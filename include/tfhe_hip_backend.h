@@ -1047,6 +1047,95 @@ void hip_test_trivium_batch_baseline_async(void *stream, uint32_t gpu_index, voi
                                            void const *r1, void *in2, void const *r2, void *keystream, void *tmp,
                                            uint32_t words, uint32_t inputs, uint64_t message_modulus);
 
+/* ------------------------------------------------------------------ AES-128 transciphering (extensions)
+ * cuda/include/aes/aes.h under hip_ names with the reference's parameter lists, on the shared scratch protocol; the
+ * reference-named symbols remain link stubs (AES-256 too).  key / iv: 128 one-bit blocks, block i holds bit 127 - i (most
+ * significant first); round_keys / expanded_keys: 11 x 128 blocks in the same order, round key r at blocks 128 r ..;
+ * output: 128 * num_aes_inputs blocks, input n at blocks 128 n .. is AES_k((iv + start_counter + n) mod 2^128);
+ * counter_bits_le_all_blocks: HOST array, entry 128 n + i is bit i (little endian) of start_counter + n.  Outputs have degree 1
+ * and noise level 1.  sbox_parallelism (1, 2, 4, 8 or 16): state bytes per S-box pass; it bounds the scratch and changes the
+ * number of rounds, never the result.  Classic and multi-bit keys; moduli with msg * carry >= 16 and
+ * (msg * carry - 1) / (msg - 1) >= 5, the others are refused.  DESIGN.md 6m has the schedule.
+ * hip_integer_aes_pbs_count / hip_integer_aes_rounds: bootstraps and round-driver rounds of one call on that scratch; every
+ * call checks both against what it issued. */
+uint64_t hip_scratch_integer_aes_ctr_encrypt_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+    uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_aes_inputs,
+    uint32_t sbox_parallelism);
+void hip_integer_aes_ctr_encrypt_64_async(
+    CudaStreamsFFI streams, CudaRadixCiphertextFFI *output,
+    CudaRadixCiphertextFFI const *iv, CudaRadixCiphertextFFI const *round_keys,
+    const uint64_t *counter_bits_le_all_blocks, uint32_t num_aes_inputs,
+    int8_t *mem_ptr, void *const *bsks, void *const *ksks);
+void hip_cleanup_integer_aes_ctr_encrypt_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+uint64_t hip_scratch_integer_key_expansion_64_async(
+    CudaStreamsFFI streams, int8_t **mem_ptr,
+    CudaLweBootstrapKeyParamsFFI bsk_params,
+    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+    uint32_t carry_modulus, bool allocate_gpu_memory,
+    enum PBS_MS_REDUCTION_T noise_reduction_type);
+void hip_integer_key_expansion_64_async(CudaStreamsFFI streams,
+                                        CudaRadixCiphertextFFI *expanded_keys,
+                                        CudaRadixCiphertextFFI const *key,
+                                        int8_t *mem_ptr, void *const *bsks,
+                                        void *const *ksks);
+void hip_cleanup_integer_key_expansion_64(CudaStreamsFFI streams, int8_t **mem_ptr_void);
+uint64_t hip_integer_aes_pbs_count(int8_t *mem_ptr);
+uint64_t hip_integer_aes_rounds(int8_t *mem_ptr);
+/* tests, benches: the gate-sum kernel alone on a caller-given program.
+ * out[(g lanes + l) inputs + n] = sum over the terms t of group g of scalar_t * src_t[row0_t + lane_t(l) * lane_stride_t + (n,
+ * or 0 for a broadcast term)] on u64 words, rows of `words` words, plus (constant_g + the group's clear terms) * delta on the
+ * last word.  base: 0 wires, 1 caller_a, 2 caller_b, 3 clear (entry n * clear_stride + row0 of `clear`, times the scalar).
+ * flags: 1 broadcast over inputs, 2 lane of the state: lane_t(l) = map(lane0 + l) with map = kind | parameter << 2, kind
+ * 0 identity, 1 permutation `parameter` of `maps` (16 entries each), 2 offset `parameter` within the column of four lanes;
+ * without flag 2 lane_t(l) = l.  Device pointers: out, wires, caller_a, caller_b, clear.  HOST arrays: group_* one entry per
+ * group (the groups' terms follow each other in the term_* arrays), maps.  rows_*: the rows the three bases hold.  Refused: an
+ * empty program, a lane map that leaves the state_lanes lanes or the base, an output that overlaps a row read. */
+void hip_test_gate_sum_async(void *stream, uint32_t gpu_index, void *out, void const *wires, void const *caller_a,
+                             void const *caller_b, void const *clear, uint32_t words, uint32_t inputs, uint32_t lanes,
+                             uint32_t lane0, uint32_t state_lanes, uint32_t clear_stride, uint64_t delta, uint32_t groups,
+                             uint64_t const *group_constant, uint32_t const *group_terms, uint64_t const *term_scalar,
+                             uint32_t const *term_row0, uint32_t const *term_lane_stride, uint32_t const *term_map,
+                             uint32_t const *term_base, uint32_t const *term_flags, uint32_t num_maps, uint32_t const *maps,
+                             uint64_t rows_wires, uint64_t rows_a, uint64_t rows_b);
+/* tests: one S-box pass on a cipher scratch's first sbox_parallelism lanes.  in / out: device rows [wire j][lane][input], j = 0
+ * the most significant bit of a byte, sbox_parallelism * num_aes_inputs rows per wire. */
+void hip_test_aes_sbox_async(CudaStreamsFFI streams, void *out, void const *in, int8_t *mem_ptr, void *const *bsks,
+                             void *const *ksks);
+/* tests: parts of a call on a cipher scratch.  r0 = 0: the counter addition (it folds round key 0 in) from iv, round_keys and
+ * the counter bits; r0 >= 1: the state is loaded from `state`.  Then the cipher rounds max(r0, 1) .. r1 (r0 <= r1 <= 10).
+ * state: device rows [wire j][byte lane][input], 16 * num_aes_inputs rows per wire; it receives the state after the last
+ * round run, unless that is round 10, which writes `output` in the caller's layout. */
+void hip_test_aes_rounds_async(CudaStreamsFFI streams, void *state, CudaRadixCiphertextFFI *output,
+                               CudaRadixCiphertextFFI const *iv, CudaRadixCiphertextFFI const *round_keys,
+                               const uint64_t *counter_bits_le_all_blocks, uint32_t r0, uint32_t r1, int8_t *mem_ptr,
+                               void *const *bsks, void *const *ksks);
+/* tests: the scheduled program of an AES scratch as u64 words in HOST memory; returns the words it takes and writes them when
+ * `capacity` holds them.  Every item is one word:
+ *   header   0x41455350, message modulus, carry modulus, inputs, sbox_parallelism, key schedule (0 / 1), cipher rounds,
+ *            tables T, entries per table E = msg * carry, permutations M, segments G, rows of the wires,
+ *            first rows of the state wires x[0 .. 7] (0 for a key schedule), first rows of the S-box outputs sb[0 .. 7]
+ *   tables   T * E entries, then M * 16 permutation entries
+ *   segment  lanes, passes, rounds; per round: rows, to_caller (0: the round writes wires, 1: the caller's output);
+ *            per row: table, constant (units of delta), terms, destination row0, lane_stride, in_stride, state_lane
+ *            (row = row0 + (state_lane ? pass * lanes + l : l) * lane_stride + n * in_stride);
+ *            per term: base, row0, lane_stride, map, flags, scalar (as for hip_test_gate_sum_async)
+ * Segments of a cipher scratch: counter addition, S-box (run `passes` times per cipher round), linear layer of a middle
+ * round (caller_a: that round's key), of the last round; of a key schedule: S-box, then the linear layer of steps 1 .. 10
+ * (caller_a: the previous round key). */
+uint64_t hip_test_aes_program(int8_t *mem_ptr, uint64_t *words, uint64_t capacity);
+/* benches: the gate-sum launches of one middle cipher round of a cipher scratch (every S-box pass, then the linear layer with
+ * the round key read from the 128 device rows of `round_key`), without the bootstraps between them. */
+void hip_test_aes_round_launches_async(CudaStreamsFFI streams, void const *round_key, int8_t *mem_ptr);
+/* benches: the data movement of one middle cipher round composed from device copies and pairwise additions in the reference's
+ * order (cuda/src/aes/aes.cuh:882-974), without the bootstraps.  state: 128 * inputs rows [block][input], key: 128 rows,
+ * tmp: 512 * inputs rows. */
+void hip_test_aes_round_baseline_async(void *stream, uint32_t gpu_index, void *state, void const *key, void *tmp,
+                                       uint32_t words, uint32_t inputs);
+
 /* ------------------------------------------------------------------ division with remainder, absolute value (extensions)
  * cuda/include/integer/integer.h:465-499 under hip_ names with the reference's parameter lists, on the shared scratch
  * protocol; the reference-named symbols remain link stubs.  A call takes a batch of integers ([integer][block], num_blocks

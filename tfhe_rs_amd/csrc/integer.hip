@@ -2188,6 +2188,7 @@ struct OprfMem : ScratchHeader {
 #include "radix_trivium.h"  // TriviumMem and the tap kernel, on the round driver and the owners above
 #include "radix_divrem.h"   // DivRemMem, AbsMem and the stage kernel, on the round driver and the carry propagation
 #include "radix_bitcount.h" // the bit-count scratches and the pair-pack kernel, on the round driver, the sums and the propagation
+#include "radix_aes.h"      // AesMem, the gate scheduler and the gate-sum kernel, on the round driver
 
 using namespace tfhe_hip;
 using namespace tfhe_hip::radix;
@@ -3484,6 +3485,250 @@ void hip_test_trivium_batch_baseline_async(void *stream, uint32_t gpu_index, voi
   uint64_t *const regs[3] = {(uint64_t *)a, (uint64_t *)b, (uint64_t *)c};
   trivium_batch_baseline((hipStream_t)stream, regs, (uint64_t *)in1, (const uint64_t *)r1, (uint64_t *)in2,
                          (const uint64_t *)r2, (uint64_t *)keystream, (uint64_t *)tmp, words, inputs, message_modulus);
+}
+
+// ---- AES-128 transciphering (radix_aes.h; hip_ names with the parameter lists of cuda/include/aes/aes.h: the reference-named
+// symbols stay link stubs).  key / iv: 128 one-bit blocks, block i holds bit 127 - i; round keys: 11 x 128 blocks in the same
+// order; output: 128 blocks per input, input n is AES_k((iv + start_counter + n) mod 2^128);
+// counter_bits_le_all_blocks[128 n + i]: bit i (little endian) of start_counter + n, a HOST array.
+namespace {
+uint64_t aes_scratch(CudaStreamsFFI streams, int8_t **mem_ptr, CudaLweBootstrapKeyParamsFFI bsk_params,
+                     CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus, uint32_t carry_modulus,
+                     bool allocate_gpu_memory, enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_aes_inputs,
+                     uint32_t sbox_parallelism, bool key_schedule) {
+  const char *who = key_schedule ? "key_expansion" : "aes_ctr_encrypt";
+  const Params p = make_params(bsk_params, ksk_params, message_modulus, carry_modulus, (uint32_t)noise_reduction_type);
+  return scratch_create<AesMem>(streams, mem_ptr, allocate_gpu_memory, who,
+                                [&](AesMem &m) { m.init(streams, p, num_aes_inputs, sbox_parallelism, key_schedule, who); });
+}
+// `blocks` one-bit blocks of the caller
+uint64_t *aes_rows(const CudaRadixCiphertextFFI *ct, uint32_t blocks, const AesMem &m, bool is_input, const char *who,
+                   const char *what) {
+  HX_PANIC_IF_FALSE(ct && ct->ptr, "%s: null pointer (%s)", who, what);
+  HX_PANIC_IF_FALSE(ct->lwe_dimension == m.drv.p.big_n, "%s: the blocks' lwe dimension should be %u", who, m.drv.p.big_n);
+  HX_PANIC_IF_FALSE(ct->num_radix_blocks == blocks, "%s: %s: %u blocks, not %u", who, what, ct->num_radix_blocks, blocks);
+  for (uint32_t i = 0; is_input && i < ct->num_radix_blocks; ++i) {
+    HX_PANIC_IF_FALSE(!ct->degrees || ct->degrees[i] <= 1, "%s: block %u of %s has degree %llu, a bit has at most 1", who, i,
+                      what, (unsigned long long)ct->degrees[i]);
+    HX_PANIC_IF_FALSE(!ct->noise_levels || ct->noise_levels[i] <= 1, "%s: block %u of %s has noise level %llu, at most 1",
+                      who, i, what, (unsigned long long)ct->noise_levels[i]);
+  }
+  return (uint64_t *)ct->ptr;
+}
+AesMem *aes_use(int8_t *mem_ptr, bool key_schedule, void *const *bsks, void *const *ksks, const char *who) {
+  auto *m = scratch_use<AesMem>(mem_ptr, who);
+  HX_PANIC_IF_FALSE(m->key_schedule == key_schedule, "%s: the scratch was created by the other aes scratch call", who);
+  HX_PANIC_IF_FALSE(bsks && ksks, "%s: null pointer", who);
+  return m;
+}
+}  // namespace
+
+uint64_t hip_scratch_integer_aes_ctr_encrypt_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                                      CudaLweBootstrapKeyParamsFFI bsk_params,
+                                                      CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+                                                      uint32_t carry_modulus, bool allocate_gpu_memory,
+                                                      enum PBS_MS_REDUCTION_T noise_reduction_type, uint32_t num_aes_inputs,
+                                                      uint32_t sbox_parallelism) {
+  return aes_scratch(streams, mem_ptr, bsk_params, ksk_params, message_modulus, carry_modulus, allocate_gpu_memory,
+                     noise_reduction_type, num_aes_inputs, sbox_parallelism, false);
+}
+
+void hip_integer_aes_ctr_encrypt_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *output,
+                                          CudaRadixCiphertextFFI const *iv, CudaRadixCiphertextFFI const *round_keys,
+                                          const uint64_t *counter_bits_le_all_blocks, uint32_t num_aes_inputs, int8_t *mem_ptr,
+                                          void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "aes_ctr_encrypt";
+  AesMem *m = aes_use(mem_ptr, false, bsks, ksks, who);
+  HX_PANIC_IF_FALSE(num_aes_inputs == m->inputs, "%s: %u inputs on a scratch created for %u", who, num_aes_inputs, m->inputs);
+  HX_PANIC_IF_FALSE(counter_bits_le_all_blocks != nullptr, "%s: null pointer (the counter bits)", who);
+  const uint64_t *v = aes_rows(iv, 128, *m, true, who, "the iv");
+  const uint64_t *k = aes_rows(round_keys, 128 * (m->cipher_rounds + 1), *m, true, who, "the round keys");
+  uint64_t *out = aes_rows(output, 128 * m->inputs, *m, false, who, "the output");
+  for (size_t i = 0; i < (size_t)128 * m->inputs; ++i)
+    HX_PANIC_IF_FALSE(counter_bits_le_all_blocks[i] <= 1, "%s: counter bit %zu is %llu", who, i,
+                      (unsigned long long)counter_bits_le_all_blocks[i]);
+  m->encrypt(streams, out, v, k, counter_bits_le_all_blocks, ksks, bsks);
+  set_block_info(output, 0, output->num_radix_blocks, 1, 1);
+}
+
+void hip_cleanup_integer_aes_ctr_encrypt_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<AesMem>(streams, mem_ptr_void, "cleanup aes_ctr_encrypt");
+}
+
+uint64_t hip_scratch_integer_key_expansion_64_async(CudaStreamsFFI streams, int8_t **mem_ptr,
+                                                    CudaLweBootstrapKeyParamsFFI bsk_params,
+                                                    CudaLweKeyswitchKeyParamsFFI ksk_params, uint32_t message_modulus,
+                                                    uint32_t carry_modulus, bool allocate_gpu_memory,
+                                                    enum PBS_MS_REDUCTION_T noise_reduction_type) {
+  return aes_scratch(streams, mem_ptr, bsk_params, ksk_params, message_modulus, carry_modulus, allocate_gpu_memory,
+                     noise_reduction_type, 1, 4, true);
+}
+
+void hip_integer_key_expansion_64_async(CudaStreamsFFI streams, CudaRadixCiphertextFFI *expanded_keys,
+                                        CudaRadixCiphertextFFI const *key, int8_t *mem_ptr, void *const *bsks,
+                                        void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "key_expansion";
+  AesMem *m = aes_use(mem_ptr, true, bsks, ksks, who);
+  const uint64_t *k = aes_rows(key, 32 * m->key_words, *m, true, who, "the key");
+  uint64_t *out = aes_rows(expanded_keys, 128 * (m->cipher_rounds + 1), *m, false, who, "the expanded keys");
+  m->expand_key(streams, out, k, ksks, bsks);
+  set_block_info(expanded_keys, 0, expanded_keys->num_radix_blocks, 1, 1);
+}
+
+void hip_cleanup_integer_key_expansion_64(CudaStreamsFFI streams, int8_t **mem_ptr_void) {
+  scratch_destroy<AesMem>(streams, mem_ptr_void, "cleanup key_expansion");
+}
+
+// bootstraps and round-driver rounds of one call on this scratch (closed formulas over the scheduled program: DESIGN.md 6m);
+// every call checks both against what it issued
+uint64_t hip_integer_aes_pbs_count(int8_t *mem_ptr) { return scratch_cast<AesMem>(mem_ptr, "hip_integer_aes_pbs_count")->pbs_count(); }
+uint64_t hip_integer_aes_rounds(int8_t *mem_ptr) { return scratch_cast<AesMem>(mem_ptr, "hip_integer_aes_rounds")->round_count(); }
+
+// lwe_gate_sum_kernel alone on a caller-given program (tests, tools/bench_aes.py).  Device pointers: out, wires, caller_a,
+// caller_b, clear (the last three may be null).  HOST arrays: group_constant / group_terms one entry per group (the terms of
+// the groups follow each other), term_* one entry per term, maps 16 entries per permutation.
+void hip_test_gate_sum_async(void *stream, uint32_t gpu_index, void *out, void const *wires, void const *caller_a,
+                             void const *caller_b, void const *clear, uint32_t words, uint32_t inputs, uint32_t lanes,
+                             uint32_t lane0, uint32_t state_lanes, uint32_t clear_stride, uint64_t delta, uint32_t groups,
+                             uint64_t const *group_constant, uint32_t const *group_terms, uint64_t const *term_scalar,
+                             uint32_t const *term_row0, uint32_t const *term_lane_stride, uint32_t const *term_map,
+                             uint32_t const *term_base, uint32_t const *term_flags, uint32_t num_maps, uint32_t const *maps,
+                             uint64_t rows_wires, uint64_t rows_a, uint64_t rows_b) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  const hipStream_t st = (hipStream_t)stream;
+  HX_PANIC_IF_FALSE(groups == 0 || (group_constant && group_terms), "hip_test_gate_sum: null array");
+  std::vector<GateGroup> hg;
+  std::vector<GateTerm> ht;
+  for (uint32_t g = 0; g < groups; ++g) {
+    hg.push_back(GateGroup{group_constant[g], (uint32_t)ht.size(), group_terms[g]});
+    for (uint32_t t = 0; t < group_terms[g]; ++t) {
+      const size_t i = ht.size();
+      HX_PANIC_IF_FALSE(term_scalar && term_row0 && term_lane_stride && term_map && term_base && term_flags && term_base[i] <= 3 &&
+                            term_flags[i] <= 3,
+                        "hip_test_gate_sum: null array, or base / flags of term %zu out of range", i);
+      ht.push_back(GateTerm{term_scalar[i], term_row0[i], term_lane_stride[i], term_map[i], term_base[i] | term_flags[i] << 2});
+    }
+  }
+  std::vector<uint32_t> hm(maps ? maps : nullptr, maps ? maps + (size_t)num_maps * kGateLanes : nullptr);
+  GateGroup *dg = nullptr;
+  GateTerm *dt = nullptr;
+  uint32_t *dm = nullptr;
+  DeviceBlocks own;
+  if (!hg.empty()) dg = own.upload(st, hg);
+  if (!ht.empty()) dt = own.upload(st, ht);
+  if (!hm.empty()) dm = own.upload(st, hm);
+  GateLaunch a{(uint64_t *)out, (const uint64_t *)wires, (const uint64_t *)caller_a, (const uint64_t *)caller_b,
+               (const uint64_t *)clear, dg, dt, dm, delta, words, inputs, lanes, lane0, clear_stride, groups};
+  GateHost h{hg.data(), ht.data(), hm.data(), num_maps, state_lanes,
+             {(size_t)rows_wires, (size_t)rows_a, (size_t)rows_b}};
+  launch_gate_sum(st, a, h);
+  own.release(st);
+}
+
+// one S-box pass on the lanes of the scratch's first pass: rows [wire j][lane][input] (j = 0 the most significant bit),
+// sbox_parallelism * num_aes_inputs rows per wire, in and out
+void hip_test_aes_sbox_async(CudaStreamsFFI streams, void *out, void const *in, int8_t *mem_ptr, void *const *bsks,
+                             void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "hip_test_aes_sbox";
+  AesMem *m = aes_use(mem_ptr, false, bsks, ksks, who);
+  HX_PANIC_IF_FALSE(out && in, "%s: null pointer", who);
+  m->move_wires(S0(streams), m->x_wire, (uint64_t *)in, m->parallelism, true);
+  m->run(streams, m->segs[AesMem::kSbox], nullptr, 0, nullptr, 0, nullptr, ksks, bsks, 0, 1);
+  m->move_wires(S0(streams), m->sb_wire, (uint64_t *)out, m->parallelism, false);
+}
+
+// parts of a call.  r0 = 0: the counter addition with round key 0 (iv, round_keys and the HOST counter bits as for the call)
+// into the state; otherwise the state is loaded from `state`.  Then the cipher rounds max(r0, 1) .. r1 (none when r1 = 0).
+// state: rows [wire j][byte lane][input], 16 * num_aes_inputs rows per wire; it receives the state after the last round run,
+// unless that is the cipher's last round, which writes `output` (the caller's layout).
+void hip_test_aes_rounds_async(CudaStreamsFFI streams, void *state, CudaRadixCiphertextFFI *output,
+                               CudaRadixCiphertextFFI const *iv, CudaRadixCiphertextFFI const *round_keys,
+                               const uint64_t *counter_bits_le_all_blocks, uint32_t r0, uint32_t r1, int8_t *mem_ptr,
+                               void *const *bsks, void *const *ksks) {
+  first_gpu(streams);
+  const char *who = "hip_test_aes_rounds";
+  AesMem *m = aes_use(mem_ptr, false, bsks, ksks, who);
+  HX_PANIC_IF_FALSE(state && r0 <= r1 && r1 <= m->cipher_rounds, "%s: null pointer, or rounds %u .. %u", who, r0, r1);
+  const uint64_t *k = aes_rows(round_keys, 128 * (m->cipher_rounds + 1), *m, true, who, "the round keys");
+  uint64_t *out = r1 == m->cipher_rounds ? aes_rows(output, 128 * m->inputs, *m, false, who, "the output") : nullptr;
+  if (r0 == 0) {
+    HX_PANIC_IF_FALSE(counter_bits_le_all_blocks != nullptr, "%s: null pointer (the counter bits)", who);
+    m->counter_addition(streams, aes_rows(iv, 128, *m, true, who, "the iv"), k, counter_bits_le_all_blocks, ksks, bsks);
+  } else {
+    m->move_wires(S0(streams), m->x_wire, (uint64_t *)state, kGateLanes, true);
+  }
+  if (r1 >= 1) m->cipher(streams, std::max(r0, 1u), r1, k, out, ksks, bsks);
+  if (out)
+    set_block_info(output, 0, output->num_radix_blocks, 1, 1);
+  else
+    m->move_wires(S0(streams), m->x_wire, (uint64_t *)state, kGateLanes, false);
+}
+
+// The scheduled program of a scratch as u64 words in HOST memory; returns the words it takes and writes them when
+// `capacity` holds them.  Format (every item one word):
+//   header   magic "AESP", message modulus, carry modulus, inputs, sbox_parallelism, key_schedule (0 / 1), cipher rounds,
+//            tables T, entries per table E = msg * carry, permutations M, segments G, rows of the wires,
+//            first row of the state wires x[0 .. 7] (0 for a key schedule), first row of the S-box outputs sb[0 .. 7]
+//   tables   T * E entries, then M * 16 permutation entries
+//   segment  lanes, passes, rounds R; then per round: rows, to_caller (0 / 1); then per row: table, constant, terms,
+//            destination (row0, lane_stride, in_stride, state_lane); then per term: base (0 wires, 1 caller a, 2 caller b,
+//            3 clear), row0, lane_stride, map (kind | parameter << 2; kinds 0 identity, 1 permutation, 2 column offset),
+//            flags (1 broadcast over inputs, 2 lane of the state), scalar
+// Segments of a cipher scratch: counter addition, S-box, middle round's linear layer, last round's; of a key schedule: S-box,
+// then the linear layer of steps 1 .. rounds.
+uint64_t hip_test_aes_program(int8_t *mem_ptr, uint64_t *words, uint64_t capacity) {
+  const AesMem *m = scratch_cast<AesMem>(mem_ptr, "hip_test_aes_program");
+  std::vector<uint64_t> o;
+  const Params &p = m->drv.p;
+  const uint64_t E = (uint64_t)p.msg * p.carry;
+  for (uint64_t x : {(uint64_t)0x41455350, (uint64_t)p.msg, (uint64_t)p.carry, (uint64_t)m->inputs, (uint64_t)m->parallelism,
+                     (uint64_t)m->key_schedule, (uint64_t)m->cipher_rounds, (uint64_t)(m->h_tables.size() / E), E,
+                     (uint64_t)(m->h_maps.size() / kGateLanes), (uint64_t)m->segs.size(), (uint64_t)m->sch.wire_rows})
+    o.push_back(x);
+  for (uint32_t j = 0; j < 8; ++j) o.push_back(m->key_schedule ? 0 : m->x_wire[j].row0);
+  for (uint32_t j = 0; j < 8; ++j) o.push_back(m->sb_wire[j].row0);
+  o.insert(o.end(), m->h_tables.begin(), m->h_tables.end());
+  o.insert(o.end(), m->h_maps.begin(), m->h_maps.end());
+  for (const GateSegment &sg : m->segs) {
+    uint64_t rounds = 0;
+    for (auto &r : sg.rounds) rounds += !r.empty();
+    o.insert(o.end(), {(uint64_t)sg.lanes, (uint64_t)sg.passes, rounds});
+    for (auto &r : sg.rounds) {
+      if (r.empty()) continue;
+      o.insert(o.end(), {(uint64_t)r.size(), (uint64_t)r[0].dst.caller});
+      for (const GateRow &row : r) {
+        o.insert(o.end(), {(uint64_t)row.table, row.constant, (uint64_t)row.terms.size(), (uint64_t)row.dst.row0,
+                           (uint64_t)row.dst.lane_stride, (uint64_t)row.dst.in_stride, (uint64_t)row.dst.state_lane});
+        for (const GateTerm &t : row.terms)
+          o.insert(o.end(), {(uint64_t)(t.base_flags & 3), (uint64_t)t.row0, (uint64_t)t.lane_stride, (uint64_t)t.map,
+                             (uint64_t)(t.base_flags >> 2), t.scalar});
+      }
+    }
+  }
+  if (words && capacity >= o.size()) std::copy(o.begin(), o.end(), words);
+  return o.size();
+}
+
+// benches: the gate-sum launches of one middle cipher round of a cipher scratch (every S-box pass, then the linear layer with
+// the round key read from `round_key`, 128 rows), without the bootstraps between them
+void hip_test_aes_round_launches_async(CudaStreamsFFI streams, void const *round_key, int8_t *mem_ptr) {
+  first_gpu(streams);
+  auto *m = scratch_use<AesMem>(mem_ptr, "hip_test_aes_round_launches");
+  HX_PANIC_IF_FALSE(!m->key_schedule && round_key, "hip_test_aes_round_launches: null pointer, or a key-schedule scratch");
+  m->run(streams, m->segs[AesMem::kSbox], nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, ~0u, true);
+  m->run(streams, m->segs[AesMem::kLin], (const uint64_t *)round_key, 128, nullptr, 0, nullptr, nullptr, nullptr, 0, ~0u, true);
+}
+
+// the data movement of one middle cipher round composed from the older primitives in the reference's order (radix_aes.h,
+// aes_round_baseline).  state: 128 * inputs rows [block][input], key: 128 rows, tmp: 512 * inputs rows
+void hip_test_aes_round_baseline_async(void *stream, uint32_t gpu_index, void *state, void const *key, void *tmp,
+                                       uint32_t words, uint32_t inputs) {
+  HX_CHECK(hipSetDevice((int)gpu_index));
+  HX_PANIC_IF_FALSE(state && key && tmp && words >= 1 && inputs >= 1, "hip_test_aes_round_baseline: null pointer or empty rows");
+  aes_round_baseline((hipStream_t)stream, (uint64_t *)state, (const uint64_t *)key, (uint64_t *)tmp, words, inputs);
 }
 
 // ---- integer.h:465-499: division with remainder and absolute value (radix_divrem.h; hip_ names with the reference's

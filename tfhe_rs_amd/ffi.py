@@ -289,6 +289,22 @@ SIGNATURES = {
     "hip_test_trivium_set_window": (None, [_v, _u32]),
     "hip_test_tap_sum_async": (None, [_v, _u32, _u32, _u32, _u32, _v, _v, _v, _v, _v, _v, _v]),
     "hip_test_trivium_batch_baseline_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _v, _v, _v, _v, _u32, _u32, _u64]),
+    # AES-128 transciphering
+    "hip_scratch_integer_aes_ctr_encrypt_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _b, _u32, _u32, _u32]),
+    "hip_integer_aes_ctr_encrypt_64_async": (None, [_S, _R, _R, _R, _v, _u32, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_aes_ctr_encrypt_64": (None, [_S, _i8pp]),
+    "hip_scratch_integer_key_expansion_64_async": (_u64, [_S, _i8pp, _BK, _KK, _u32, _u32, _b, _u32]),
+    "hip_integer_key_expansion_64_async": (None, [_S, _R, _R, _v, _i8pp, _i8pp]),
+    "hip_cleanup_integer_key_expansion_64": (None, [_S, _i8pp]),
+    "hip_integer_aes_pbs_count": (_u64, [_v]),
+    "hip_integer_aes_rounds": (_u64, [_v]),
+    "hip_test_gate_sum_async": (None, [_v, _u32, _v, _v, _v, _v, _v, _u32, _u32, _u32, _u32, _u32, _u32, _u64, _u32, _v, _v, _v,
+                                       _v, _v, _v, _v, _v, _u32, _v, _u64, _u64, _u64]),
+    "hip_test_aes_sbox_async": (None, [_S, _v, _v, _v, _i8pp, _i8pp]),
+    "hip_test_aes_rounds_async": (None, [_S, _v, _R, _R, _R, _v, _u32, _u32, _v, _i8pp, _i8pp]),
+    "hip_test_aes_program": (_u64, [_v, _v, _u64]),
+    "hip_test_aes_round_launches_async": (None, [_S, _v, _v]),
+    "hip_test_aes_round_baseline_async": (None, [_v, _u32, _v, _v, _v, _u32, _u32]),
     # division with remainder, absolute value
     "hip_scratch_integer_div_rem_64_async": (_u64, [_S, _b, _i8pp, _BK, _KK, _u32, _u32, _u32, _b, _u32]),
     "hip_integer_div_rem_64_async": (None, [_S, _R, _R, _R, _R, _b, _v, _i8pp, _i8pp]),

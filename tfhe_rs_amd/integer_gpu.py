@@ -25,6 +25,7 @@ KS_TYPE_BIG_TO_SMALL, KS_TYPE_SMALL_TO_BIG = 0, 1                      # keyswit
 EXPAND_KIND = {"no_casting": 0, "casting": 1, "sanity_check": 2}       # zk/zk_enums.h
 RERAND_WITH_KS, RERAND_WITHOUT_KS = 0, 1                               # integer/integer.h:45
 TRIVIUM_KEY_BITS, TRIVIUM_BATCH_SIZE, TRIVIUM_REGISTER_BITS = 80, 64, (93, 84, 111)   # trivium/trivium_utilities.h:5-12
+AES_BLOCK_BITS, AES_ROUND_KEYS, AES_PARALLELISMS = 128, 11, (16, 8, 4, 2, 1)             # aes/aes_utilities.h, radix/aes.rs
 
 
 class CudaServerKey:
@@ -599,6 +600,99 @@ class CudaServerKey:
             raise ValueError(f"The number of steps must be a multiple of {TRIVIUM_BATCH_SIZE}.")
         return self.trivium_next(self.trivium_init(key, iv, streams), num_steps, streams)
 
+    # ---- AES-128 transciphering (integer/gpu/server_key/radix/aes.rs)
+    def _aes_scratch(self, lib, s, mem, kind, allocate, num_aes_inputs=1, sbox_parallelism=16):
+        head = (s, C.byref(mem), self._bsk_params(), self._ksk_params(), self.message_modulus, self.carry_modulus, allocate,
+                self._noise_reduction())
+        if kind == "key_expansion":
+            return int(lib.hip_scratch_integer_key_expansion_64_async(*head))
+        return int(lib.hip_scratch_integer_aes_ctr_encrypt_64_async(*head, num_aes_inputs, sbox_parallelism))
+
+    def _aes_call(self, kind, streams, launch, counts, **shape):
+        """scratch -> launch -> cleanup of hip_integer_{aes_ctr_encrypt,key_expansion}_64; `counts` receives the published
+        bootstraps and rounds of the call"""
+        s, keep = self._streams(streams)
+        ksks, bsks = self._key_ptrs(streams)
+        mem = C.c_void_p()
+        lib = _lib()
+        self._aes_scratch(lib, s, mem, kind, True, **shape)
+        counts[:] = [int(lib.hip_integer_aes_pbs_count(mem)), int(lib.hip_integer_aes_rounds(mem))]
+        launch(lib, s, mem, bsks, ksks)
+        getattr(lib, f"hip_cleanup_integer_{kind}_64")(s, C.byref(mem))
+
+    def get_key_expansion_size_on_gpu(self, streams):
+        s, keep = self._streams(streams)
+        mem = C.c_void_p()
+        size = self._aes_scratch(_lib(), s, mem, "key_expansion", False)
+        _lib().hip_cleanup_integer_key_expansion_64(s, C.byref(mem))
+        return size
+
+    def get_aes_encrypt_size_on_gpu(self, num_aes_inputs, sbox_parallelism, streams):
+        s, keep = self._streams(streams)
+        mem = C.c_void_p()
+        size = self._aes_scratch(_lib(), s, mem, "aes_ctr_encrypt", False, num_aes_inputs, sbox_parallelism)
+        _lib().hip_cleanup_integer_aes_ctr_encrypt_64(s, C.byref(mem))
+        return size
+
+    @staticmethod
+    def _aes_result(ct, counts, return_pbs_count, return_rounds):
+        extra = ([counts[0]] if return_pbs_count else []) + ([counts[1]] if return_rounds else [])
+        return (ct, *extra) if extra else ct
+
+    def key_expansion(self, key, streams, return_pbs_count=False, return_rounds=False):
+        """The 11 round keys of AES-128 from 128 encrypted key bits (block i holds bit 127 - i): 1,408 blocks, round key r at
+        blocks 128 r .. 128 r + 127 in the same bit order, every block a clean bit."""
+        if key.total_blocks != AES_BLOCK_BITS:
+            raise ValueError(f"Input key must contain {AES_BLOCK_BITS} encrypted bits, but contains {key.total_blocks}")
+        w = key.lwe_dimension + 1
+        blocks = AES_ROUND_KEYS * AES_BLOCK_BITS
+        out = CudaUnsignedRadixCiphertext(CudaVec(blocks * w, streams), 1, blocks, key.lwe_dimension)
+        counts = []
+        self._aes_call("key_expansion", streams, lambda lib, s, mem, bsks, ksks: lib.hip_integer_key_expansion_64_async(
+            s, C.byref(out._ffi()), C.byref(key._ffi()), mem, bsks, ksks), counts)
+        return self._aes_result(out, counts, return_pbs_count, return_rounds)
+
+    def aes_encrypt(self, iv, round_keys, start_counter, num_aes_inputs, sbox_parallelism, streams, return_pbs_count=False,
+                    return_rounds=False):
+        """AES_k((iv + start_counter + n) mod 2^128) for n < num_aes_inputs under the expanded key: 128 blocks per input, input
+        n at blocks 128 n .., block i of an input holds bit 127 - i.  sbox_parallelism: state bytes per S-box pass."""
+        if iv.total_blocks != AES_BLOCK_BITS:
+            raise ValueError(f"AES IV must contain {AES_BLOCK_BITS} encrypted bits, but contains {iv.total_blocks}")
+        if round_keys.total_blocks != AES_ROUND_KEYS * AES_BLOCK_BITS:
+            raise ValueError(f"Round keys must contain {AES_ROUND_KEYS * AES_BLOCK_BITS} encrypted bits, but contain "
+                             f"{round_keys.total_blocks}")
+        if sbox_parallelism not in AES_PARALLELISMS:
+            raise ValueError(f"Invalid S-Box parallelism: must be one of [1, 2, 4, 8, 16], got {sbox_parallelism}")
+        if num_aes_inputs < 1:
+            raise ValueError("AES needs at least one input")
+        n = int(num_aes_inputs)
+        w = iv.lwe_dimension + 1
+        out = CudaUnsignedRadixCiphertext(CudaVec(AES_BLOCK_BITS * n * w, streams), 1, AES_BLOCK_BITS * n, iv.lwe_dimension)
+        bits = np.array([((int(start_counter) + i) >> b) & 1 for i in range(n) for b in range(AES_BLOCK_BITS)], dtype=U64)
+        counts = []
+        self._aes_call("aes_ctr_encrypt", streams, lambda lib, s, mem, bsks, ksks: lib.hip_integer_aes_ctr_encrypt_64_async(
+            s, C.byref(out._ffi()), C.byref(iv._ffi()), C.byref(round_keys._ffi()), bits.ctypes.data, n, mem, bsks, ksks),
+            counts, num_aes_inputs=n, sbox_parallelism=sbox_parallelism)
+        streams.synchronize()     # `bits` is host memory of this call
+        return self._aes_result(out, counts, return_pbs_count, return_rounds)
+
+    def aes_ctr_with_fixed_parallelism(self, key, iv, start_counter, num_aes_inputs, sbox_parallelism, streams):
+        """key_expansion, then aes_encrypt at the given S-box parallelism."""
+        if sbox_parallelism not in AES_PARALLELISMS:
+            raise ValueError(f"Invalid S-Box parallelism: must be one of [1, 2, 4, 8, 16], got {sbox_parallelism}")
+        return self.aes_encrypt(iv, self.key_expansion(key, streams), start_counter, num_aes_inputs, sbox_parallelism, streams)
+
+    def aes_ctr(self, key, iv, start_counter, num_aes_inputs, streams):
+        """AES-128 in counter mode on encrypted key and IV, at the largest S-box parallelism whose scratch fits the first GPU
+        of the stream set (aes.rs aes_ctr: 16, 8, .. 1, asked of cuda_check_valid_malloc)."""
+        gpu = streams.gpu_indexes[0]
+        if not _lib().cuda_check_valid_malloc(self.get_key_expansion_size_on_gpu(streams), gpu):
+            raise MemoryError("Not enough GPU memory for the AES key expansion")
+        for parallelism in AES_PARALLELISMS:
+            if _lib().cuda_check_valid_malloc(self.get_aes_encrypt_size_on_gpu(num_aes_inputs, parallelism, streams), gpu):
+                return self.aes_ctr_with_fixed_parallelism(key, iv, start_counter, num_aes_inputs, parallelism, streams)
+        raise MemoryError("Failed to allocate GPU memory for AES, even with the lowest parallelism setting.")
+
     def scalar_shift_assign(self, ct, shift, streams, left=True, arithmetic=False):
         """ct <<= shift / ct >>= shift (clear amount; radix/scalar_shift.rs unchecked_scalar_{left,right}_shift_assign).
         Logical: ONE integer.  arithmetic=True: the right shift of a two's complement value, every integer of the batch."""
@@ -827,6 +921,25 @@ class CudaUnsignedRadixCiphertext:
         _lib().hip_rerand_64_async(s, self.d_blocks.ptr, zeros.d_vec.ptr, mem, keys)
         _lib().hip_cleanup_rerand_64(s, C.byref(mem))
         self._info[1][:] = 1
+
+
+def encrypt_u128_for_aes_ctr(data):
+    """radix/aes.rs encrypt_u128_for_aes_ctr, the clear half: the 128 one-bit blocks of a 128-bit key, IV or block, most
+    significant bit first (block i holds bit 127 - i).  The caller encrypts each as one block."""
+    data = int(data)
+    if not 0 <= data < 1 << AES_BLOCK_BITS:
+        raise ValueError("an AES block has 128 bits")
+    return [(data >> (AES_BLOCK_BITS - 1 - i)) & 1 for i in range(AES_BLOCK_BITS)]
+
+
+def decrypt_u128_from_aes_ctr(bits, num_aes_inputs):
+    """radix/aes.rs decrypt_u128_from_aes_ctr, the clear half: the decrypted blocks of num_aes_inputs outputs back to 128-bit
+    integers."""
+    bits = [int(b) for b in bits]
+    if len(bits) != AES_BLOCK_BITS * num_aes_inputs or any(b not in (0, 1) for b in bits):
+        raise ValueError(f"expected {AES_BLOCK_BITS * num_aes_inputs} decrypted bits")
+    return [sum(b << (AES_BLOCK_BITS - 1 - i) for i, b in enumerate(bits[AES_BLOCK_BITS * n:AES_BLOCK_BITS * (n + 1)]))
+            for n in range(num_aes_inputs)]
 
 
 class CudaTriviumState:
